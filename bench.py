@@ -2,8 +2,20 @@
 """Headline benchmark (BASELINE.json): device-resident GiB/s of LZ4 block
 decompression, 4 MiB blocks, 4096 blocks in HBM per GPU (configs[1]).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
+
+A plain run does what the headline figure needs and nothing else: it builds
+the batch, warms up, times exactly K steps, writes its outputs when
+--dump-outputs is given, and prints one JSON result line.  --full adds the
+check of the decoded output, every sub-record below and the CPU legs (minutes
+of run time), and prints a compact summary record after the result line.
+
+--dump-outputs DIR writes what the last timed step left in the caller's
+buffers, as float32 / float64 .npy files: decoded.npy (a fixed, seeded sample
+of the decoded bytes, every byte when the output is small) and sizes.npy (the
+decoder's return value per block).  The inputs depend on the arguments alone,
+so two builds can be compared file for file.
 
 `python bench.py --gpus N` with N > 1 and no torchrun environment starts the N
 ranks itself (torch.distributed.run as a child process, before anything here
@@ -14,10 +26,10 @@ Blocks are independent, so ranks shard them with no data-path collective
 (weak scaling: every rank decodes its own 4096 blocks); torch.distributed is
 used only for the barrier and the max-over-ranks time.  Inputs are synthetic
 text-like blocks generated on the GPU and compressed by the GPU
-encoder (byte-identical to LZ4_compress_default) before timing; the decoded
-output is checked against the original on the device after timing.
+encoder (byte-identical to LZ4_compress_default) before timing; with --full
+the decoded output is checked against the original on the device after timing.
 
-Sub-records of the same JSON line (each names its BASELINE config):
+Sub-records of the same JSON line with --full (each names its BASELINE config):
   configs_3        Zstd level-3 decode, 4096 x 4 MiB frames in HBM, every rank
   configs_2        LZ4 compress + decompress, 2048 blocks per GPU, block i on
                    rank i % N (round robin), every block verified, every rank
@@ -78,6 +90,11 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--full", action="store_true",
+                   help="also verify the decoded output and run every sub-record and CPU leg (the --no-* and "
+                        "sub-record options below apply only with --full)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs to DIR/<name>.npy (float32/float64, <= 64 MB)")
     p.add_argument("--blocks", type=int, default=4096)
     p.add_argument("--block-bytes", type=int, default=4 << 20)
     p.add_argument("--cls", default="T")
@@ -874,6 +891,28 @@ def measured_traffic(path, nblk, U, sources=KERNEL_SOURCES):
     return tj.get("hbm_bytes_per_launch"), f"rocprofv3 PMC FETCH_SIZE/WRITE_SIZE ({stamp})"
 
 
+DUMP_SAMPLE = 8 << 20  # decoded bytes kept by --dump-outputs (32 MiB as float32)
+
+
+def dump_outputs(batch, dirpath, seed=20240917):
+    """--dump-outputs: what a caller of batch.decompress holds after the last
+    timed step.  decoded.npy = the output buffer's bytes as float32, all of
+    them up to DUMP_SAMPLE, else the bytes at DUMP_SAMPLE seeded random
+    offsets (ascending; the same offsets for the same blocks x block_bytes);
+    sizes.npy = the per-block return values as float64."""
+    import torch
+    if batch.out.is_cuda:
+        torch.cuda.synchronize()
+    os.makedirs(dirpath, exist_ok=True)
+    n = batch.out.numel()
+    sample = batch.out
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(seed).integers(0, n, DUMP_SAMPLE, dtype=np.int64))
+        sample = batch.out[torch.from_numpy(idx).to(batch.out.device)]
+    np.save(os.path.join(dirpath, "decoded.npy"), sample.to(torch.float32).cpu().numpy())
+    np.save(os.path.join(dirpath, "sizes.npy"), batch.dec_ret.to(torch.float64).cpu().numpy())
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -908,7 +947,9 @@ def main():
     # barrier + synchronize on both sides of exactly a.steps steps; max over ranks
     elapsed, kms = timed_launches(batch.decompress, a.steps, a.warmup, S, world, dev)
     kern_s = kms / 1e3
-    if not S.all_ranks_ok(batch.verify(), world, dev):
+    if a.dump_outputs and rank == 0:
+        dump_outputs(batch, a.dump_outputs)
+    if a.full and not S.all_ranks_ok(batch.verify(), world, dev):
         raise SystemExit("decoded output mismatch: benchmark invalid")
 
     ms_per_step = elapsed / a.steps * 1e3
@@ -953,7 +994,7 @@ def main():
         },
         "setup_s": setup_s,
     }
-    extras = not a.no_extras
+    extras = a.full and not a.no_extras
     if extras and a.codec == "lz4":
         try:
             _mark("configs_3")
@@ -991,7 +1032,7 @@ def main():
             except Exception as e:
                 out["dealer_all_gpus"] = {"error": repr(e)}
         S._barrier(world)
-    if rank == 0 and world == 1:
+    if a.full and rank == 0 and world == 1:
         # bounded sample for the CPU legs: 32 distinct blocks of the headline batch
         ns = min(32, nblk)
         comp_blocks = [batch.comp[i * batch.slot:i * batch.slot + int(batch.csize[i])].cpu().numpy().tobytes()
@@ -1052,10 +1093,11 @@ def main():
                         out["mixed_host_path"] = {"error": repr(e)}
     if rank == 0:
         print(json.dumps(out), flush=True)
-        # the full line is ~45 KB and a driver may keep only the tail of stdout:
-        # a compact record (the same top-level fields, so it is itself a valid
-        # result line) carrying every leg's headline figures follows it
-        print(json.dumps(summary_record(out)), flush=True)
+        if a.full:
+            # the full line is ~45 KB and a driver may keep only the tail of stdout:
+            # a compact record (the same top-level fields, so it is itself a valid
+            # result line) carrying every leg's headline figures follows it
+            print(json.dumps(summary_record(out)), flush=True)
     if world > 1:
         dist.destroy_process_group()
 

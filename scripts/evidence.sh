@@ -28,7 +28,7 @@ timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE -d $T/zpw -o zpw --output-format 
 timeout -s KILL 120 rocprofv3 --pmc $SQC -d $T/zpi -o zpi --output-format csv -- python scripts/prof_run.py 4096 1 T zstd > $O/zpi.log 2>&1
 python scripts/pmc_summary.py $(find $T/zpi -name '*counter_collection.csv' | head -1) --kernel z > $O/pmc_zstd_decode.txt
 python scripts/traffic_zstd.py $(find $T/zpf -name '*counter_collection.csv' | head -1) $(find $T/zpw -name '*counter_collection.csv' | head -1) 4096 4194304 $O/traffic_zstd.json > /dev/null
-timeout -k 10 900 python bench.py --traffic-file $O/traffic.json --zstd-traffic-file $O/traffic_zstd.json > $O/bench.json 2> $O/bench.err
+timeout -k 10 900 python bench.py --full --traffic-file $O/traffic.json --zstd-traffic-file $O/traffic_zstd.json > $O/bench.json 2> $O/bench.err
 tail -c 400 $O/bench.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $T/kt_lz4 -o kt --output-format csv -- python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-extras --no-host-path --traffic-file $O/traffic.json > $O/kt_lz4.log 2>&1
 find $T/kt_lz4 -name '*kernel_stats.csv' -exec cp {} $O/lz4_kernel_stats.csv \;

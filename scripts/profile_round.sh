@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 O=gpurun_out/prof
 mkdir -p $O
 if [ "$what" = lz4 ] || [ "$what" = all ]; then
-  timeout -k 10 400 python bench.py > $O/bench_lz4.json 2> $O/bench_lz4.err
+  timeout -k 10 400 python bench.py --full > $O/bench_lz4.json 2> $O/bench_lz4.err
   tail -1 $O/bench_lz4.json
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/kt_lz4 -o kt --output-format csv -- python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-extras --no-host-path > $O/kt_lz4.log 2>&1
   find $O/kt_lz4 -name '*kernel_stats.csv' -exec cp {} $O/lz4_kernel_stats.csv \;
@@ -19,7 +19,7 @@ if [ "$what" = lz4 ] || [ "$what" = all ]; then
   python scripts/traffic.py $(find $O/pf -name '*counter_collection.csv' | head -1) $(find $O/pw -name '*counter_collection.csv' | head -1) lz4_decode_kernel 4096 4194304 $O/traffic.json
 fi
 if [ "$what" = zstd ] || [ "$what" = all ]; then
-  timeout -k 10 300 python bench.py --codec zstd > $O/bench_zstd.json 2> $O/bench_zstd.err
+  timeout -k 10 300 python bench.py --full --codec zstd > $O/bench_zstd.json 2> $O/bench_zstd.err
   tail -1 $O/bench_zstd.json
   # (libzstd is not loaded under the profiler: the conda libzstd clashes with the
   # profiler's own; the frames come from a cache written by an unprofiled run)
