@@ -309,6 +309,87 @@ int64_t jfs_lz4_compress_seal_device(const jfs_dev_block *d_comp, const jfs_aead
 int64_t jfs_open_lz4_decompress_device(const jfs_aead_block *d_aead, const jfs_dev_block *d_dec, int nblk,
                                        int32_t *d_ret_open, int32_t *d_ret, void *stream);
 
+/* ---- Slice compaction (pkg/vfs/compact.go:54-108) --------------------------
+ * Compact reads byte ranges [s.Off, s.Off+s.Len) of N existing slices (zeros
+ * for holes, s.Id == 0, :70-77), concatenates them, re-cuts the stream at
+ * BlockSize and uploads each new block through Compress; on the read side
+ * every touched block is decompressed whole (cached_store.go:177).  These
+ * calls do decode -> gather -> re-encode without the decoded bytes leaving
+ * HBM.  The plan: every output block is a run of segments that tile
+ * [0, total) in order -- seg[k].dst_off == seg[k-1].dst_off + seg[k-1].len,
+ * the first 0 (the caller fills dst_off, so the kernel needs no scan). */
+typedef struct jfs_compact_seg {
+    int32_t src;     /* index of the decoded source block, or -1: `len` zero bytes (a hole) */
+    int32_t src_off; /* first byte inside the decoded source block (ignored for src = -1) */
+    int32_t dst_off; /* where the bytes go inside the output block */
+    int32_t len;     /* > 0 */
+} jfs_compact_seg;
+
+typedef struct jfs_compact_out {
+    uint8_t *dst;      /* gathered (uncompressed) output block */
+    int32_t dst_cap;
+    int32_t seg_first; /* this block's segments are seg[seg_first .. seg_first+seg_count) */
+    int32_t seg_count; /* 0 is legal: an empty block */
+    int32_t reserved;
+} jfs_compact_out;
+
+/* The gather alone, device-resident.  d_src[i].dst / d_src_n[i]: decoded source
+ * block i and its decoded length as a decoder's d_ret wrote it (negative = that
+ * source failed; d_src[i].dst_cap bounds it too).  d_ret[j] = bytes gathered
+ * into d_out[j].dst; JFS_CHAIN_FAILED (INT32_MIN) when a segment of block j
+ * reads a failed source or reaches past d_src_n[src]; -1 for a bad plan (src
+ * outside [-1, nsrc), negative offsets, len <= 0, broken tiling, total >
+ * dst_cap; a bad plan wins over a failed source).  Nothing outside
+ * dst[0, total) is ever written, and nothing at all for a block that is not
+ * gathered.  max_dst_cap: a HOST value >= every d_out[j].dst_cap (it sizes the
+ * launch).  Asynchronous on `stream`. */
+int64_t jfs_gather_device(const jfs_dev_block *d_src, const int32_t *d_src_n, int nsrc, const jfs_compact_out *d_out,
+                          int nout, const jfs_compact_seg *d_seg, int32_t max_dst_cap, int32_t *d_ret, void *stream);
+
+/* decode d_src (LZ4 blocks) -> gather -> LZ4_compress_default of every gathered
+ * block, chained on `stream` with no host round trip.  d_src_ret[i] = the
+ * LZ4_decompress_safe result; d_gather[j].dst is the intermediate gathered
+ * block; d_enc[j].src must be that buffer (its src_len must equal the block's
+ * planned total), d_enc[j].dst receives the compressed block.  d_ret[j] =
+ * compressed size, 0 when it does not fit, JFS_CHAIN_FAILED / -1 as
+ * jfs_gather_device (the encoder may run on a block whose gather failed; its
+ * result is replaced by the gather's verdict). */
+int64_t jfs_lz4_compact_device(const jfs_dev_block *d_src, int nsrc, int32_t *d_src_ret,
+                               const jfs_compact_out *d_gather, const jfs_compact_seg *d_seg,
+                               const jfs_dev_block *d_enc, int nout, int32_t max_dst_cap, int32_t *d_ret,
+                               void *stream);
+
+/* Host buffers (what a Go Compact adapter calls).  src[i].src/src_len: stored
+ * object i; src[i].dst_cap: its block size (src[i].dst is ignored: the decoded
+ * block never reaches the host).  out[j].dst/dst_cap receives new stored
+ * object j (out[j].src/src_len are ignored); its segments are
+ * seg[seg_first[j] .. seg_first[j+1]) (seg_first has nout+1 entries).
+ * src_n[i] = what jfs_decompress would have returned for source i; out_n[j] =
+ * what jfs_compress would have returned for the gathered bytes of block j,
+ * byte for byte (Zstd's dst_cap < CompressBound rule and LZ4's "does not fit"
+ * included), or JFS_ERR_CORRUPT when a source feeding block j failed or is
+ * shorter than a segment needs (this wins over the block's own codec error);
+ * crc (may be NULL) as jfs_compress_batch_crc.  Errors are per block: blocks
+ * that depend only on good sources succeed (the reference aborts the whole
+ * compaction on any error, compact.go:83-88: that decision stays with the
+ * caller), and a plan may hold several independent compactions.  algo: LZ4,
+ * Zstd or none (decode is then a copy, the output the gathered bytes).
+ * The plan is checked on the host first: bad indices, broken tiling, len <= 0,
+ * a non-monotone seg_first, NULL pointers, negative sizes or sizes beyond
+ * int32 return JFS_ERR_INVALID; then JFS_ERR_NO_DEVICE without a usable device.
+ * One call runs on ONE device of device_mask (a compaction's sources and
+ * outputs are coupled, so the call is not dealt across devices; concurrent
+ * calls take turns over the devices).  Only compressed bytes cross the host
+ * link, in both directions.  If the device scratch for the decoded sources
+ * and gathered blocks cannot be allocated every src_n[i] and out_n[j] is
+ * JFS_ERR_NO_MEMORY (JFS_ERR_HIP after a runtime failure); the call still
+ * returns JFS_OK.  jfs_stats counts the sources under (algo, decompress) and
+ * the outputs under (algo, compress).  The calling thread's current HIP
+ * device is unchanged on return. */
+int64_t jfs_compact_batch(int algo, int nsrc, const jfs_iov *src, int nout, const jfs_iov *out,
+                          const int32_t *seg_first /* nout+1 */, const jfs_compact_seg *seg, int64_t *src_n,
+                          int64_t *out_n, uint32_t *crc /* may be NULL */, uint32_t device_mask);
+
 /* ---- Runtime / utilities ------------------------------------------------- */
 
 /* Number of usable gfx950 devices (0 when none; never an error).  Only the

@@ -38,6 +38,7 @@ EXPORTS = [
     "jfs_aead_open_device", "jfs_envelope_bound", "jfs_envelope_parse", "jfs_compress_seal_batch",
     "jfs_open_decompress_batch", "jfs_compress_batch_crc", "jfs_decompress_batch_csum", "jfs_deal_plan",
     "jfs_test_spread_locking", "jfs_compress_batch_mixed", "jfs_decompress_batch_mixed",
+    "jfs_gather_device", "jfs_lz4_compact_device", "jfs_compact_batch",
 ]
 
 MODE_OFF, MODE_AUTO, MODE_FORCE = 0, 1, 2
@@ -68,6 +69,17 @@ class JfsSealParam(ctypes.Structure):
 class JfsDevBlock(ctypes.Structure):
     _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p),
                 ("src_len", ctypes.c_int32), ("dst_cap", ctypes.c_int32)]
+
+
+class JfsCompactSeg(ctypes.Structure):
+    """src = -1: a hole of `len` zero bytes"""
+    _fields_ = [("src", ctypes.c_int32), ("src_off", ctypes.c_int32), ("dst_off", ctypes.c_int32),
+                ("len", ctypes.c_int32)]
+
+
+class JfsCompactOut(ctypes.Structure):
+    _fields_ = [("dst", ctypes.c_void_p), ("dst_cap", ctypes.c_int32), ("seg_first", ctypes.c_int32),
+                ("seg_count", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 _lib = None
@@ -146,6 +158,14 @@ def load() -> ctypes.CDLL:
     for f in (lib.jfs_lz4_compress_seal_device, lib.jfs_open_lz4_decompress_device):
         f.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp]
         f.restype = i64
+    lib.jfs_gather_device.argtypes = [vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, i32, vp, vp]
+    lib.jfs_gather_device.restype = i64
+    lib.jfs_lz4_compact_device.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, ctypes.c_int, i32, vp, vp]
+    lib.jfs_lz4_compact_device.restype = i64
+    lib.jfs_compact_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(JfsIov), ctypes.c_int,
+                                      ctypes.POINTER(JfsIov), ctypes.POINTER(i32), ctypes.POINTER(JfsCompactSeg),
+                                      ctypes.POINTER(i64), ctypes.POINTER(i64), vp, u32]
+    lib.jfs_compact_batch.restype = i64
     lib.jfs_release_staging.argtypes = []
     lib.jfs_release_staging.restype = None
     lib.jfs_device_count.argtypes = []

@@ -128,6 +128,59 @@ class Compressor:
         pkg/object/checksum.go:30-45): [(n, err, crc)]"""
         return _batch(self.algo, pairs, device_mask, compress=True, with_crc=True)
 
+    def CompactBatch(self, sources, outputs, plan, device_mask: int = 0, with_crc: bool = False):
+        """Slice compaction on one GPU (jfs_compact_batch): decode the stored
+        source objects, gather the planned byte ranges into new blocks and
+        compress those, without a decoded byte leaving HBM.
+
+        sources: list of (stored_object, block_size); outputs: list of writable
+        dst buffers, one per new block; plan: (seg_first, seg) as compact_plan
+        returns them, seg entries (src, src_off, dst_off, len) with src = -1
+        for a hole.  Returns (src_results, out_results[, crcs]): [(n, err)] as
+        DecompressBatch would give for the sources and as CompressBatch would
+        give for the gathered blocks (JFS_ERR_CORRUPT for a block fed by a
+        failed or short source), plus each payload's CRC-32C with with_crc."""
+        lib = L.load()
+        seg_first, seg = plan
+        ns, no = len(sources), len(outputs)
+        if len(seg_first) != no + 1:
+            raise ValueError("seg_first must have one entry per output plus one")
+        siov, oiov = (L.JfsIov * max(ns, 1))(), (L.JfsIov * max(no, 1))()
+        keep = []
+        for i, (obj, block_size) in enumerate(sources):
+            s, sn, ks = _addr(obj, False)
+            keep.append(ks)
+            siov[i].src, siov[i].src_len, siov[i].dst, siov[i].dst_cap = s, sn, None, int(block_size)
+        for j, dst in enumerate(outputs):
+            d, dn, kd = _addr(dst, True)
+            keep.append(kd)
+            oiov[j].src, oiov[j].src_len, oiov[j].dst, oiov[j].dst_cap = None, 0, d, dn
+        first = (ctypes.c_int32 * (no + 1))(*[int(x) for x in seg_first])
+        segs = (L.JfsCompactSeg * max(len(seg), 1))()
+        for k, (src, src_off, dst_off, n) in enumerate(seg):
+            segs[k].src, segs[k].src_off, segs[k].dst_off, segs[k].len = int(src), int(src_off), int(dst_off), int(n)
+        src_n, out_n = (ctypes.c_int64 * max(ns, 1))(), (ctypes.c_int64 * max(no, 1))()
+        crc = (ctypes.c_uint32 * max(no, 1))()
+        rc = lib.jfs_compact_batch(self.algo, ns, siov, no, oiov, first, segs, src_n, out_n, crc if with_crc else None,
+                                   device_mask)
+        if rc != 0:
+            raise _err(rc, 0, 0, "compact")
+        src_res, out_res = [], []
+        for i in range(ns):
+            r = int(src_n[i])
+            if r < 0:
+                n = r if (self.algo == L.ALGO_LZ4 and r > L.JFS_ERR_BASE) else 0
+                src_res.append((n, _err(r, siov[i].dst_cap, siov[i].src_len, "decompress")))
+            else:
+                src_res.append((r, None))
+        for j in range(no):
+            r = int(out_n[j])
+            total = sum(s[3] for s in seg[seg_first[j]:seg_first[j + 1]])
+            out_res.append((0, _err(r, oiov[j].dst_cap, total, "compress")) if r < 0 else (r, None))
+        if with_crc:
+            return src_res, out_res, [int(crc[j]) for j in range(no)]
+        return src_res, out_res
+
 
 class noOp(Compressor):  # noqa: N801  (reference name, compress.go:51)
     algo = L.ALGO_NONE
@@ -158,6 +211,57 @@ def NewCompressor(algr: str):
     if a == L.ALGO_NONE:
         return noOp()
     return None
+
+
+def compact_plan(slices, block_size: int, src_block_size: int | None = None):
+    """The gather plan of pkg/vfs/compact.go:54-108 (Compact + readSlice).
+
+    slices: [(id, size, off, len)] in write order -- bytes [off, off+len) of
+    slice `id`, which is `size` bytes long and stored in blocks cut at
+    src_block_size (default block_size); id == 0 is a hole of `len` zero bytes
+    (compact.go:70-77).  The new slice is their concatenation, cut at
+    block_size (the last block is ragged).
+
+    Returns (sources, seg_first, seg): sources = [(slice_index, block_index,
+    block_len)], the stored blocks to fetch, each once, in first-use order
+    (slice_index: the first entry of `slices` that names the slice);
+    seg = [(src, src_off, dst_off, len)] with src an index into sources or -1
+    for a hole, and seg_first (one entry per new block, plus one) delimiting
+    each new block's segments -- the arguments of jfs_compact_batch."""
+    S = int(src_block_size or block_size)
+    B = int(block_size)
+    if B <= 0 or S <= 0:
+        raise ValueError("block sizes must be positive")
+    sources, index, seg, seg_first = [], {}, [], []
+    pos = 0  # position in the new slice
+
+    def put(src, src_off, n):
+        nonlocal pos
+        while n > 0:  # cut at the new block boundaries
+            take = min(n, B - pos % B)
+            while len(seg_first) <= pos // B:
+                seg_first.append(len(seg))
+            seg.append((src, src_off, pos % B, take))
+            pos, src_off, n = pos + take, src_off + take, n - take
+
+    for si, (sid, size, off, ln) in enumerate(slices):
+        if ln < 0 or (sid != 0 and (off < 0 or off + ln > size)):
+            raise ValueError(f"slice {si}: [{off}, {off + ln}) outside its {size} bytes")
+        if sid == 0:
+            put(-1, 0, ln)
+            continue
+        p, end = off, off + ln
+        while p < end:  # cut at the stored blocks' boundaries
+            b = p // S
+            take = min(end, (b + 1) * S) - p
+            key = (sid, size, b)
+            if key not in index:
+                index[key] = len(sources)
+                sources.append((si, b, min(S, size - b * S)))
+            put(index[key], p - b * S, take)
+            p += take
+    seg_first.append(len(seg))
+    return sources, seg_first, seg
 
 
 CSUM_BLOCK = 32 << 10  # disk_cache_file.go csBlock

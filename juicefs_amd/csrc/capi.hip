@@ -1879,6 +1879,217 @@ int64_t batch_common(int algo, int dir, int nblk, const jfs_iov *iov, int64_t *o
     return deal(algo, dir, todo, iov2, out_n, mask, nullptr, crc, csum);
 }
 
+// ---------------------------------------------------------------------------
+// compaction: decode -> gather -> encode on one device (jfs_compact_batch)
+// ---------------------------------------------------------------------------
+// One source / output the device works on (the others were answered on the
+// host); idx = its position in the caller's arrays.
+struct CompactSrc {
+    int idx;
+    int64_t cap;  // staged decode capacity (staged_cap)
+};
+struct CompactOut {
+    int idx;
+    int64_t total;  // gathered bytes
+    int64_t cap;    // staged encode capacity
+};
+
+// Runs the whole chain on one lane (the caller holds ln.mu) in a single pass
+// on the lane's kernel stream: compressed sources and the plan H2D, decode,
+// gather, encode, checksums, results D2H, then exactly the compressed bytes
+// D2H.  Staging comes from the lane's slots: slot 0's pinned/HBM pair for what
+// crosses the link, slot 0's device scratch for the decoded sources and the
+// gathered blocks, slots 1 and 2's for the small-batch encoder and decoder.
+// src_map[i]: source i's position in `ss`, or -1 (answered on the host: it
+// counts as failed).  Returns JFS_OK with src_n / out_n / crc of these blocks
+// filled, or JFS_ERR_NO_MEMORY / JFS_ERR_HIP with nothing filled.
+int64_t compact_run(DevCtx *dev, Lane &ln, int algo, const jfs_iov *src, const std::vector<CompactSrc> &ss,
+                    const std::vector<int> &src_map, const jfs_iov *out, const std::vector<CompactOut> &oo,
+                    const int32_t *seg_first, const jfs_compact_seg *seg, int64_t *src_n, int64_t *out_n,
+                    uint32_t *crc) {
+    DevGuard guard;
+    (void)hipSetDevice(dev->id);
+    dev->last_use_ms = steady_ms();
+    ln.kind.store(algo * 2 + COMPRESS, std::memory_order_relaxed);
+    dev->batches.fetch_add(1, std::memory_order_relaxed);
+    dev->blocks.fetch_add((uint64_t)(ss.size() + oo.size()), std::memory_order_relaxed);
+    start_janitor();
+    struct Touch {
+        DevCtx *d;
+        ~Touch() { d->last_use_ms = steady_ms(); }
+    } touch{dev};
+    const bool codec = algo != JFS_ALGO_NONE;
+    const int ns = (int)ss.size(), no = (int)oo.size();
+    // staged area, mirrored pinned / HBM: [compressed sources | meta | compressed outputs]
+    // meta: source descriptors (ns + 1: the last one is "a failed source"),
+    // output plan, segments, encoder and checksum descriptors, then the three
+    // result arrays (source lengths, output results, checksums) back to back
+    std::vector<int64_t> in_off(ns), out_off(no), dec_off(ns), gat_off(no);
+    int64_t tin = 0, tout = 0, scratch = 0, nseg = 0;
+    int32_t max_total = 0;
+    for (int k = 0; k < ns; k++) {
+        in_off[k] = tin;
+        tin += align16(src[ss[k].idx].src_len);
+        if (codec) {
+            dec_off[k] = scratch;
+            scratch += align16(ss[k].cap);
+        }
+    }
+    for (int k = 0; k < no; k++) {
+        out_off[k] = tout;
+        tout += align16(oo[k].cap);
+        if (codec) {
+            gat_off[k] = scratch;
+            scratch += align16(oo[k].total);
+        }
+        nseg += seg_first[oo[k].idx + 1] - seg_first[oo[k].idx];
+        max_total = (int32_t)std::max<int64_t>(max_total, oo[k].total);
+    }
+    const int64_t o_sdesc = tin;
+    const int64_t o_plan = o_sdesc + align16((int64_t)(ns + 1) * (int64_t)sizeof(jfs_dev_block));
+    const int64_t o_seg = o_plan + align16((int64_t)no * (int64_t)sizeof(jfs_compact_out));
+    const int64_t o_enc = o_seg + align16(nseg * (int64_t)sizeof(jfs_compact_seg));
+    const int64_t o_cd = o_enc + align16((int64_t)no * (int64_t)sizeof(jfs_dev_block));
+    const int64_t o_srcn = o_cd + align16((int64_t)no * (int64_t)sizeof(jfs_dev_block));
+    const int64_t o_ret = o_srcn + align16((int64_t)(ns + 1) * 4);
+    const int64_t o_crc = o_ret + align16((int64_t)no * 4);
+    const int64_t o_out = o_crc + align16((int64_t)no * 4);
+    Slot &sl = ln.slot[0];
+    if (!sl.ensure(o_out + tout)) return JFS_ERR_NO_MEMORY;
+    if (codec && !sl.ensure_split(std::max<int64_t>(scratch, 16))) return JFS_ERR_NO_MEMORY;
+    uint8_t *h = sl.h, *d = sl.d;
+    jfs_dev_block *h_sdesc = (jfs_dev_block *)(h + o_sdesc), *h_enc = (jfs_dev_block *)(h + o_enc),
+                  *h_cd = (jfs_dev_block *)(h + o_cd);
+    jfs_compact_out *h_plan = (jfs_compact_out *)(h + o_plan);
+    jfs_compact_seg *h_seg = (jfs_compact_seg *)(h + o_seg);
+    int32_t *h_srcn = (int32_t *)(h + o_srcn), *h_ret = (int32_t *)(h + o_ret);
+    uint32_t *h_crc = (uint32_t *)(h + o_crc);
+    const jfs_dev_block *d_sdesc = (const jfs_dev_block *)(d + o_sdesc), *d_enc = (const jfs_dev_block *)(d + o_enc),
+                        *d_cd = (const jfs_dev_block *)(d + o_cd);
+    int32_t *d_srcn = (int32_t *)(d + o_srcn), *d_ret = (int32_t *)(d + o_ret);
+    std::vector<CopyJob> jobs;
+    for (int k = 0; k < ns; k++) {
+        const jfs_iov &v = src[ss[k].idx];
+        if (v.src_len > 0) jobs.push_back({h + in_off[k], v.src, v.src_len});
+        // "none": the stored object is the decoded block
+        uint8_t *dec = codec ? sl.sp + dec_off[k] : d + in_off[k];
+        h_sdesc[k] = jfs_dev_block{d + in_off[k], dec, (int32_t)v.src_len, (int32_t)(codec ? ss[k].cap : v.src_len)};
+        h_srcn[k] = codec ? -1 : (int32_t)v.src_len;  // a decoder overwrites it
+    }
+    h_sdesc[ns] = jfs_dev_block{nullptr, nullptr, 0, 0};
+    h_srcn[ns] = -1;
+    par_copy(jobs);
+    int64_t sg = 0;
+    for (int k = 0; k < no; k++) {
+        const int j = oo[k].idx;
+        const int cnt = seg_first[j + 1] - seg_first[j];
+        uint8_t *gat = codec ? sl.sp + gat_off[k] : d + o_out + out_off[k];
+        h_plan[k] = jfs_compact_out{gat, (int32_t)oo[k].total, (int32_t)sg, cnt, 0};
+        for (int q = 0; q < cnt; q++) {
+            jfs_compact_seg s = seg[seg_first[j] + q];
+            if (s.src >= 0) s.src = src_map[s.src] >= 0 ? src_map[s.src] : ns;
+            h_seg[sg + q] = s;
+        }
+        sg += cnt;
+        h_enc[k] = jfs_dev_block{gat, d + o_out + out_off[k], (int32_t)oo[k].total, (int32_t)oo[k].cap};
+        h_cd[k] = jfs_dev_block{d + o_out + out_off[k], nullptr, 0, 0};
+    }
+    // the small-batch LZ4 decoder and encoder run one after the other on the
+    // stream: they share slot 1's scratch, sized for both before anything is queued
+    Slot &s1 = ln.slot[1];
+    const bool split_dec = algo == JFS_ALGO_LZ4 && ns > 0 && ns <= split_max();
+    const bool seg_enc = algo == JFS_ALGO_LZ4 && no > 0 && no <= eseg_max();
+    {
+        int64_t need = 0;
+        if (split_dec) {
+            std::vector<int32_t> lens(ns), caps(ns);
+            for (int k = 0; k < ns; k++) {
+                lens[k] = h_sdesc[k].src_len;
+                caps[k] = h_sdesc[k].dst_cap;
+            }
+            need = jfs_lz4_split_scratch_bytes(ns, lens.data(), caps.data());
+        }
+        if (seg_enc) {
+            std::vector<int32_t> lens(no);
+            for (int k = 0; k < no; k++) lens[k] = h_enc[k].src_len;
+            need = std::max(need, jfs_lz4_eseg_scratch_bytes(no, lens.data()));
+        }
+        if (need > 0 && !s1.ensure_split(need)) return JFS_ERR_NO_MEMORY;
+    }
+    hipStream_t ks = ln.s_k;
+    // one H2D: compressed sources, the plan and the preset result arrays
+    if (hipMemcpyAsync(d, h, (size_t)o_ret, hipMemcpyHostToDevice, ks) != hipSuccess) return JFS_ERR_HIP;
+    int lk = 0;
+    if (algo == JFS_ALGO_LZ4 && ns > 0) {
+        if (split_dec) {
+            std::vector<int32_t> lens(ns), caps(ns);
+            int64_t nsg = 0, max_cap = 0, norg = 0;
+            for (int k = 0; k < ns; k++) {
+                lens[k] = h_sdesc[k].src_len;
+                caps[k] = h_sdesc[k].dst_cap;
+                nsg += (std::max(lens[k], 0) + JFS_LZ4_SPLIT_SEG - 1) / JFS_LZ4_SPLIT_SEG;
+                max_cap = std::max<int64_t>(max_cap, caps[k]);
+                norg += (std::max<int64_t>(caps[k], 0) + 3) & ~3ll;
+            }
+            lk = jfs_launch_lz4_split(d_sdesc, ns, d_srcn, s1.sp, nsg, max_cap, norg, ks);
+        } else {
+            lk = jfs_launch_lz4_decode(d_sdesc, ns, d_srcn, ks);
+        }
+    } else if (algo == JFS_ALGO_ZSTD && ns > 0) {
+        lk = jfs_launch_zstd_decode(d_sdesc, ns, d_srcn, nullptr, ks);  // plans its own scratch
+    }
+    const jfs_compact_out *d_plan = (const jfs_compact_out *)(d + o_plan);
+    const jfs_compact_seg *d_seg = (const jfs_compact_seg *)(d + o_seg);
+    if (lk == 0) lk = jfs_launch_gather(d_sdesc, d_srcn, ns + 1, d_plan, no, d_seg, max_total, d_ret, 0, ks);
+    if (lk == 0 && codec && no > 0) {
+        if (seg_enc) {
+            std::vector<int32_t> lens(no);
+            for (int k = 0; k < no; k++) lens[k] = h_enc[k].src_len;
+            lk = jfs_launch_lz4_encode_seg(d_enc, no, lens.data(), d_ret, s1.sp, s1.sp_cap, ks);
+        } else {
+            lk = launch_kernel(algo, COMPRESS, d_enc, no, d_ret, ks);
+        }
+        // the encoder ran on every block: a failed gather's verdict replaces its result
+        if (lk == 0) lk = jfs_launch_gather(d_sdesc, d_srcn, ns + 1, d_plan, no, d_seg, max_total, d_ret, 1, ks);
+    }
+    if (lk == 0 && crc && no > 0)
+        lk = jfs_launch_crc32c_lens(d_cd, no, d_ret, nullptr, (uint32_t *)(d + o_crc), ks);
+    if (lk != 0 || hipMemcpyAsync(h + o_srcn, d + o_srcn, (size_t)(o_out - o_srcn), hipMemcpyDeviceToHost, ks) !=
+                       hipSuccess ||
+        hipStreamSynchronize(ks) != hipSuccess) {
+        (void)hipStreamSynchronize(ks);
+        return JFS_ERR_HIP;
+    }
+    // exactly the compressed bytes come back
+    for (int k = 0; k < no; k++) {
+        const int64_t n = h_ret[k];
+        if (n > 0 && hipMemcpyAsync(h + o_out + out_off[k], d + o_out + out_off[k], (size_t)n, hipMemcpyDeviceToHost,
+                                    ks) != hipSuccess) {
+            (void)hipStreamSynchronize(ks);
+            return JFS_ERR_HIP;
+        }
+    }
+    if (hipStreamSynchronize(ks) != hipSuccess) return JFS_ERR_HIP;
+    jobs.clear();
+    for (int k = 0; k < ns; k++)
+        src_n[ss[k].idx] = codec ? finish_result(algo, DECOMPRESS, h_srcn[k]) : (int64_t)h_srcn[k];
+    for (int k = 0; k < no; k++) {
+        const int j = oo[k].idx;
+        const int32_t raw = h_ret[k];
+        int64_t r;
+        if (raw == JFS_CHAIN_FAILED) r = JFS_ERR_CORRUPT;
+        else if (codec) r = finish_result(algo, COMPRESS, raw);
+        else r = raw >= 0 ? (int64_t)raw : JFS_ERR_INVALID;
+        out_n[j] = r;
+        if (crc) crc[j] = r >= 0 ? h_crc[k] : 0u;
+        if (r > 0) jobs.push_back({out[j].dst, h + o_out + out_off[k], r});
+    }
+    par_copy(jobs);
+    return JFS_OK;
+}
+
+std::atomic<unsigned> g_compact_turn{0};
+
 }  // namespace
 
 extern "C" {
@@ -2397,6 +2608,119 @@ int64_t jfs_open_lz4_decompress_device(const jfs_aead_block *d_aead, const jfs_d
     hipStream_t st = (hipStream_t)stream;
     if (jfs_launch_aes256gcm(d_aead, nblk, 1, d_ret_open, nullptr, st) != 0) return JFS_ERR_HIP;
     return jfs_launch_lz4_decode_lens(d_dec, nblk, d_ret, d_ret_open, st) == 0 ? JFS_OK : JFS_ERR_HIP;
+}
+
+int64_t jfs_gather_device(const jfs_dev_block *d_src, const int32_t *d_src_n, int nsrc, const jfs_compact_out *d_out,
+                          int nout, const jfs_compact_seg *d_seg, int32_t max_dst_cap, int32_t *d_ret, void *stream) {
+    if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
+    if (nsrc < 0 || nout < 0 || (nout > 0 && (!d_out || !d_ret))) return JFS_ERR_INVALID;
+    return jfs_launch_gather(d_src, d_src_n, nsrc, d_out, nout, d_seg, max_dst_cap, d_ret, 0, (hipStream_t)stream) == 0
+               ? JFS_OK
+               : JFS_ERR_HIP;
+}
+
+int64_t jfs_lz4_compact_device(const jfs_dev_block *d_src, int nsrc, int32_t *d_src_ret,
+                               const jfs_compact_out *d_gather, const jfs_compact_seg *d_seg,
+                               const jfs_dev_block *d_enc, int nout, int32_t max_dst_cap, int32_t *d_ret,
+                               void *stream) {
+    if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
+    if (nsrc < 0 || nout < 0 || (nsrc > 0 && (!d_src || !d_src_ret)) || (nout > 0 && (!d_gather || !d_enc || !d_ret)))
+        return JFS_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    stat_launch(JFS_ALGO_LZ4, DECOMPRESS, nsrc);
+    stat_launch(JFS_ALGO_LZ4, COMPRESS, nout);
+    if (nsrc > 0 && jfs_launch_lz4_decode(d_src, nsrc, d_src_ret, st) != 0) return JFS_ERR_HIP;
+    if (jfs_launch_gather(d_src, d_src_ret, nsrc, d_gather, nout, d_seg, max_dst_cap, d_ret, 0, st) != 0)
+        return JFS_ERR_HIP;
+    if (nout > 0 && jfs_launch_lz4_encode(d_enc, nout, d_ret, st) != 0) return JFS_ERR_HIP;
+    // the encoder ran on every block: a failed gather's verdict replaces its result
+    return jfs_launch_gather(d_src, d_src_ret, nsrc, d_gather, nout, d_seg, max_dst_cap, d_ret, 1, st) == 0
+               ? JFS_OK
+               : JFS_ERR_HIP;
+}
+
+int64_t jfs_compact_batch(int algo, int nsrc, const jfs_iov *src, int nout, const jfs_iov *out,
+                          const int32_t *seg_first, const jfs_compact_seg *seg, int64_t *src_n, int64_t *out_n,
+                          uint32_t *crc, uint32_t device_mask) {
+    // the whole plan is checked before any device is touched
+    if (algo != JFS_ALGO_NONE && algo != JFS_ALGO_LZ4 && algo != JFS_ALGO_ZSTD) return JFS_ERR_INVALID;
+    if (nsrc < 0 || nout < 0 || (nsrc > 0 && (!src || !src_n)) || (nout > 0 && (!out || !out_n || !seg_first)))
+        return JFS_ERR_INVALID;
+    for (int i = 0; i < nsrc; i++) {
+        const jfs_iov &v = src[i];
+        if (v.src_len < 0 || v.dst_cap < 0 || v.src_len > INT32_MAX || v.dst_cap > INT32_MAX || (v.src_len > 0 && !v.src))
+            return JFS_ERR_INVALID;
+    }
+    std::vector<int64_t> total(nout, 0);
+    for (int j = 0; j < nout; j++) {
+        if (out[j].dst_cap < 0 || (out[j].dst_cap > 0 && !out[j].dst)) return JFS_ERR_INVALID;
+        if (seg_first[j] < 0 || seg_first[j + 1] < seg_first[j] || (seg_first[j + 1] > seg_first[j] && !seg))
+            return JFS_ERR_INVALID;
+        for (int k = seg_first[j]; k < seg_first[j + 1]; k++) {
+            const jfs_compact_seg &s = seg[k];
+            if (s.len <= 0 || (int64_t)s.dst_off != total[j] || s.src < -1 || s.src >= nsrc ||
+                (s.src >= 0 && s.src_off < 0))
+                return JFS_ERR_INVALID;
+            total[j] += s.len;
+            if (total[j] > INT32_MAX) return JFS_ERR_INVALID;
+        }
+    }
+    std::vector<DevCtx *> ds;
+    for (DevCtx *d : devices())
+        if (device_mask == 0 || (d->id < 32 && (device_mask >> d->id) & 1u)) ds.push_back(d);
+    if (ds.empty()) return JFS_ERR_NO_DEVICE;
+    const int64_t t0 = steady_ns();
+    // what the Go adapters answer before the codec runs (pre_answer's rules;
+    // "none" decodes by copying, here without the copy)
+    std::vector<CompactSrc> ss;
+    std::vector<int> src_map(nsrc, -1);
+    for (int i = 0; i < nsrc; i++) {
+        const jfs_iov &v = src[i];
+        if (algo == JFS_ALGO_NONE ? v.dst_cap < v.src_len : v.src_len == 0) {
+            src_n[i] = algo == JFS_ALGO_NONE ? JFS_ERR_SHORT_BUFFER : JFS_ERR_EMPTY_INPUT;
+            continue;
+        }
+        src_map[i] = (int)ss.size();
+        ss.push_back({i, algo == JFS_ALGO_NONE ? v.src_len : staged_cap(algo, DECOMPRESS, v)});
+    }
+    std::vector<CompactOut> oo;
+    for (int j = 0; j < nout; j++) {
+        if (crc) crc[j] = 0;
+        const jfs_iov g{nullptr, total[j], out[j].dst, out[j].dst_cap};  // the gathered block as Compress sees it
+        bool dead = false;  // a source answered on the host feeds it
+        for (int k = seg_first[j]; k < seg_first[j + 1] && !dead; k++) dead = seg[k].src >= 0 && src_map[seg[k].src] < 0;
+        if (dead) out_n[j] = JFS_ERR_CORRUPT;
+        else if (algo == JFS_ALGO_NONE && g.dst_cap < g.src_len) out_n[j] = JFS_ERR_SHORT_BUFFER;
+        else if (algo == JFS_ALGO_LZ4 && g.src_len > LZ4_MAX_INPUT) out_n[j] = JFS_ERR_COMPRESS_FAIL;
+        else if (algo == JFS_ALGO_ZSTD && g.dst_cap < jfs_compress_bound(JFS_ALGO_ZSTD, g.src_len))
+            out_n[j] = JFS_ERR_SHORT_BUFFER;
+        else oo.push_back({j, total[j], algo == JFS_ALGO_NONE ? total[j] : staged_cap(algo, COMPRESS, g)});
+    }
+    int64_t rc = JFS_OK;
+    if (!ss.empty() || !oo.empty()) {
+        DevCtx *dev = ds[g_compact_turn.fetch_add(1) % ds.size()];
+        std::unique_lock<std::mutex> lk;
+        Lane &ln = dev->acquire_lane(lk, algo * 2 + COMPRESS);
+        rc = compact_run(dev, ln, algo, src, ss, src_map, out, oo, seg_first, seg, src_n, out_n, crc);
+        if (rc == JFS_ERR_HIP) (void)lane_healthy(dev, ln);  // leave nothing in flight into the staging
+    }
+    if (rc != JFS_OK) {  // the chain did not run: every block it held reports why
+        for (const CompactSrc &s : ss) src_n[s.idx] = rc;
+        for (const CompactOut &o : oo) out_n[o.idx] = rc;
+    }
+    const uint64_t ns = (uint64_t)(steady_ns() - t0);
+    if (OpStats *st = op_stats(algo, DECOMPRESS)) {
+        st->calls.fetch_add(1, std::memory_order_relaxed);
+        if (!ss.empty()) st->batches.fetch_add(1, std::memory_order_relaxed);
+        for (int i = 0; i < nsrc; i++) stat_block(st, src[i].src_len, src_n[i]);
+    }
+    if (OpStats *st = op_stats(algo, COMPRESS)) {
+        st->calls.fetch_add(1, std::memory_order_relaxed);
+        if (!oo.empty()) st->batches.fetch_add(1, std::memory_order_relaxed);
+        for (int j = 0; j < nout; j++) stat_block(st, total[j], out_n[j]);
+        st->nanos.fetch_add(ns, std::memory_order_relaxed);
+    }
+    return JFS_OK;
 }
 
 int jfs_device_count(void) { return (int)devices().size(); }

@@ -71,6 +71,11 @@ int jfs_launch_lz4_split(const jfs_dev_block *d_desc, int nb, int32_t *d_ret, vo
                          int64_t max_cap, int64_t norg_all, hipStream_t st);
 // ret value of a fused chain's second step when its first step failed
 #define JFS_CHAIN_FAILED (-2147483647 - 1)
+// compaction gather (compact.hip): verdicts into d_ret and the copy; merge != 0:
+// only the verdicts, written over d_ret[j] where negative (after an encoder)
+int jfs_launch_gather(const jfs_dev_block *d_src, const int32_t *d_src_n, int nsrc, const jfs_compact_out *d_out,
+                      int nout, const jfs_compact_seg *d_seg, int32_t max_dst_cap, int32_t *d_ret, int merge,
+                      hipStream_t stream);
 int jfs_launch_gen(uint8_t *d_dst, int nblk, int64_t block_bytes, char cls, uint64_t seed_base,
                    const uint8_t *d_vocab, hipStream_t stream);
 }

@@ -182,6 +182,53 @@ def open_lz4_decompress(aead_desc: torch.Tensor, dec_desc: torch.Tensor, ret_ope
                                                    ret.data_ptr(), _stream_ptr(stream)), "jfs_open_lz4_decompress_device")
 
 
+SEG_DTYPE = np.dtype([("src", "<i4"), ("src_off", "<i4"), ("dst_off", "<i4"), ("len", "<i4")])
+COMPACT_OUT_DTYPE = np.dtype([("dst", "<u8"), ("dst_cap", "<i4"), ("seg_first", "<i4"), ("seg_count", "<i4"),
+                              ("reserved", "<i4")])
+assert SEG_DTYPE.itemsize == ctypes.sizeof(L.JfsCompactSeg)
+assert COMPACT_OUT_DTYPE.itemsize == ctypes.sizeof(L.JfsCompactOut)
+
+
+def make_compact_desc(dst: torch.Tensor, dst_offs, dst_caps, seg_first, seg):
+    """Device tensors for a gather plan: (jfs_compact_out descriptors, one per
+    output block at dst[dst_offs[j] : +dst_caps[j]]; jfs_compact_seg records).
+    seg_first has one entry per block plus one; seg = [(src, src_off, dst_off, len)]."""
+    n = len(dst_offs)
+    o = np.zeros(n, dtype=COMPACT_OUT_DTYPE)
+    o["dst"] = dst.data_ptr() + np.asarray(dst_offs, dtype=np.uint64)
+    o["dst_cap"] = np.asarray(dst_caps, dtype=np.int32)
+    first = np.asarray(seg_first, dtype=np.int32)
+    o["seg_first"] = first[:n]
+    o["seg_count"] = first[1:n + 1] - first[:n]
+    s = np.zeros(max(len(seg), 1), dtype=SEG_DTYPE)
+    if len(seg):
+        a = np.asarray(seg, dtype=np.int32).reshape(-1, 4)
+        s["src"], s["src_off"], s["dst_off"], s["len"] = a[:, 0], a[:, 1], a[:, 2], a[:, 3]
+    return (torch.from_numpy(o.view(np.uint8).copy()).to(dst.device),
+            torch.from_numpy(s.view(np.uint8).copy()).to(dst.device))
+
+
+def gather(src_desc: torch.Tensor, src_n: torch.Tensor, out_desc: torch.Tensor, seg: torch.Tensor, max_dst_cap: int,
+           ret: torch.Tensor, stream=None):
+    """jfs_gather_device: src_desc = jfs_dev_block per decoded source (its dst /
+    dst_cap), src_n = their decoded lengths (int32, negative = failed)."""
+    ns = src_desc.numel() // DESC_DTYPE.itemsize
+    no = out_desc.numel() // COMPACT_OUT_DTYPE.itemsize
+    _check(L.load().jfs_gather_device(src_desc.data_ptr(), src_n.data_ptr(), ns, out_desc.data_ptr(), no,
+                                      seg.data_ptr(), int(max_dst_cap), ret.data_ptr(), _stream_ptr(stream)),
+           "jfs_gather_device")
+
+
+def lz4_compact(src_desc: torch.Tensor, src_ret: torch.Tensor, gather_desc: torch.Tensor, seg: torch.Tensor,
+                enc_desc: torch.Tensor, max_dst_cap: int, ret: torch.Tensor, stream=None):
+    """Fused LZ4 decode -> gather -> LZ4 encode (jfs_lz4_compact_device)."""
+    ns = src_desc.numel() // DESC_DTYPE.itemsize
+    no = gather_desc.numel() // COMPACT_OUT_DTYPE.itemsize
+    _check(L.load().jfs_lz4_compact_device(src_desc.data_ptr(), ns, src_ret.data_ptr(), gather_desc.data_ptr(),
+                                           seg.data_ptr(), enc_desc.data_ptr(), no, int(max_dst_cap), ret.data_ptr(),
+                                           _stream_ptr(stream)), "jfs_lz4_compact_device")
+
+
 def gen_blocks(out: torch.Tensor, nblk: int, block_bytes: int, cls: str, seed_base: int, stream=None):
     """Fill out[0 : nblk*block_bytes] with synthetic blocks."""
     assert out.numel() >= nblk * block_bytes
