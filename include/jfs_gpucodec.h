@@ -224,6 +224,19 @@ int64_t jfs_lz4_compress_device(const jfs_dev_block *d_blocks, int nblk, int32_t
  * it below JFS_LZ4E_SEG_MAX blocks (default 256). */
 int64_t jfs_lz4_compress_device_small(const jfs_dev_block *d_blocks, const int32_t *src_len, int nblk, int32_t *d_ret,
                                       void *stream);
+/* Fast LZ4 encode (throughput mode): ret[i] = size of a valid LZ4 block that
+ * LZ4_decompress_safe decodes back to src, or 0 when it does not fit dst_cap
+ * or src_len > 0x7E000000 (no byte of that dst is written).  NOT liblz4's
+ * bytes: every block is cut into independent 64 KiB chunks that are parsed
+ * 64 positions at a time, so no parse chain is longer than a chunk.  The bytes
+ * depend on the input bytes alone (not on the batch, the block's index, the
+ * device or alignment); the size never exceeds jfs_compress_bound(LZ4, n);
+ * src_len == 0 gives the single byte 0x00.  src_len = HOST copies of the
+ * descriptors' src_len.  Asynchronous on `stream`; per-device scratch of at
+ * most 1 GiB (2 bytes per input byte below that), reused across calls.  Does
+ * not consult jfs_lz4_parse_mode. */
+int64_t jfs_lz4_compress_fast_device(const jfs_dev_block *d_blocks, const int32_t *src_len, int nblk, int32_t *d_ret,
+                                     void *stream);
 /* Diagnostics of the segment encoder: out[r] (r = 1..16) = blocks whose
  * segments settled after r rounds, out[0] = blocks handed to the serial kernel
  * (not settled within JFS_LZ4E_SEG_ROUNDS, default 8, or a segment with too
@@ -411,6 +424,23 @@ int jfs_device_count(void);
 #define JFS_MODE_AUTO 1
 #define JFS_MODE_FORCE 2
 int jfs_gpu_mode(void);
+
+/* LZ4 parse of the HOST-buffer compress calls (jfs_compress and its
+ * coalescer, jfs_compress_batch / _crc / _mixed, jfs_compress_seal_batch, the
+ * encode step of jfs_compact_batch): JFS_LZ4_PARSE_EXACT (default) writes
+ * LZ4_compress_default's bytes, JFS_LZ4_PARSE_FAST the blocks of
+ * jfs_lz4_compress_fast_device -- ordinary LZ4 blocks to every reader, and
+ * per-block results keep their meaning (JFS_ERR_COMPRESS_FAIL when a block
+ * does not fit).  The device-resident entry points above do what their
+ * comments say in either mode.  The initial value is read once from
+ * JFS_LZ4_PARSE = "exact" | "fast" (case-insensitive, like JFS_GPU_CODEC;
+ * anything else, or unset: exact).  jfs_set_lz4_parse_mode returns the
+ * previous mode, or -1 for an unknown value (which changes nothing); it is
+ * atomic and applies to calls that start afterwards. */
+#define JFS_LZ4_PARSE_EXACT 0
+#define JFS_LZ4_PARSE_FAST 1
+int jfs_lz4_parse_mode(void);
+int jfs_set_lz4_parse_mode(int mode);
 
 /* Per-codec counters (the data behind cachedStore's object_request_data_bytes
  * and block-size metrics, cached_store.go:931-974).  Index algo * 2 + dir,

@@ -39,9 +39,13 @@ EXPORTS = [
     "jfs_open_decompress_batch", "jfs_compress_batch_crc", "jfs_decompress_batch_csum", "jfs_deal_plan",
     "jfs_test_spread_locking", "jfs_compress_batch_mixed", "jfs_decompress_batch_mixed",
     "jfs_gather_device", "jfs_lz4_compact_device", "jfs_compact_batch",
+    "jfs_lz4_compress_fast_device", "jfs_lz4_parse_mode", "jfs_set_lz4_parse_mode",
 ]
+# the hook include/jfs_gpucodec_lz4_fast_test.h declares (the fast LZ4 encoder's host twin)
+LZ4_FAST_TEST_EXPORTS = ["jfs_test_lz4_fast_host"]
 
 MODE_OFF, MODE_AUTO, MODE_FORCE = 0, 1, 2
+LZ4_PARSE_EXACT, LZ4_PARSE_FAST = 0, 1
 CIPHER_AES256GCM, CIPHER_CHACHA20POLY1305, CIPHER_SM4GCM = 0, 1, 2
 STATS_N = 6  # index algo * 2 + dir (0 compress, 1 decompress)
 
@@ -118,6 +122,14 @@ def load() -> ctypes.CDLL:
     lib.jfs_zstd_split_counts.restype = ctypes.c_int
     lib.jfs_lz4_compress_device_small.argtypes = [vp, vp, ctypes.c_int, vp, vp]
     lib.jfs_lz4_compress_device_small.restype = ctypes.c_int64
+    lib.jfs_lz4_compress_fast_device.argtypes = [vp, vp, ctypes.c_int, vp, vp]
+    lib.jfs_lz4_compress_fast_device.restype = i64
+    lib.jfs_lz4_parse_mode.argtypes = []
+    lib.jfs_lz4_parse_mode.restype = ctypes.c_int
+    lib.jfs_set_lz4_parse_mode.argtypes = [ctypes.c_int]
+    lib.jfs_set_lz4_parse_mode.restype = ctypes.c_int
+    lib.jfs_test_lz4_fast_host.argtypes = [vp, i64, vp, i64]
+    lib.jfs_test_lz4_fast_host.restype = i64
     lib.jfs_lz4_eseg_counts.argtypes = [vp, ctypes.c_int]
     lib.jfs_lz4_eseg_counts.restype = ctypes.c_int
     lib.jfs_cipher_from_name.argtypes = [ctypes.c_char_p]

@@ -19,6 +19,7 @@ fallback (the library returns ``JFS_ERR_NO_DEVICE`` without a gfx950 GPU).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 
 import numpy as np
@@ -211,6 +212,36 @@ def NewCompressor(algr: str):
     if a == L.ALGO_NONE:
         return noOp()
     return None
+
+
+_LZ4_PARSE = {"exact": L.LZ4_PARSE_EXACT, "fast": L.LZ4_PARSE_FAST}
+
+
+@contextlib.contextmanager
+def lz4_parse_mode(mode: str):
+    """Hold the LZ4 parse of the host-buffer compress calls at "exact"
+    (LZ4_compress_default's bytes) or "fast" (jfs_lz4_compress_fast_device's
+    blocks) and put the previous mode back on exit.  The mode is process-wide
+    (jfs_set_lz4_parse_mode)."""
+    if mode not in _LZ4_PARSE:
+        raise ValueError(f"lz4 parse mode {mode!r}: expected 'exact' or 'fast'")
+    lib = L.load()
+    prev = lib.jfs_set_lz4_parse_mode(_LZ4_PARSE[mode])
+    try:
+        yield
+    finally:
+        lib.jfs_set_lz4_parse_mode(prev)
+
+
+def lz4_fast_host(src) -> bytes:
+    """The fast encoder's host twin (jfs_test_lz4_fast_host, test
+    infrastructure): the bytes jfs_lz4_compress_fast_device writes for src."""
+    lib = L.load()
+    src = bytes(src)
+    cap = int(lib.jfs_compress_bound(L.ALGO_LZ4, len(src)))
+    dst = ctypes.create_string_buffer(max(cap, 1))
+    n = int(lib.jfs_test_lz4_fast_host(ctypes.addressof(dst), cap, src, len(src)))
+    return dst.raw[:n]
 
 
 def compact_plan(slices, block_size: int, src_block_size: int | None = None):

@@ -286,6 +286,19 @@ int gpu_mode() {
     return m;
 }
 
+// JFS_LZ4_PARSE (include/jfs_gpucodec.h): exact (default) | fast
+std::atomic<int> &lz4_parse() {
+    static std::atomic<int> m{[] {
+        const char *e = getenv("JFS_LZ4_PARSE");
+        if (!e) return JFS_LZ4_PARSE_EXACT;
+        std::string v(e);
+        for (auto &ch : v) ch = (char)tolower((unsigned char)ch);
+        return v == "fast" ? JFS_LZ4_PARSE_FAST : JFS_LZ4_PARSE_EXACT;
+    }()};
+    return m;
+}
+inline bool lz4_fast_mode() { return lz4_parse().load(std::memory_order_relaxed) == JFS_LZ4_PARSE_FAST; }
+
 // JFS_GPU_DEVICES: "all" (default), a comma list of ordinals, or a 0x mask
 uint64_t device_select_mask() {
     const char *e = getenv("JFS_GPU_DEVICES");
@@ -983,11 +996,16 @@ int64_t run_batch(DevCtx *dev, Lane &ln, int algo, int dir, int nblk, const jfs_
     (void)aeb;
     // compress -> seal, or open -> decompress (the staged inputs and the
     // LZ4 encode of a staged chunk: segment-parallel for small batches
+    const bool lz4_fast = lz4_fast_mode();  // the mode when this batch started
     auto lz4_encode = [&](Slot &sl, const jfs_dev_block *h_desc, const jfs_dev_block *d_desc, int n, int32_t *d_ret,
                           hipStream_t ks) -> int64_t {
-        if (n > eseg_max()) return jfs_launch_lz4_encode(d_desc, n, d_ret, ks) == 0 ? JFS_OK : JFS_ERR_HIP;
+        if (!lz4_fast && n > eseg_max()) return jfs_launch_lz4_encode(d_desc, n, d_ret, ks) == 0 ? JFS_OK : JFS_ERR_HIP;
         std::vector<int32_t> lens(n);
         for (int k = 0; k < n; k++) lens[k] = h_desc[k].src_len;
+        if (lz4_fast) {
+            if (!sl.ensure_split(jfs_lz4_fast_scratch_bytes(n, lens.data()))) return JFS_ERR_NO_MEMORY;
+            return jfs_launch_lz4_fast(d_desc, n, lens.data(), d_ret, sl.sp, sl.sp_cap, ks) == 0 ? JFS_OK : JFS_ERR_HIP;
+        }
         if (!sl.ensure_split(jfs_lz4_eseg_scratch_bytes(n, lens.data()))) return JFS_ERR_NO_MEMORY;
         return jfs_launch_lz4_encode_seg(d_desc, n, lens.data(), d_ret, sl.sp, sl.sp_cap, ks) == 0 ? JFS_OK
                                                                                                    : JFS_ERR_HIP;
@@ -1998,7 +2016,8 @@ int64_t compact_run(DevCtx *dev, Lane &ln, int algo, const jfs_iov *src, const s
     // stream: they share slot 1's scratch, sized for both before anything is queued
     Slot &s1 = ln.slot[1];
     const bool split_dec = algo == JFS_ALGO_LZ4 && ns > 0 && ns <= split_max();
-    const bool seg_enc = algo == JFS_ALGO_LZ4 && no > 0 && no <= eseg_max();
+    const bool fast_enc = algo == JFS_ALGO_LZ4 && no > 0 && lz4_fast_mode();
+    const bool seg_enc = algo == JFS_ALGO_LZ4 && no > 0 && !fast_enc && no <= eseg_max();
     {
         int64_t need = 0;
         if (split_dec) {
@@ -2013,6 +2032,11 @@ int64_t compact_run(DevCtx *dev, Lane &ln, int algo, const jfs_iov *src, const s
             std::vector<int32_t> lens(no);
             for (int k = 0; k < no; k++) lens[k] = h_enc[k].src_len;
             need = std::max(need, jfs_lz4_eseg_scratch_bytes(no, lens.data()));
+        }
+        if (fast_enc) {
+            std::vector<int32_t> lens(no);
+            for (int k = 0; k < no; k++) lens[k] = h_enc[k].src_len;
+            need = std::max(need, jfs_lz4_fast_scratch_bytes(no, lens.data()));
         }
         if (need > 0 && !s1.ensure_split(need)) return JFS_ERR_NO_MEMORY;
     }
@@ -2042,7 +2066,11 @@ int64_t compact_run(DevCtx *dev, Lane &ln, int algo, const jfs_iov *src, const s
     const jfs_compact_seg *d_seg = (const jfs_compact_seg *)(d + o_seg);
     if (lk == 0) lk = jfs_launch_gather(d_sdesc, d_srcn, ns + 1, d_plan, no, d_seg, max_total, d_ret, 0, ks);
     if (lk == 0 && codec && no > 0) {
-        if (seg_enc) {
+        if (fast_enc) {
+            std::vector<int32_t> lens(no);
+            for (int k = 0; k < no; k++) lens[k] = h_enc[k].src_len;
+            lk = jfs_launch_lz4_fast(d_enc, no, lens.data(), d_ret, s1.sp, s1.sp_cap, ks);
+        } else if (seg_enc) {
             std::vector<int32_t> lens(no);
             for (int k = 0; k < no; k++) lens[k] = h_enc[k].src_len;
             lk = jfs_launch_lz4_encode_seg(d_enc, no, lens.data(), d_ret, s1.sp, s1.sp_cap, ks);
@@ -2521,6 +2549,43 @@ int64_t jfs_lz4_compress_device_small(const jfs_dev_block *d_blocks, const int32
     if (hipStreamWaitEvent(st, z.ev_done, 0) != hipSuccess) return JFS_ERR_HIP;
     if (jfs_launch_lz4_encode_seg(d_blocks, nblk, src_len, d_ret, z.p, z.cap, st) != 0) return JFS_ERR_HIP;
     return hipEventRecord(z.ev_done, st) == hipSuccess ? JFS_OK : JFS_ERR_HIP;
+}
+
+SplitScratch g_fast_scr[64];
+
+int64_t jfs_lz4_compress_fast_device(const jfs_dev_block *d_blocks, const int32_t *src_len, int nblk, int32_t *d_ret,
+                                     void *stream) {
+    if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
+    if (nblk < 0 || (nblk > 0 && !src_len)) return JFS_ERR_INVALID;
+    if (nblk == 0) return JFS_OK;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return JFS_ERR_HIP;
+    stat_launch(JFS_ALGO_LZ4, COMPRESS, nblk);
+    const int64_t need = jfs_lz4_fast_scratch_bytes(nblk, src_len);
+    SplitScratch &z = g_fast_scr[dev];
+    std::lock_guard<std::mutex> lk(z.mu);
+    if (!z.ev_done && hipEventCreateWithFlags(&z.ev_done, hipEventDisableTiming) != hipSuccess) return JFS_ERR_HIP;
+    if (need > z.cap) {
+        if (hipEventSynchronize(z.ev_done) != hipSuccess) return JFS_ERR_HIP;
+        if (z.p) (void)hipFree(z.p);
+        z.p = nullptr;
+        z.cap = 0;
+        int64_t want = 64ll << 20;
+        while (want < need) want <<= 1;
+        if (hipMalloc((void **)&z.p, (size_t)want) != hipSuccess) return JFS_ERR_NO_MEMORY;
+        z.cap = want;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (hipStreamWaitEvent(st, z.ev_done, 0) != hipSuccess) return JFS_ERR_HIP;
+    if (jfs_launch_lz4_fast(d_blocks, nblk, src_len, d_ret, z.p, z.cap, st) != 0) return JFS_ERR_HIP;
+    return hipEventRecord(z.ev_done, st) == hipSuccess ? JFS_OK : JFS_ERR_HIP;
+}
+
+int jfs_lz4_parse_mode(void) { return lz4_parse().load(std::memory_order_relaxed); }
+
+int jfs_set_lz4_parse_mode(int mode) {
+    if (mode != JFS_LZ4_PARSE_EXACT && mode != JFS_LZ4_PARSE_FAST) return -1;
+    return lz4_parse().exchange(mode);
 }
 
 int64_t jfs_lz4_compress_device(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, void *stream) {

@@ -89,6 +89,16 @@ def lz4_compress_small(desc: torch.Tensor, ret: torch.Tensor, src_lens, stream=N
            "jfs_lz4_compress_device_small")
 
 
+def lz4_compress_fast(desc: torch.Tensor, ret: torch.Tensor, src_lens, stream=None):
+    """jfs_lz4_compress_fast_device: the throughput encoder (independent 64 KiB
+    chunks, 64 positions searched at once).  Valid LZ4 blocks, not liblz4's
+    bytes; src_lens = host copies."""
+    n = desc.numel() // DESC_DTYPE.itemsize
+    sl = (ctypes.c_int32 * max(n, 1))(*[int(x) for x in src_lens])
+    _check(L.load().jfs_lz4_compress_fast_device(desc.data_ptr(), sl, n, ret.data_ptr(), _stream_ptr(stream)),
+           "jfs_lz4_compress_fast_device")
+
+
 def lz4_eseg_counts(reset: bool = False):
     """Segment encoder: {rounds: blocks settled after that many rounds}, with
     0 = blocks handed to the serial kernel."""
