@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/jfs_gpucodec_test.h"
+#include "batch_plan.h"
 #include "blockgen.h"
 #include "jfs_internal.h"
 
@@ -41,7 +42,7 @@ namespace {
 
 constexpr int64_t LZ4_MAX_INPUT = 0x7E000000;
 
-inline int64_t align16(int64_t x) { return (x + 15) & ~(int64_t)15; }
+using jfs_plan::align16;
 
 // JFS_HOST_TRACE=1: per-chunk host timings on stderr (diagnostics)
 bool host_trace() {
@@ -342,6 +343,17 @@ inline void stat_block(OpStats *st, int64_t in, int64_t out) {
     }
 }
 
+// a host batch call that began at t0: the call, its time and, when it ran
+// (rc), every block's outcome
+inline void stat_call(int algo, int dir, int64_t rc, int nblk, const jfs_iov *iov, const int64_t *out_n, int64_t t0) {
+    OpStats *st = op_stats(algo, dir);
+    if (!st) return;
+    st->calls.fetch_add(1, std::memory_order_relaxed);
+    if (rc == JFS_OK)
+        for (int i = 0; i < nblk; i++) stat_block(st, iov[i].src_len, out_n[i]);
+    st->nanos.fetch_add((uint64_t)(steady_ns() - t0), std::memory_order_relaxed);
+}
+
 inline void stat_launch(int algo, int dir, int nblk) {
     if (OpStats *st = op_stats(algo, dir)) {
         st->calls.fetch_add(1, std::memory_order_relaxed);
@@ -544,7 +556,10 @@ int host_ramp_len() {
     }();
     return v;
 }
-bool host_ramp() { return host_ramp_len() > 0; }
+// blocks in the first full chunk after the ramp (0: no cap)
+#ifndef JFS_HOST_FIRST_BIG
+#define JFS_HOST_FIRST_BIG 192
+#endif
 
 // LZ4 compress chunks: the serial-parse encoder holds 8 blocks per CU and a
 // launch lasts one block's parse (~0.5 s) whatever its size, so a 2 GiB chunk
@@ -719,249 +734,169 @@ struct Aead {
     }
 };
 
-// Run blocks [0,nblk) of iov on one device through one lane (the caller holds
-// ln.mu); returns when every result is in out[].  Blocks that the C-ABI
-// answers without a kernel (empty input, noOp) are handled by the caller.  The
-// batch is cut into chunks pipelined over the lane's NSLOT (stream, pinned,
-// HBM) slots: host copy-in of chunk k (threads) | H2D k+1, kernel k, D2H k-1
-// (streams) | host copy-out of chunk k-NSLOT.  A chunk holds at most
-// chunk_limit() staging bytes; the lane's kernels run in chunk order, so a
-// batch is not cut finer than that (a decode kernel over fewer blocks than
-// CUs lasts about one block's latency whatever its size).
-// max_chunk_blocks (> 0) also caps a chunk's block count; on_chunk (optional)
-// is called with [s, e) as soon as those blocks' results and outputs are final
-// (the coalescer releases their callers there, before later chunks finish).
-int64_t run_batch(DevCtx *dev, Lane &ln, int algo, int dir, int nblk, const jfs_iov *iov, int64_t *out,
-                  const Aead *ae = nullptr, uint32_t *crc_out = nullptr, int max_chunk_blocks = 0,
-                  const std::function<void(int, int)> *on_chunk = nullptr, uint8_t *const *csum_out = nullptr) {
-    if (nblk <= 0) return JFS_OK;
+// What every run on a lane begins and ends with: the caller's device is kept
+// and the lane's selected, the device's counters and idle clock move on, the
+// staging janitor runs; the idle clock starts anew when the run ends.
+struct LaneRun {
     DevGuard guard;
-    (void)hipSetDevice(dev->id);
-    dev->last_use_ms = steady_ms();
-    ln.kind.store(algo * 2 + dir, std::memory_order_relaxed);
-    dev->batches.fetch_add(1, std::memory_order_relaxed);
-    dev->blocks.fetch_add((uint64_t)nblk, std::memory_order_relaxed);
-    if (OpStats *st = op_stats(algo, dir)) st->batches.fetch_add(1, std::memory_order_relaxed);
-    start_janitor();
-    struct Touch {  // the idle clock starts when the batch ends
-        DevCtx *d;
-        ~Touch() { d->last_use_ms = steady_ms(); }
-    } touch{dev};
+    DevCtx *dev;
+    LaneRun(DevCtx *d, Lane &ln, int kind, uint64_t nblk) : dev(d) {
+        (void)hipSetDevice(d->id);
+        d->last_use_ms = steady_ms();
+        ln.kind.store(kind, std::memory_order_relaxed);
+        d->batches.fetch_add(1, std::memory_order_relaxed);
+        d->blocks.fetch_add(nblk, std::memory_order_relaxed);
+        start_janitor();
+    }
+    ~LaneRun() { dev->last_use_ms = steady_ms(); }
+};
+
+inline int64_t launch_rc(int lk) { return lk == 0 ? JFS_OK : JFS_ERR_HIP; }
+
+// src_len / dst_cap of staged descriptors, as the small-batch launchers take them
+std::vector<int32_t> desc_lens(const jfs_dev_block *h_desc, int n) {
+    std::vector<int32_t> v(n);
+    for (int k = 0; k < n; k++) v[k] = h_desc[k].src_len;
+    return v;
+}
+std::vector<int32_t> desc_caps(const jfs_dev_block *h_desc, int n) {
+    std::vector<int32_t> v(n);
+    for (int k = 0; k < n; k++) v[k] = h_desc[k].dst_cap;
+    return v;
+}
+
+// LZ4 encode of n staged blocks (h_desc = d_desc's host copy): the fast parse
+// when `fast`, else the segment-parallel parse for small batches (eseg_max)
+// and one whole-block parse per wave for large ones.  lz4_encode_scratch: the
+// slot scratch that launch will ask for (a caller that shares a slot's scratch
+// between launches sizes it first: growing it waits for the whole device).
+int64_t lz4_encode_scratch(int n, const int32_t *lens, bool fast) {
+    if (fast) return jfs_lz4_fast_scratch_bytes(n, lens);
+    return n <= eseg_max() ? jfs_lz4_eseg_scratch_bytes(n, lens) : 0;
+}
+int64_t launch_lz4_encode(Slot &sl, const jfs_dev_block *h_desc, const jfs_dev_block *d_desc, int n, int32_t *d_ret,
+                          hipStream_t st, bool fast) {
+    if (!fast && n > eseg_max()) return launch_rc(jfs_launch_lz4_encode(d_desc, n, d_ret, st));
+    const std::vector<int32_t> lens = desc_lens(h_desc, n);
+    if (!sl.ensure_split(lz4_encode_scratch(n, lens.data(), fast))) return JFS_ERR_NO_MEMORY;
+    return launch_rc(fast ? jfs_launch_lz4_fast(d_desc, n, lens.data(), d_ret, sl.sp, sl.sp_cap, st)
+                          : jfs_launch_lz4_encode_seg(d_desc, n, lens.data(), d_ret, sl.sp, sl.sp_cap, st));
+}
+
+static_assert(jfs_plan::LZ4_SPLIT_SEG == JFS_LZ4_SPLIT_SEG, "batch_plan.h restates the small-batch segment size");
+
+// LZ4 decode of n staged blocks: the small-batch path up to split_max()
+// blocks, else one workgroup per block.  lz4_decode_scratch: the slot scratch
+// that launch will ask for (lens / caps: the descriptors' src_len / dst_cap).
+int64_t lz4_decode_scratch(int n, const int32_t *lens, const int32_t *caps) {
+    return n <= split_max() ? jfs_lz4_split_scratch_bytes(n, lens, caps) : 0;
+}
+int64_t launch_lz4_decode(Slot &sl, const jfs_dev_block *h_desc, const jfs_dev_block *d_desc, int n, int32_t *d_ret,
+                          hipStream_t st) {
+    if (n > split_max()) return launch_rc(jfs_launch_lz4_decode(d_desc, n, d_ret, st));
+    const std::vector<int32_t> lens = desc_lens(h_desc, n), caps = desc_caps(h_desc, n);
+    if (!sl.ensure_split(lz4_decode_scratch(n, lens.data(), caps.data()))) return JFS_ERR_NO_MEMORY;
+    const jfs_plan::Lz4SplitGeom g = jfs_plan::lz4_split_geom(n, lens.data(), caps.data());
+    return launch_rc(jfs_launch_lz4_split(d_desc, n, d_ret, sl.sp, g.nseg, g.max_cap, g.norg, st));
+}
+
+// One run_batch call: the chunk plan (batch_plan.h), every chunk's staging
+// layout and the call's options; launch(k) queues chunk k, finish(k) waits for
+// it and hands its results and outputs to the caller.  Every pointer into a
+// slot's staging comes from the chunk's ChunkLayout, applied to the pinned
+// (sl.h) and the HBM (sl.d) copy alike.
+struct BatchRun {
+    using Chunk = jfs_plan::Chunk;
+    using Layout = jfs_plan::ChunkLayout;
+
+    DevCtx *const dev;
+    Lane &ln, &other;  // chunk kernels alternate between the two lanes' kernel streams
+    const int algo, dir;
+    const jfs_iov *const iov;
+    int64_t *const out;
+    const Aead *const ae;
+    uint32_t *const crc_out;
+    uint8_t *const *const csum_out;  // decode-side disk-cache checksums, or null
+    const bool zplan;                // Zstd decode: the per-input scratch plan (ZInfo) rides in the chunk
+    const int64_t zib;
+    const bool lz4_fast;  // the parse mode when this batch started
+    const jfs_plan::Pieces pieces{NPIECE, byte_npiece()};
+    std::vector<jfs_plan::Block> blk;  // staged input bytes and capacity per block
+    jfs_plan::Plan plan;
+    std::vector<Layout> lay;  // per chunk
+
+    BatchRun(DevCtx *dev, Lane &ln, int algo, int dir, int nblk, const jfs_iov *iov, int64_t *out, const Aead *ae,
+             uint32_t *crc_out, int max_chunk_blocks, uint8_t *const *csum)
+        : dev(dev), ln(ln), other(dev->lane[(&ln - dev->lane + 1) % NLANE]), algo(algo), dir(dir), iov(iov), out(out),
+          ae(ae), crc_out(crc_out), csum_out(dir == DECOMPRESS && !ae ? csum : nullptr),
+          zplan(algo == JFS_ALGO_ZSTD && dir == DECOMPRESS && !ae), zib(zplan ? (int64_t)jfs_zstd_info_bytes() : 0),
+          lz4_fast(lz4_fast_mode()), blk(nblk) {
+        for (int i = 0; i < nblk; i++) blk[i] = {iov[i].src_len, ae ? iov[i].dst_cap : staged_cap(algo, dir, iov[i])};
+        const int64_t limit =
+            (algo == JFS_ALGO_LZ4 || algo == JFS_ALGO_ZSTD) && dir == COMPRESS && !ae ? chunk_limit_lz4c()
+                                                                                      : chunk_limit();
+        const bool ramp_ok = dir == DECOMPRESS && !ae && max_chunk_blocks <= 0;
+        plan = jfs_plan::plan_chunks(blk.data(), nblk,
+                                     {limit, max_chunk_blocks, ramp_ok, host_ramp_len(), JFS_HOST_FIRST_BIG, NSLOT});
+        lay.reserve(plan.ch.size());
+        for (const Chunk &c : plan.ch)
+            lay.emplace_back(c.e - c.s, c.tin, c.tout, zib, ae != nullptr, crc_out != nullptr, csum_out != nullptr,
+                             csum_out ? csum_bytes(c) : 0);
+    }
+
     // Chunk kernels alternate between this lane's kernel stream and the other
     // lane's: an encode launch lasts one block's latency (~0.5 s) whatever its
     // size, so two chunks' kernels must run side by side (a device has only
     // two kernel streams: see Lane).
-    Lane &other = dev->lane[(&ln - dev->lane + 1) % NLANE];
-    auto kstream = [&](int chunk) { return (chunk & 1) ? other.s_k : ln.s_k; };
-    std::vector<int64_t> cap(nblk), in_off(nblk), out_off(nblk);
-    struct Chunk {
-        int s, e, slot;
-        int64_t tin, tout;
-        hipStream_t ks;  // its kernel stream
-    };
-    std::vector<Chunk> ch;
-    {
-        const int64_t limit =
-            (algo == JFS_ALGO_LZ4 || algo == JFS_ALGO_ZSTD) && dir == COMPRESS && !ae ? chunk_limit_lz4c() : chunk_limit();
-        // Decode ramp: the first output cannot leave before chunk 0's H2D and
-        // kernel are done, and the one-workgroup-per-block kernels take a
-        // block's whole latency (~20 ms) whatever the chunk size; so a long
-        // decode starts with chunks of 32, 64 and 128 blocks (the small-batch
-        // kernels) that put the D2H stream to work while the first full chunk
-        // is staged and decoded, and ends with a chunk of at most 128 blocks
-        // so that little copy-out is left after the last D2H.  Measured on
-        // 2,048 x 4 MiB LZ4 (scripts/hostpath.py): no ramp 34.9-36.5 GiB/s,
-        // 3 ramp chunks 39.7-40.0, 5: 37.5, 7: 36.5.
-        int64_t total = 0;
-        for (int i = 0; i < nblk; i++) total += staged_bytes(algo, dir, iov[i]);
-        const bool ramp = dir == DECOMPRESS && !ae && max_chunk_blocks <= 0 && total > 2 * limit && host_ramp();
-        int s = 0;
-        while (s < nblk) {
-            Chunk c{s, s, (int)(ch.size() % NSLOT), 0, 0, kstream((int)ch.size())};
-            const int k = (int)ch.size();
-#ifndef JFS_HOST_FIRST_BIG
-#define JFS_HOST_FIRST_BIG 192  // blocks in the first full chunk after the ramp (0: no cap)
-#endif
-            // (the first full chunk's H2D and one-block kernel latency are on
-            // the critical path: a smaller one reaches the D2H stream sooner)
-            int cap_blocks = ramp && k < host_ramp_len() ? std::min(32 << k, 128) : max_chunk_blocks;
-            if (JFS_HOST_FIRST_BIG > 0 && ramp && k == host_ramp_len()) cap_blocks = JFS_HOST_FIRST_BIG;
-            while (c.e < nblk) {
-                const int64_t ci = ae ? iov[c.e].dst_cap : staged_cap(algo, dir, iov[c.e]);
-                const int64_t ib = align16(iov[c.e].src_len), ob = align16(ci);  // = staged_bytes()
-                if (c.e > s && (c.tin + c.tout + ib + ob > limit || (cap_blocks > 0 && c.e - s >= cap_blocks)))
-                    break;
-                cap[c.e] = ci;
-                in_off[c.e] = c.tin;
-                out_off[c.e] = c.tout;
-                c.tin += ib;
-                c.tout += ob;
-                c.e++;
-            }
-            ch.push_back(c);
-            s = c.e;
-        }
-        if (ramp && ch.size() > 4 && ch.back().e - ch.back().s > 128) {  // ramp down: split the last chunk
-            Chunk &l = ch.back();
-            const int mid = l.e - 128;
-            Chunk t{mid, l.e, (int)(ch.size() % NSLOT), 0, 0, kstream((int)ch.size())};
-            l.e = mid;
-            l.tin = l.tout = 0;
-            for (int i = l.s; i < l.e; i++) {
-                in_off[i] = l.tin;
-                out_off[i] = l.tout;
-                l.tin += align16(iov[i].src_len);
-                l.tout += align16(cap[i]);
-            }
-            for (int i = t.s; i < t.e; i++) {
-                in_off[i] = t.tin;
-                out_off[i] = t.tout;
-                t.tin += align16(iov[i].src_len);
-                t.tout += align16(cap[i]);
-            }
-            ch.push_back(t);
-        }
+    hipStream_t kstream(int k) const { return (k & 1) ? other.s_k : ln.s_k; }
+    bool h2d(void *d, const void *h, int64_t n) const {
+        return hipMemcpyAsync(d, h, (size_t)n, hipMemcpyHostToDevice, dev->s_in) == hipSuccess;
     }
-    // Zstd decode: the per-input scratch plan (ZInfo) rides in the chunk
-    const bool zplan = algo == JFS_ALGO_ZSTD && dir == DECOMPRESS && !ae;
-    const int64_t zib = zplan ? (int64_t)jfs_zstd_info_bytes() : 0;
-    // aead extras per block: descriptor, second result, 64 bytes of key (32) + nonce (12)
-    const int64_t aeb = ae ? (int64_t)sizeof(jfs_aead_block) + 4 + 64 : 0;
-    // output pieces of a chunk (see NPIECE): large chunks in block ranges
-    // [piece_b(c, p), piece_b(c, p + 1)); a one-block chunk (a lone cache
-    // miss) in byte ranges of the output area (byte_npiece), so that the
-    // copy-out of one piece overlaps the D2H of the next; other small chunks
-    // (the coalescer's 16-block ones) stay whole: a piece's host copy is a
-    // thread-pool round of its own.  piece_o(c, p) = the piece's first byte.
-    auto byte_pieces = [&](const Chunk &c) { return byte_npiece() > 1 && c.e - c.s == 1; };
-    // input staging pieces: block ranges of large chunks only
-    auto in_npiece = [&](const Chunk &c) { return c.e - c.s >= 64 ? std::min(NPIECE, c.e - c.s) : 1; };
-    auto in_piece_b = [&](const Chunk &c, int p) {
-        return c.s + (int)((int64_t)(c.e - c.s) * p / in_npiece(c));
-    };
-    auto npiece = [&](const Chunk &c) {
-        return c.e - c.s >= 64 ? std::min(NPIECE, c.e - c.s) : byte_pieces(c) ? byte_npiece() : 1;
-    };
-    auto piece_b = [&](const Chunk &c, int p) {
-        return byte_pieces(c) ? c.s : c.s + (int)((int64_t)(c.e - c.s) * p / npiece(c));
-    };
-    auto piece_o = [&](const Chunk &c, int p) -> int64_t {
-        const int np = npiece(c);
-        if (p >= np) return c.tout;
-        if (byte_pieces(c)) return (c.tout * p / np) & ~(int64_t)15;
-        const int b = piece_b(c, p);
-        return b < c.e ? out_off[b] : c.tout;
-    };
-    auto layout = [&](const Chunk &c, uint8_t *base, uint8_t **in, uint8_t **outp, jfs_dev_block **desc, int32_t **ret,
-                      uint8_t **zinfo) {
-        const int64_t desc_bytes = align16((int64_t)(c.e - c.s) * (int64_t)sizeof(jfs_dev_block));
-        const int64_t ret_bytes = align16((int64_t)(c.e - c.s) * 4);
-        *in = base;
-        *outp = base + c.tin;
-        *desc = (jfs_dev_block *)(base + c.tin + c.tout);
-        *ret = (int32_t *)(base + c.tin + c.tout + desc_bytes);
-        *zinfo = base + c.tin + c.tout + desc_bytes + ret_bytes;
-    };
-    // the aead area follows the Zstd plan area: descriptors, results, key+nonce slots
-    auto aead_layout = [&](const Chunk &c, uint8_t *base, jfs_aead_block **ad, int32_t **ret2, uint8_t **kn) {
-        const int64_t nb = c.e - c.s;
-        uint8_t *p = base + c.tin + c.tout + align16(nb * (int64_t)sizeof(jfs_dev_block)) + align16(nb * 4) +
-                     align16(nb * zib);
-        *ad = (jfs_aead_block *)p;
-        p += align16(nb * (int64_t)sizeof(jfs_aead_block));
-        *ret2 = (int32_t *)p;
-        p += align16(nb * 4);
-        *kn = p;
-    };
-    auto aead_bytes = [&](int64_t nb) {
-        return ae ? align16(nb * (int64_t)sizeof(jfs_aead_block)) + align16(nb * 4) + align16(nb * 64) : 0;
-    };
-    // PUT-payload checksums: descriptors, seeds, results (after the aead area)
-    auto crc_layout = [&](const Chunk &c, uint8_t *base, jfs_dev_block **cd, uint32_t **seed, uint32_t **crc) {
-        const int64_t nb = c.e - c.s;
-        uint8_t *p = base + c.tin + c.tout + align16(nb * (int64_t)sizeof(jfs_dev_block)) + align16(nb * 4) +
-                     align16(nb * zib) + aead_bytes(nb);
-        *cd = (jfs_dev_block *)p;
-        p += align16(nb * (int64_t)sizeof(jfs_dev_block));
-        *seed = (uint32_t *)p;
-        p += align16(nb * 4);
-        *crc = (uint32_t *)p;
-    };
-    // decode-side disk-cache checksums (csum_out): descriptors, then every
-    // block's ((cap-1)/32 KiB+1)*4 checksum bytes (after the crc area)
-    const bool want_csum = csum_out && dir == DECOMPRESS && !ae;
-    auto csum_words = [&](int i) { return cap[i] > 0 ? (cap[i] - 1) / CSUM_SEG + 1 : 1; };
-    auto crc_bytes = [&](int64_t nb) {
-        return crc_out ? align16(nb * (int64_t)sizeof(jfs_dev_block)) + 2 * align16(nb * 4) : 0;
-    };
-    auto csum_layout = [&](const Chunk &c, uint8_t *base, jfs_dev_block **cd, uint8_t **area) {
-        const int64_t nb = c.e - c.s;
-        uint8_t *p = base + c.tin + c.tout + align16(nb * (int64_t)sizeof(jfs_dev_block)) + align16(nb * 4) +
-                     align16(nb * zib) + aead_bytes(nb) + crc_bytes(nb);
-        *cd = (jfs_dev_block *)p;
-        *area = p + align16(nb * (int64_t)sizeof(jfs_dev_block));
-    };
-    auto csum_area_bytes = [&](const Chunk &c) {
+    bool d2h(void *h, const void *d, int64_t n) const {
+        return hipMemcpyAsync(h, d, (size_t)n, hipMemcpyDeviceToHost, dev->s_out) == hipSuccess;
+    }
+    // what block i's codec descriptor holds (launch), known before it is staged (presize)
+    int32_t desc_len(int i) const { return (int32_t)iov[i].src_len; }
+    int32_t desc_cap(int i) const { return (int32_t)std::min<int64_t>(blk[i].cap, INT32_MAX); }
+    // a block's disk-cache checksums: ((cap-1)/32 KiB+1)*4 bytes, 16-aligned in the chunk's area
+    int64_t csum_words(int i) const { return blk[i].cap > 0 ? (blk[i].cap - 1) / CSUM_SEG + 1 : 1; }
+    int64_t csum_bytes(const Chunk &c) const {
         int64_t t = 0;
         for (int i = c.s; i < c.e; i++) t += align16(4 * csum_words(i));
         return t;
-    };
-    auto chunk_bytes = [&](const Chunk &c) {
-        const int64_t nb = c.e - c.s;
-        return c.tin + c.tout + align16(nb * (int64_t)sizeof(jfs_dev_block)) + align16(nb * 4) + align16(nb * zib) +
-               aead_bytes(nb) + crc_bytes(nb) +
-               (want_csum ? align16(nb * (int64_t)sizeof(jfs_dev_block)) + csum_area_bytes(c) : 0);
-    };
-    // stage the checksum descriptors: the decoded output is the data, the
-    // checksum bytes go to the chunk's checksum area
-    auto stage_csum = [&](const Chunk &c, Slot &sl, uint8_t *d_out) -> int64_t {
-        if (!want_csum) return JFS_OK;
-        const int n = c.e - c.s;
-        jfs_dev_block *h_cd, *d_cd;
-        uint8_t *h_area, *d_area;
-        csum_layout(c, sl.h, &h_cd, &h_area);
-        csum_layout(c, sl.d, &d_cd, &d_area);
-        int64_t o = 0;
-        for (int k = 0; k < n; k++) {
-            const int i = c.s + k;
-            h_cd[k] = jfs_dev_block{d_out + out_off[i], d_area + o, 0, (int32_t)(4 * csum_words(i))};
-            o += align16(4 * csum_words(i));
+    }
+
+    // stage the checksum descriptors (the decoded output is the data, the
+    // checksum bytes go to the chunk's checksum area) and queue their H2D
+    bool stage_csum(const Chunk &c, const Layout &L, Slot &sl) const {
+        if (!csum_out) return true;
+        jfs_dev_block *h_cd = Layout::at<jfs_dev_block>(sl.h, L.csum_desc);
+        uint8_t *d_out = Layout::at(sl.d, L.out), *d_area = Layout::at(sl.d, L.csum);
+        for (int i = c.s; i < c.e; i++) {
+            const int64_t bytes = 4 * csum_words(i);
+            h_cd[i - c.s] = jfs_dev_block{d_out + plan.out_off[i], d_area, 0, (int32_t)bytes};
+            d_area += align16(bytes);
         }
-        return hipMemcpyAsync(d_cd, h_cd, (size_t)n * sizeof(jfs_dev_block), hipMemcpyHostToDevice, dev->s_in) ==
-                       hipSuccess
-                   ? JFS_OK
-                   : JFS_ERR_HIP;
-    };
-    auto run_csum = [&](const Chunk &c, Slot &sl, const int32_t *d_lens) -> int64_t {
-        if (!want_csum) return JFS_OK;
-        jfs_dev_block *d_cd;
-        uint8_t *d_area;
-        csum_layout(c, sl.d, &d_cd, &d_area);
-        return jfs_launch_crc32c_segs_lens(d_cd, c.e - c.s, CSUM_SEG, d_lens, c.ks) == 0 ? JFS_OK : JFS_ERR_HIP;
-    };
-    auto fetch_csum = [&](const Chunk &c, Slot &sl) -> int64_t {
-        if (!want_csum) return JFS_OK;
-        jfs_dev_block *h_cd, *d_cd;
-        uint8_t *h_area, *d_area;
-        csum_layout(c, sl.h, &h_cd, &h_area);
-        csum_layout(c, sl.d, &d_cd, &d_area);
-        return hipMemcpyAsync(h_area, d_area, (size_t)csum_area_bytes(c), hipMemcpyDeviceToHost, dev->s_out) ==
-                       hipSuccess
-                   ? JFS_OK
-                   : JFS_ERR_HIP;
-    };
-    // stage the checksum descriptors (payload = the codec's output area) and
-    // queue their H2D on s_in; seeds: the envelope header's CRC for a seal
-    auto stage_crc = [&](const Chunk &c, Slot &sl, uint8_t *d_out) -> int64_t {
-        if (!crc_out) return JFS_OK;
-        const int n = c.e - c.s;
-        jfs_dev_block *h_cd, *d_cd;
-        uint32_t *h_seed, *d_seed, *h_crc, *d_crc;
-        crc_layout(c, sl.h, &h_cd, &h_seed, &h_crc);
-        crc_layout(c, sl.d, &d_cd, &d_seed, &d_crc);
-        for (int k = 0; k < n; k++) {
-            const int i = c.s + k;
-            h_cd[k] = jfs_dev_block{d_out + out_off[i], nullptr, 0, 0};
+        return h2d(Layout::at(sl.d, L.csum_desc), h_cd, (int64_t)(c.e - c.s) * (int64_t)sizeof(jfs_dev_block));
+    }
+    bool run_csum(const Chunk &c, const Layout &L, Slot &sl, const int32_t *d_lens, hipStream_t ks) const {
+        const jfs_dev_block *d_cd = Layout::at<jfs_dev_block>(sl.d, L.csum_desc);
+        return !csum_out || jfs_launch_crc32c_segs_lens(d_cd, c.e - c.s, CSUM_SEG, d_lens, ks) == 0;
+    }
+    bool fetch_csum(const Layout &L, Slot &sl) const {
+        return !csum_out || d2h(Layout::at(sl.h, L.csum), Layout::at(sl.d, L.csum), L.csum_bytes);
+    }
+    // PUT-payload checksums: stage the descriptors (payload = the codec's
+    // output area) and the seeds (the envelope header's CRC for a seal) and
+    // queue their H2D; after the kernels the checksum launch (lengths from the
+    // device), then its D2H
+    bool stage_crc(const Chunk &c, const Layout &L, Slot &sl) const {
+        if (!crc_out) return true;
+        jfs_dev_block *h_cd = Layout::at<jfs_dev_block>(sl.h, L.crc_desc);
+        uint32_t *h_seed = Layout::at<uint32_t>(sl.h, L.crc_seed);
+        for (int i = c.s; i < c.e; i++) {
+            const int k = i - c.s;
+            h_cd[k] = jfs_dev_block{Layout::at(sl.d, L.out) + plan.out_off[i], nullptr, 0, 0};
             h_seed[k] = 0;
             if (ae && ae->seal) {
                 const jfs_seal_param &p = ae->sp[i];
@@ -971,58 +906,135 @@ int64_t run_batch(DevCtx *dev, Lane &ln, int algo, int dir, int nblk, const jfs_
                 h_seed[k] = host_crc32c(v, ae->nonce[i], 12);
             }
         }
-        const size_t bytes = (size_t)(align16((int64_t)n * (int64_t)sizeof(jfs_dev_block)) + align16((int64_t)n * 4));
-        return hipMemcpyAsync(d_cd, h_cd, bytes, hipMemcpyHostToDevice, dev->s_in) == hipSuccess ? JFS_OK : JFS_ERR_HIP;
-    };
-    // after the kernels: the checksum launch (lengths from the device) and its D2H
-    auto run_crc = [&](const Chunk &c, Slot &sl, const int32_t *d_lens) -> int64_t {
-        if (!crc_out) return JFS_OK;
-        const int n = c.e - c.s;
-        jfs_dev_block *d_cd;
-        uint32_t *d_seed, *d_crc;
-        crc_layout(c, sl.d, &d_cd, &d_seed, &d_crc);
-        return jfs_launch_crc32c_lens(d_cd, n, d_lens, d_seed, d_crc, c.ks) == 0 ? JFS_OK : JFS_ERR_HIP;
-    };
-    auto fetch_crc = [&](const Chunk &c, Slot &sl) -> int64_t {
-        if (!crc_out) return JFS_OK;
-        jfs_dev_block *h_cd, *d_cd;
-        uint32_t *h_seed, *d_seed, *h_crc, *d_crc;
-        crc_layout(c, sl.h, &h_cd, &h_seed, &h_crc);
-        crc_layout(c, sl.d, &d_cd, &d_seed, &d_crc);
-        return hipMemcpyAsync(h_crc, d_crc, (size_t)(c.e - c.s) * 4, hipMemcpyDeviceToHost, dev->s_out) == hipSuccess
-                   ? JFS_OK
-                   : JFS_ERR_HIP;
-    };
-    (void)aeb;
-    // compress -> seal, or open -> decompress (the staged inputs and the
-    // LZ4 encode of a staged chunk: segment-parallel for small batches
-    const bool lz4_fast = lz4_fast_mode();  // the mode when this batch started
-    auto lz4_encode = [&](Slot &sl, const jfs_dev_block *h_desc, const jfs_dev_block *d_desc, int n, int32_t *d_ret,
-                          hipStream_t ks) -> int64_t {
-        if (!lz4_fast && n > eseg_max()) return jfs_launch_lz4_encode(d_desc, n, d_ret, ks) == 0 ? JFS_OK : JFS_ERR_HIP;
-        std::vector<int32_t> lens(n);
-        for (int k = 0; k < n; k++) lens[k] = h_desc[k].src_len;
-        if (lz4_fast) {
-            if (!sl.ensure_split(jfs_lz4_fast_scratch_bytes(n, lens.data()))) return JFS_ERR_NO_MEMORY;
-            return jfs_launch_lz4_fast(d_desc, n, lens.data(), d_ret, sl.sp, sl.sp_cap, ks) == 0 ? JFS_OK : JFS_ERR_HIP;
+        return h2d(Layout::at(sl.d, L.crc_desc), h_cd, L.crc - L.crc_desc);  // descriptors and seeds
+    }
+    bool run_crc(const Chunk &c, const Layout &L, Slot &sl, const int32_t *d_lens, hipStream_t ks) const {
+        const jfs_dev_block *d_cd = Layout::at<jfs_dev_block>(sl.d, L.crc_desc);
+        uint32_t *d_seed = Layout::at<uint32_t>(sl.d, L.crc_seed), *d_crc = Layout::at<uint32_t>(sl.d, L.crc);
+        return !crc_out || jfs_launch_crc32c_lens(d_cd, c.e - c.s, d_lens, d_seed, d_crc, ks) == 0;
+    }
+    bool fetch_crc(const Chunk &c, const Layout &L, Slot &sl) const {
+        return !crc_out || d2h(Layout::at(sl.h, L.crc), Layout::at(sl.d, L.crc), (int64_t)(c.e - c.s) * 4);
+    }
+
+    // Size every slot for all of its chunks (staging, LZ4 small-batch scratch)
+    // before the first launch: growing a slot mid-batch frees the old buffer,
+    // and hipFree waits for the whole device -- the batch's own chunks in
+    // flight (64 ms of a 273 ms 1,024-block decode).  A size that cannot be
+    // had is left to the chunk's own ensure(), which reports it.
+    void presize() {
+        int64_t need[NSLOT] = {}, need_sp[NSLOT] = {};
+        for (size_t k = 0; k < plan.ch.size(); k++) {
+            const Chunk &c = plan.ch[k];
+            need[c.slot] = std::max(need[c.slot], lay[k].total);
+            const int n = c.e - c.s;
+            if (algo == JFS_ALGO_LZ4 && dir == DECOMPRESS && !ae) {
+                std::vector<int32_t> lens(n), caps(n);
+                for (int i = 0; i < n; i++) {
+                    lens[i] = desc_len(c.s + i);
+                    caps[i] = desc_cap(c.s + i);
+                }
+                need_sp[c.slot] = std::max(need_sp[c.slot], lz4_decode_scratch(n, lens.data(), caps.data()));
+            }
         }
-        if (!sl.ensure_split(jfs_lz4_eseg_scratch_bytes(n, lens.data()))) return JFS_ERR_NO_MEMORY;
-        return jfs_launch_lz4_encode_seg(d_desc, n, lens.data(), d_ret, sl.sp, sl.sp_cap, ks) == 0 ? JFS_OK
-                                                                                                   : JFS_ERR_HIP;
-    };
-    // codec descriptors are already in place; run on the lane's kernel stream)
-    auto launch_aead = [&](const Chunk &c, Slot &sl, uint8_t *h_in, uint8_t *h_out, jfs_dev_block *h_desc,
-                           int32_t *h_ret, uint8_t *d_in, uint8_t *d_out, jfs_dev_block *d_desc,
-                           int32_t *d_ret) -> int64_t {
+        for (int s = 0; s < NSLOT; s++) {
+            if (need[s] > 0) (void)ln.slot[s].ensure(need[s]);
+            if (need_sp[s] > 0) (void)ln.slot[s].ensure_split(need_sp[s]);
+        }
+    }
+
+    // Stage a chunk and queue its H2D (s_in), kernels (its kernel stream) and D2H (s_out).
+    int64_t launch(int chunk) {
+        const Chunk &c = plan.ch[chunk];
+        const Layout &L = lay[chunk];
+        Slot &sl = ln.slot[c.slot];
+        if (!sl.ensure(L.total)) return JFS_ERR_NO_MEMORY;
+        const hipStream_t ks = kstream(chunk);
         const int n = c.e - c.s;
-        jfs_aead_block *h_ad, *d_ad;
-        int32_t *h_r2, *d_r2;
-        uint8_t *h_kn, *d_kn;
-        aead_layout(c, sl.h, &h_ad, &h_r2, &h_kn);
-        aead_layout(c, sl.d, &d_ad, &d_r2, &d_kn);
+        uint8_t *h_in = Layout::at(sl.h, L.in), *h_out = Layout::at(sl.h, L.out);
+        uint8_t *d_in = Layout::at(sl.d, L.in), *d_out = Layout::at(sl.d, L.out);
+        jfs_dev_block *h_desc = Layout::at<jfs_dev_block>(sl.h, L.desc);
+        jfs_dev_block *d_desc = Layout::at<jfs_dev_block>(sl.d, L.desc);
+        int32_t *h_ret = Layout::at<int32_t>(sl.h, L.ret), *d_ret = Layout::at<int32_t>(sl.d, L.ret);
+        for (int i = c.s; i < c.e; i++)
+            h_desc[i - c.s] = jfs_dev_block{d_in + plan.in_off[i], d_out + plan.out_off[i], desc_len(i), desc_cap(i)};
+        const double t0 = host_trace() ? now_ms() : 0.0;
+        // Stage the inputs in pieces (NPIECE), each piece's H2D issued as soon as
+        // it is staged so that it overlaps the staging of the next (the
+        // encrypted path stages everything first: launch_aead issues its H2D).
+        for (int p = 0; p < pieces.in_npiece(c); p++) {
+            const int b0 = pieces.in_piece_b(c, p), b1 = pieces.in_piece_b(c, p + 1);
+            std::vector<CopyJob> jobs;
+            for (int i = b0; i < b1; i++)
+                if (iov[i].src_len > 0) jobs.push_back({h_in + plan.in_off[i], iov[i].src, iov[i].src_len});
+            par_copy(jobs);
+            if (ae) continue;
+            const int64_t o0 = plan.in_off[b0], o1 = b1 < c.e ? plan.in_off[b1] : c.tin;
+            if (o1 > o0 && !h2d(d_in + o0, h_in + o0, o1 - o0)) return JFS_ERR_HIP;
+        }
+        if (host_trace())
+            fprintf(stderr, "[jfs host] t=%.2f lane %d algo %d dir %d chunk %d-%d stage-in %.1f MiB %.2f ms\n",
+                    now_ms(), (int)(&ln - dev->lane), algo, dir, c.s, c.e, c.tin / 1048576.0, now_ms() - t0);
+        if (ae) return launch_aead(c, L, sl, ks);
+        if (algo != JFS_ALGO_LZ4 && algo != JFS_ALGO_ZSTD) return JFS_ERR_UNSUPPORTED;
+        uint64_t ztot[6] = {0, 0, 0, 0, 0, 0};
+        uint8_t *h_zi = Layout::at(sl.h, L.zinfo), *d_zi = Layout::at(sl.d, L.zinfo);
+        if (zplan) {  // plan the Zstd scratch from the staged inputs: no device round trip
+            std::vector<const uint8_t *> srcs(n);
+            for (int i = 0; i < n; i++) srcs[i] = h_in + plan.in_off[c.s + i];
+            jfs_zstd_plan_host(srcs.data(), desc_lens(h_desc, n).data(), desc_caps(h_desc, n).data(), n, h_zi, ztot);
+            if (!sl.ensure_zstd(ztot)) return JFS_ERR_NO_MEMORY;
+            if (jfs_zstd_split_ok(n, ztot) && !sl.ensure_split(jfs_zstd_split_bytes(n, ztot))) return JFS_ERR_NO_MEMORY;
+        }
+        if (!h2d(d_desc, h_desc, (int64_t)n * (int64_t)sizeof(jfs_dev_block))) return JFS_ERR_HIP;
+        if (zplan && !h2d(d_zi, h_zi, n * zib)) return JFS_ERR_HIP;
+        if (dir == COMPRESS && !stage_crc(c, L, sl)) return JFS_ERR_HIP;
+        if (!stage_csum(c, L, sl)) return JFS_ERR_HIP;
+        if (hipEventRecord(sl.ev_in, dev->s_in) != hipSuccess) return JFS_ERR_HIP;
+        if (hipStreamWaitEvent(ks, sl.ev_in, 0) != hipSuccess) return JFS_ERR_HIP;
+        int64_t r;
+        if (zplan)
+            r = launch_rc(jfs_launch_zstd_decode_planned(d_desc, n, d_ret, d_zi, sl.z_lit, sl.z_tabs, sl.z_items,
+                                                         jfs_zstd_split_ok(n, ztot) ? sl.sp : nullptr, ztot, ks));
+        else if (algo == JFS_ALGO_LZ4 && dir == DECOMPRESS)
+            r = launch_lz4_decode(sl, h_desc, d_desc, n, d_ret, ks);
+        else if (algo == JFS_ALGO_LZ4)
+            r = launch_lz4_encode(sl, h_desc, d_desc, n, d_ret, ks, lz4_fast);
+        else
+            r = launch_rc(launch_kernel(algo, dir, d_desc, n, d_ret, ks));
+        if (r != JFS_OK) return r;
+        if (dir == COMPRESS && !run_crc(c, L, sl, d_ret, ks)) return JFS_ERR_HIP;
+        if (!run_csum(c, L, sl, d_ret, ks)) return JFS_ERR_HIP;
+        if (hipEventRecord(sl.ev_k, ks) != hipSuccess) return JFS_ERR_HIP;
+        if (hipStreamWaitEvent(dev->s_out, sl.ev_k, 0) != hipSuccess) return JFS_ERR_HIP;
+        if (!d2h(h_ret, d_ret, (int64_t)n * 4)) return JFS_ERR_HIP;
+        if (dir == COMPRESS && !fetch_crc(c, L, sl)) return JFS_ERR_HIP;
+        if (!fetch_csum(L, sl)) return JFS_ERR_HIP;
+        for (int p = 0; p < pieces.npiece(c); p++) {  // output bytes [piece_o(c, p), piece_o(c, p + 1))
+            const int64_t o0 = pieces.piece_o(c, p, plan.out_off.data());
+            const int64_t o1 = pieces.piece_o(c, p + 1, plan.out_off.data());
+            if (o1 > o0 && !d2h(h_out + o0, d_out + o0, o1 - o0)) return JFS_ERR_HIP;
+            if (hipEventRecord(sl.ev_p[p], dev->s_out) != hipSuccess) return JFS_ERR_HIP;
+        }
+        if (hipEventRecord(sl.ev, dev->s_out) != hipSuccess) return JFS_ERR_HIP;
+        return JFS_OK;
+    }
+
+    // compress -> seal, or open -> decompress (the staged inputs and the
+    // codec descriptors are already in place; run on the chunk's kernel stream)
+    int64_t launch_aead(const Chunk &c, const Layout &L, Slot &sl, hipStream_t ks) {
+        const int n = c.e - c.s;
+        uint8_t *d_in = Layout::at(sl.d, L.in), *d_out = Layout::at(sl.d, L.out);
+        jfs_dev_block *h_desc = Layout::at<jfs_dev_block>(sl.h, L.desc);
+        jfs_dev_block *d_desc = Layout::at<jfs_dev_block>(sl.d, L.desc);
+        jfs_aead_block *h_ad = Layout::at<jfs_aead_block>(sl.h, L.aead_desc);
+        jfs_aead_block *d_ad = Layout::at<jfs_aead_block>(sl.d, L.aead_desc);
+        int32_t *d_ret = Layout::at<int32_t>(sl.d, L.ret), *d_r2 = Layout::at<int32_t>(sl.d, L.aead_ret);
+        uint8_t *h_kn = Layout::at(sl.h, L.aead_kn), *d_kn = Layout::at(sl.d, L.aead_kn);
         const int klen = jfs_cipher_key_size(ae->cipher);
         for (int k = 0; k < n; k++) {
             const int i = c.s + k;
+            const int64_t cap = blk[i].cap, io = plan.in_off[i], oo = plan.out_off[i];
             memcpy(h_kn + 64 * k, ae->key[i], (size_t)klen);
             memcpy(h_kn + 64 * k + 32, ae->nonce[i], 12);
             jfs_aead_block &a = h_ad[k];
@@ -1030,196 +1042,68 @@ int64_t run_batch(DevCtx *dev, Lane &ln, int algo, int dir, int nblk, const jfs_
             a.nonce = d_kn + 64 * k + 32;
             if (ae->seal) {
                 // the codec writes the payload area; the seal runs in place over it
-                h_desc[k].dst_cap = (int32_t)(cap[i] - 16);
-                a.src = algo == JFS_ALGO_NONE ? d_in + in_off[i] : d_out + out_off[i];
-                a.dst = d_out + out_off[i];
+                h_desc[k].dst_cap = (int32_t)(cap - 16);
+                a.src = algo == JFS_ALGO_NONE ? d_in + io : d_out + oo;
+                a.dst = d_out + oo;
                 a.src_len = (int32_t)iov[i].src_len;
-                a.dst_cap = (int32_t)cap[i];
+                a.dst_cap = (int32_t)cap;
             } else {
                 // open in place over the staged payload (into the output for "none"),
                 // then the codec reads the plaintext: the payload minus its tag
                 h_desc[k].src_len = (int32_t)std::max<int64_t>(iov[i].src_len - 16, 0);
-                a.src = d_in + in_off[i];
-                a.dst = algo == JFS_ALGO_NONE ? d_out + out_off[i] : d_in + in_off[i];
+                a.src = d_in + io;
+                a.dst = algo == JFS_ALGO_NONE ? d_out + oo : d_in + io;
                 a.src_len = (int32_t)iov[i].src_len;
-                a.dst_cap = algo == JFS_ALGO_NONE ? (int32_t)cap[i] : (int32_t)iov[i].src_len;
+                a.dst_cap = algo == JFS_ALGO_NONE ? (int32_t)cap : (int32_t)iov[i].src_len;
             }
         }
-        const int64_t ab = aead_bytes(n);
-        if (hipMemcpyAsync(d_in, h_in, (size_t)c.tin, hipMemcpyHostToDevice, dev->s_in) != hipSuccess) return JFS_ERR_HIP;
-        if (hipMemcpyAsync(d_desc, h_desc, (size_t)n * sizeof(jfs_dev_block), hipMemcpyHostToDevice, dev->s_in) !=
-            hipSuccess)
-            return JFS_ERR_HIP;
-        if (hipMemcpyAsync(d_ad, h_ad, (size_t)ab, hipMemcpyHostToDevice, dev->s_in) != hipSuccess) return JFS_ERR_HIP;
-        if (stage_crc(c, sl, d_out) != JFS_OK) return JFS_ERR_HIP;
+        if (!h2d(d_in, Layout::at(sl.h, L.in), c.tin)) return JFS_ERR_HIP;
+        if (!h2d(d_desc, h_desc, (int64_t)n * (int64_t)sizeof(jfs_dev_block))) return JFS_ERR_HIP;
+        if (!h2d(d_ad, h_ad, L.aead_bytes)) return JFS_ERR_HIP;
+        if (!stage_crc(c, L, sl)) return JFS_ERR_HIP;
         if (hipEventRecord(sl.ev_in, dev->s_in) != hipSuccess) return JFS_ERR_HIP;
-        if (hipStreamWaitEvent(c.ks, sl.ev_in, 0) != hipSuccess) return JFS_ERR_HIP;
-        int lk = 0;
+        if (hipStreamWaitEvent(ks, sl.ev_in, 0) != hipSuccess) return JFS_ERR_HIP;
+        int64_t r = JFS_OK;
         if (ae->seal) {
-            if (algo == JFS_ALGO_LZ4) {
-                const int64_t r = lz4_encode(sl, h_desc, d_desc, n, d_ret, c.ks);
-                if (r == JFS_ERR_NO_MEMORY) return r;
-                lk = r == JFS_OK ? 0 : -1;
-            } else if (algo != JFS_ALGO_NONE) {
-                lk = launch_kernel(algo, COMPRESS, d_desc, n, d_ret, c.ks);
-            }
-            if (lk == 0)
-                lk = jfs_launch_aead(ae->cipher, d_ad, n, 0, d_r2, algo != JFS_ALGO_NONE ? d_ret : nullptr, c.ks);
+            if (algo == JFS_ALGO_LZ4) r = launch_lz4_encode(sl, h_desc, d_desc, n, d_ret, ks, lz4_fast);
+            else if (algo != JFS_ALGO_NONE) r = launch_rc(launch_kernel(algo, COMPRESS, d_desc, n, d_ret, ks));
+            if (r == JFS_OK)
+                r = launch_rc(
+                    jfs_launch_aead(ae->cipher, d_ad, n, 0, d_r2, algo != JFS_ALGO_NONE ? d_ret : nullptr, ks));
         } else {
-            lk = jfs_launch_aead(ae->cipher, d_ad, n, 1, d_r2, nullptr, c.ks);
-            if (lk == 0 && algo == JFS_ALGO_LZ4) {
-                if (n <= split_max()) {
-                    std::vector<int32_t> lens(n), caps(n);
-                    int64_t nseg = 0, max_cap = 0, norg = 0;
-                    for (int k = 0; k < n; k++) {
-                        lens[k] = h_desc[k].src_len;
-                        caps[k] = h_desc[k].dst_cap;
-                        nseg += (std::max(lens[k], 0) + JFS_LZ4_SPLIT_SEG - 1) / JFS_LZ4_SPLIT_SEG;
-                        max_cap = std::max<int64_t>(max_cap, caps[k]);
-                        norg += (std::max<int64_t>(caps[k], 0) + 3) & ~3ll;
-                    }
-                    if (!sl.ensure_split(jfs_lz4_split_scratch_bytes(n, lens.data(), caps.data())))
-                        return JFS_ERR_NO_MEMORY;
-                    lk = jfs_launch_lz4_split(d_desc, n, d_ret, sl.sp, nseg, max_cap, norg, c.ks);
-                } else {
-                    lk = jfs_launch_lz4_decode(d_desc, n, d_ret, c.ks);
-                }
-            } else if (lk == 0 && algo == JFS_ALGO_ZSTD) {
-                // the host holds ciphertext only: the device API plans the scratch itself
-                lk = jfs_launch_zstd_decode(d_desc, n, d_ret, nullptr, c.ks);
-            }
+            r = launch_rc(jfs_launch_aead(ae->cipher, d_ad, n, 1, d_r2, nullptr, ks));
+            if (r == JFS_OK && algo == JFS_ALGO_LZ4) r = launch_lz4_decode(sl, h_desc, d_desc, n, d_ret, ks);
+            // Zstd: the host holds ciphertext only, the device API plans the scratch itself
+            if (r == JFS_OK && algo == JFS_ALGO_ZSTD)
+                r = launch_rc(jfs_launch_zstd_decode(d_desc, n, d_ret, nullptr, ks));
         }
-        if (lk != 0) return JFS_ERR_HIP;
-        if (ae->seal && run_crc(c, sl, d_r2) != JFS_OK) return JFS_ERR_HIP;
-        if (hipEventRecord(sl.ev_k, c.ks) != hipSuccess) return JFS_ERR_HIP;
+        if (r != JFS_OK) return r;
+        if (ae->seal && !run_crc(c, L, sl, d_r2, ks)) return JFS_ERR_HIP;
+        if (hipEventRecord(sl.ev_k, ks) != hipSuccess) return JFS_ERR_HIP;
         if (hipStreamWaitEvent(dev->s_out, sl.ev_k, 0) != hipSuccess) return JFS_ERR_HIP;
-        if (hipMemcpyAsync(h_ret, d_ret, (size_t)n * 4, hipMemcpyDeviceToHost, dev->s_out) != hipSuccess)
-            return JFS_ERR_HIP;
-        if (hipMemcpyAsync(h_r2, d_r2, (size_t)n * 4, hipMemcpyDeviceToHost, dev->s_out) != hipSuccess)
-            return JFS_ERR_HIP;
-        if (ae->seal && fetch_crc(c, sl) != JFS_OK) return JFS_ERR_HIP;
-        if (hipMemcpyAsync(h_out, d_out, (size_t)c.tout, hipMemcpyDeviceToHost, dev->s_out) != hipSuccess)
-            return JFS_ERR_HIP;
+        if (!d2h(Layout::at(sl.h, L.ret), d_ret, (int64_t)n * 4)) return JFS_ERR_HIP;
+        if (!d2h(Layout::at(sl.h, L.aead_ret), d_r2, (int64_t)n * 4)) return JFS_ERR_HIP;
+        if (ae->seal && !fetch_crc(c, L, sl)) return JFS_ERR_HIP;
+        if (!d2h(Layout::at(sl.h, L.out), d_out, c.tout)) return JFS_ERR_HIP;
         if (hipEventRecord(sl.ev, dev->s_out) != hipSuccess) return JFS_ERR_HIP;
         return JFS_OK;
-    };
-    auto launch = [&](const Chunk &c) -> int64_t {
-        Slot &sl = ln.slot[c.slot];
-        if (!sl.ensure(chunk_bytes(c))) return JFS_ERR_NO_MEMORY;
-        uint8_t *h_in, *h_out, *d_in, *d_out, *h_zi, *d_zi;
-        jfs_dev_block *h_desc, *d_desc;
-        int32_t *h_ret, *d_ret;
-        layout(c, sl.h, &h_in, &h_out, &h_desc, &h_ret, &h_zi);
-        layout(c, sl.d, &d_in, &d_out, &d_desc, &d_ret, &d_zi);
-        for (int i = c.s; i < c.e; i++) {
-            const int k = i - c.s;
-            h_desc[k].src = d_in + in_off[i];
-            h_desc[k].dst = d_out + out_off[i];
-            h_desc[k].src_len = (int32_t)iov[i].src_len;
-            h_desc[k].dst_cap = (int32_t)std::min<int64_t>(cap[i], INT32_MAX);
-        }
-        const double t0 = host_trace() ? now_ms() : 0.0;
-        // Stage the inputs in pieces (NPIECE), each piece's H2D issued as soon as
-        // it is staged so that it overlaps the staging of the next (the
-        // encrypted path stages everything first: launch_aead issues its H2D).
-        for (int p = 0; p < in_npiece(c); p++) {
-            const int b0 = in_piece_b(c, p), b1 = in_piece_b(c, p + 1);
-            std::vector<CopyJob> jobs;
-            for (int i = b0; i < b1; i++)
-                if (iov[i].src_len > 0) jobs.push_back({h_in + in_off[i], iov[i].src, iov[i].src_len});
-            par_copy(jobs);
-            if (ae) continue;
-            const int64_t o0 = in_off[b0], o1 = b1 < c.e ? in_off[b1] : c.tin;
-            if (o1 > o0 && hipMemcpyAsync(d_in + o0, h_in + o0, (size_t)(o1 - o0), hipMemcpyHostToDevice, dev->s_in) !=
-                               hipSuccess)
-                return JFS_ERR_HIP;
-        }
-        if (host_trace())
-            fprintf(stderr, "[jfs host] t=%.2f lane %d algo %d dir %d chunk %d-%d stage-in %.1f MiB %.2f ms\n",
-                    now_ms(), (int)(&ln - dev->lane), algo, dir, c.s, c.e, c.tin / 1048576.0, now_ms() - t0);
-        const int n = c.e - c.s;
-        uint64_t ztot[6] = {0, 0, 0, 0, 0, 0};
-        if (ae) return launch_aead(c, sl, h_in, h_out, h_desc, h_ret, d_in, d_out, d_desc, d_ret);
-        if (algo != JFS_ALGO_LZ4 && algo != JFS_ALGO_ZSTD) return JFS_ERR_UNSUPPORTED;
-        if (zplan) {  // plan the Zstd scratch from the staged inputs: no device round trip
-            std::vector<const uint8_t *> srcs(n);
-            std::vector<int32_t> lens(n), caps(n);
-            for (int k = 0; k < n; k++) {
-                srcs[k] = h_in + in_off[c.s + k];
-                lens[k] = h_desc[k].src_len;
-                caps[k] = h_desc[k].dst_cap;
-            }
-            jfs_zstd_plan_host(srcs.data(), lens.data(), caps.data(), n, h_zi, ztot);
-            if (!sl.ensure_zstd(ztot)) return JFS_ERR_NO_MEMORY;
-            if (jfs_zstd_split_ok(n, ztot) && !sl.ensure_split(jfs_zstd_split_bytes(n, ztot))) return JFS_ERR_NO_MEMORY;
-        }
-        if (hipMemcpyAsync(d_desc, h_desc, (size_t)n * sizeof(jfs_dev_block), hipMemcpyHostToDevice, dev->s_in) !=
-            hipSuccess)
-            return JFS_ERR_HIP;
-        if (zplan && hipMemcpyAsync(d_zi, h_zi, (size_t)(n * zib), hipMemcpyHostToDevice, dev->s_in) != hipSuccess)
-            return JFS_ERR_HIP;
-        if (dir == COMPRESS && stage_crc(c, sl, d_out) != JFS_OK) return JFS_ERR_HIP;
-        if (stage_csum(c, sl, d_out) != JFS_OK) return JFS_ERR_HIP;
-        if (hipEventRecord(sl.ev_in, dev->s_in) != hipSuccess) return JFS_ERR_HIP;
-        if (hipStreamWaitEvent(c.ks, sl.ev_in, 0) != hipSuccess) return JFS_ERR_HIP;
-        int lk;
-        if (zplan) {
-            lk = jfs_launch_zstd_decode_planned(d_desc, n, d_ret, d_zi, sl.z_lit, sl.z_tabs, sl.z_items,
-                                                jfs_zstd_split_ok(n, ztot) ? sl.sp : nullptr, ztot, c.ks);
-        } else if (algo == JFS_ALGO_LZ4 && dir == DECOMPRESS && n <= split_max()) {
-            std::vector<int32_t> lens(n), caps(n);
-            int64_t nseg = 0, max_cap = 0, norg = 0;
-            for (int k = 0; k < n; k++) {
-                lens[k] = h_desc[k].src_len;
-                caps[k] = h_desc[k].dst_cap;
-                nseg += (std::max(lens[k], 0) + JFS_LZ4_SPLIT_SEG - 1) / JFS_LZ4_SPLIT_SEG;
-                max_cap = std::max<int64_t>(max_cap, caps[k]);
-                norg += (std::max<int64_t>(caps[k], 0) + 3) & ~3ll;
-            }
-            if (!sl.ensure_split(jfs_lz4_split_scratch_bytes(n, lens.data(), caps.data()))) return JFS_ERR_NO_MEMORY;
-            lk = jfs_launch_lz4_split(d_desc, n, d_ret, sl.sp, nseg, max_cap, norg, c.ks);
-        } else if (algo == JFS_ALGO_LZ4 && dir == COMPRESS) {
-            const int64_t r = lz4_encode(sl, h_desc, d_desc, n, d_ret, c.ks);
-            if (r == JFS_ERR_NO_MEMORY) return r;
-            lk = r == JFS_OK ? 0 : -1;
-        } else {
-            lk = launch_kernel(algo, dir, d_desc, n, d_ret, c.ks);
-        }
-        if (lk != 0) return JFS_ERR_HIP;
-        if (dir == COMPRESS && run_crc(c, sl, d_ret) != JFS_OK) return JFS_ERR_HIP;
-        if (run_csum(c, sl, d_ret) != JFS_OK) return JFS_ERR_HIP;
-        if (hipEventRecord(sl.ev_k, c.ks) != hipSuccess) return JFS_ERR_HIP;
-        if (hipStreamWaitEvent(dev->s_out, sl.ev_k, 0) != hipSuccess) return JFS_ERR_HIP;
-        if (hipMemcpyAsync(h_ret, d_ret, (size_t)n * 4, hipMemcpyDeviceToHost, dev->s_out) != hipSuccess)
-            return JFS_ERR_HIP;
-        if (dir == COMPRESS && fetch_crc(c, sl) != JFS_OK) return JFS_ERR_HIP;
-        if (fetch_csum(c, sl) != JFS_OK) return JFS_ERR_HIP;
-        for (int p = 0; p < npiece(c); p++) {  // output bytes [piece_o(c, p), piece_o(c, p + 1))
-            const int64_t o0 = piece_o(c, p), o1 = piece_o(c, p + 1);
-            if (o1 > o0 && hipMemcpyAsync(h_out + o0, d_out + o0, (size_t)(o1 - o0), hipMemcpyDeviceToHost,
-                                          dev->s_out) != hipSuccess)
-                return JFS_ERR_HIP;
-            if (hipEventRecord(sl.ev_p[p], dev->s_out) != hipSuccess) return JFS_ERR_HIP;
-        }
-        if (hipEventRecord(sl.ev, dev->s_out) != hipSuccess) return JFS_ERR_HIP;
-        return JFS_OK;
-    };
-    auto finish = [&](const Chunk &c) -> int64_t {
+    }
+
+    // Wait for a chunk and copy its results and outputs to the caller.
+    int64_t finish(int chunk) {
+        const Chunk &c = plan.ch[chunk];
+        const Layout &L = lay[chunk];
         Slot &sl = ln.slot[c.slot];
         const double t0 = host_trace() ? now_ms() : 0.0;
         // (results, CRCs and checksums land before the first output piece)
         if (hipEventSynchronize(ae ? sl.ev : sl.ev_p[0]) != hipSuccess) return JFS_ERR_HIP;
         const double t1 = host_trace() ? now_ms() : 0.0;
-        uint8_t *h_in, *h_out, *h_zi;
-        jfs_dev_block *h_desc;
-        int32_t *h_ret;
-        layout(c, sl.h, &h_in, &h_out, &h_desc, &h_ret, &h_zi);
+        const uint8_t *h_out = Layout::at(sl.h, L.out);
+        const int32_t *h_ret = Layout::at<int32_t>(sl.h, L.ret);
+        const int64_t *out_off = plan.out_off.data();
         std::vector<CopyJob> jobs;
         if (ae) {
-            jfs_aead_block *h_ad;
-            int32_t *h_r2;
-            uint8_t *h_kn;
-            aead_layout(c, sl.h, &h_ad, &h_r2, &h_kn);
+            const int32_t *h_r2 = Layout::at<int32_t>(sl.h, L.aead_ret);
             for (int i = c.s; i < c.e; i++) {
                 const int k = i - c.s;
                 const jfs_iov &o = ae->orig[i];
@@ -1254,8 +1138,9 @@ int64_t run_batch(DevCtx *dev, Lane &ln, int algo, int dir, int nblk, const jfs_
             }
         } else {
             for (int i = c.s; i < c.e; i++) out[i] = finish_result(algo, dir, h_ret[i - c.s]);
-            for (int p = 0; p < npiece(c); p++) {  // each piece's copy-out as soon as it landed
-                if (p > 0 && byte_pieces(c)) {  // (a piece of a lone block: spin, it lands within microseconds)
+            const bool bytewise = pieces.byte_pieces(c);
+            for (int p = 0; p < pieces.npiece(c); p++) {  // each piece's copy-out as soon as it landed
+                if (p > 0 && bytewise) {  // (a piece of a lone block: spin, it lands within microseconds)
                     hipError_t q;
                     while ((q = hipEventQuery(sl.ev_p[p])) == hipErrorNotReady) {
                     }
@@ -1264,8 +1149,8 @@ int64_t run_batch(DevCtx *dev, Lane &ln, int algo, int dir, int nblk, const jfs_
                     return JFS_ERR_HIP;
                 }
                 std::vector<CopyJob> pj;
-                const int64_t p0 = piece_o(c, p), p1 = piece_o(c, p + 1);
-                const int i0 = byte_pieces(c) ? c.s : piece_b(c, p), i1 = byte_pieces(c) ? c.e : piece_b(c, p + 1);
+                const int64_t p0 = pieces.piece_o(c, p, out_off), p1 = pieces.piece_o(c, p + 1, out_off);
+                const int i0 = bytewise ? c.s : pieces.piece_b(c, p), i1 = bytewise ? c.e : pieces.piece_b(c, p + 1);
                 for (int i = i0; i < i1; i++) {  // the part of block i's output inside the piece
                     if (out[i] <= 0) continue;
                     const int64_t lo = std::max(out_off[i], p0), hi = std::min(out_off[i] + out[i], p1);
@@ -1275,15 +1160,11 @@ int64_t run_batch(DevCtx *dev, Lane &ln, int algo, int dir, int nblk, const jfs_
             }
         }
         if (crc_out) {
-            jfs_dev_block *h_cd;
-            uint32_t *h_seed, *h_crc;
-            crc_layout(c, sl.h, &h_cd, &h_seed, &h_crc);
+            const uint32_t *h_crc = Layout::at<uint32_t>(sl.h, L.crc);
             for (int i = c.s; i < c.e; i++) crc_out[i] = out[i] >= 0 ? h_crc[i - c.s] : 0u;
         }
-        if (want_csum) {
-            jfs_dev_block *h_cd;
-            uint8_t *h_area;
-            csum_layout(c, sl.h, &h_cd, &h_area);
+        if (csum_out) {
+            const uint8_t *h_area = Layout::at(sl.h, L.csum);
             int64_t o = 0;
             for (int i = c.s; i < c.e; i++) {
                 if (csum_out[i] && out[i] >= 0) {
@@ -1295,54 +1176,55 @@ int64_t run_batch(DevCtx *dev, Lane &ln, int algo, int dir, int nblk, const jfs_
         }
         par_copy(jobs);
         if (host_trace())
-            fprintf(stderr, "[jfs host] t=%.2f chunk %d-%d wait %.2f ms copy-out %.1f MiB %.2f ms\n", now_ms(), c.s, c.e, t1 - t0,
-                    c.tout / 1048576.0, now_ms() - t1);
+            fprintf(stderr, "[jfs host] t=%.2f chunk %d-%d wait %.2f ms copy-out %.1f MiB %.2f ms\n", now_ms(), c.s, c.e,
+                    t1 - t0, c.tout / 1048576.0, now_ms() - t1);
         return JFS_OK;
-    };
-    const int nch = (int)ch.size();
-    // Size every slot for all of its chunks (staging, LZ4 small-batch scratch)
-    // before the first launch: growing a slot mid-batch frees the old buffer,
-    // and hipFree waits for the whole device -- the batch's own chunks in
-    // flight (64 ms of a 273 ms 1,024-block decode).  A size that cannot be
-    // had is left to the chunk's own ensure(), which reports it.
-    {
-        int64_t need[NSLOT] = {}, need_sp[NSLOT] = {};
-        for (const Chunk &c : ch) {
-            need[c.slot] = std::max(need[c.slot], chunk_bytes(c));
-            const int n = c.e - c.s;
-            if (algo == JFS_ALGO_LZ4 && dir == DECOMPRESS && !ae && n <= split_max()) {
-                std::vector<int32_t> lens(n), caps(n);
-                for (int k = 0; k < n; k++) {
-                    lens[k] = (int32_t)iov[c.s + k].src_len;
-                    caps[k] = (int32_t)std::min<int64_t>(cap[c.s + k], INT32_MAX);
-                }
-                need_sp[c.slot] = std::max(need_sp[c.slot], jfs_lz4_split_scratch_bytes(n, lens.data(), caps.data()));
-            }
-        }
-        for (int s = 0; s < NSLOT; s++) {
-            if (need[s] > 0) (void)ln.slot[s].ensure(need[s]);
-            if (need_sp[s] > 0) (void)ln.slot[s].ensure_split(need_sp[s]);
-        }
     }
-    int64_t rc = JFS_OK;
-    int done = 0;  // chunks [0, done) finished
-    auto finish_next = [&]() -> int64_t {
-        const Chunk &c = ch[done++];
-        const int64_t r = finish(c);
-        if (r == JFS_OK && on_chunk) (*on_chunk)(c.s, c.e);
-        return r;
-    };
-    for (int k = 0; k < nch && rc == JFS_OK; k++) {
-        if (k >= NSLOT) rc = finish_next();
-        if (rc == JFS_OK) rc = launch(ch[k]);
-    }
-    while (done < nch && rc == JFS_OK) rc = finish_next();
-    if (rc != JFS_OK) {  // leave no copy in flight into the staging slots
+
+    // after a failure: leave no copy in flight into the staging slots
+    void drain() const {
         (void)hipStreamSynchronize(dev->s_in);
         (void)hipStreamSynchronize(ln.s_k);
         (void)hipStreamSynchronize(other.s_k);
         (void)hipStreamSynchronize(dev->s_out);
     }
+};
+
+// Run blocks [0,nblk) of iov on one device through one lane (the caller holds
+// ln.mu); returns when every result is in out[].  Blocks that the C-ABI
+// answers without a kernel (empty input, noOp) are handled by the caller.  The
+// batch is cut into chunks pipelined over the lane's NSLOT (stream, pinned,
+// HBM) slots: host copy-in of chunk k (threads) | H2D k+1, kernel k, D2H k-1
+// (streams) | host copy-out of chunk k-NSLOT.  A chunk holds at most
+// chunk_limit() staging bytes; the lane's kernels run in chunk order, so a
+// batch is not cut finer than that (a decode kernel over fewer blocks than
+// CUs lasts about one block's latency whatever its size).
+// max_chunk_blocks (> 0) also caps a chunk's block count; on_chunk (optional)
+// is called with [s, e) as soon as those blocks' results and outputs are final
+// (the coalescer releases their callers there, before later chunks finish).
+int64_t run_batch(DevCtx *dev, Lane &ln, int algo, int dir, int nblk, const jfs_iov *iov, int64_t *out,
+                  const Aead *ae = nullptr, uint32_t *crc_out = nullptr, int max_chunk_blocks = 0,
+                  const std::function<void(int, int)> *on_chunk = nullptr, uint8_t *const *csum_out = nullptr) {
+    if (nblk <= 0) return JFS_OK;
+    LaneRun scope(dev, ln, algo * 2 + dir, (uint64_t)nblk);
+    if (OpStats *st = op_stats(algo, dir)) st->batches.fetch_add(1, std::memory_order_relaxed);
+    BatchRun b(dev, ln, algo, dir, nblk, iov, out, ae, crc_out, max_chunk_blocks, csum_out);
+    b.presize();
+    const int nch = (int)b.plan.ch.size();
+    int64_t rc = JFS_OK;
+    int done = 0;  // chunks [0, done) finished
+    auto finish_next = [&]() -> int64_t {
+        const jfs_plan::Chunk &c = b.plan.ch[done];
+        const int64_t r = b.finish(done++);
+        if (r == JFS_OK && on_chunk) (*on_chunk)(c.s, c.e);
+        return r;
+    };
+    for (int k = 0; k < nch && rc == JFS_OK; k++) {
+        if (k >= NSLOT) rc = finish_next();
+        if (rc == JFS_OK) rc = b.launch(k);
+    }
+    while (done < nch && rc == JFS_OK) rc = finish_next();
+    if (rc != JFS_OK) b.drain();
     return rc;
 }
 
@@ -1925,17 +1807,7 @@ int64_t compact_run(DevCtx *dev, Lane &ln, int algo, const jfs_iov *src, const s
                     const std::vector<int> &src_map, const jfs_iov *out, const std::vector<CompactOut> &oo,
                     const int32_t *seg_first, const jfs_compact_seg *seg, int64_t *src_n, int64_t *out_n,
                     uint32_t *crc) {
-    DevGuard guard;
-    (void)hipSetDevice(dev->id);
-    dev->last_use_ms = steady_ms();
-    ln.kind.store(algo * 2 + COMPRESS, std::memory_order_relaxed);
-    dev->batches.fetch_add(1, std::memory_order_relaxed);
-    dev->blocks.fetch_add((uint64_t)(ss.size() + oo.size()), std::memory_order_relaxed);
-    start_janitor();
-    struct Touch {
-        DevCtx *d;
-        ~Touch() { d->last_use_ms = steady_ms(); }
-    } touch{dev};
+    LaneRun scope(dev, ln, algo * 2 + COMPRESS, (uint64_t)(ss.size() + oo.size()));
     const bool codec = algo != JFS_ALGO_NONE;
     const int ns = (int)ss.size(), no = (int)oo.size();
     // staged area, mirrored pinned / HBM: [compressed sources | meta | compressed outputs]
@@ -2015,50 +1887,19 @@ int64_t compact_run(DevCtx *dev, Lane &ln, int algo, const jfs_iov *src, const s
     // the small-batch LZ4 decoder and encoder run one after the other on the
     // stream: they share slot 1's scratch, sized for both before anything is queued
     Slot &s1 = ln.slot[1];
-    const bool split_dec = algo == JFS_ALGO_LZ4 && ns > 0 && ns <= split_max();
-    const bool fast_enc = algo == JFS_ALGO_LZ4 && no > 0 && lz4_fast_mode();
-    const bool seg_enc = algo == JFS_ALGO_LZ4 && no > 0 && !fast_enc && no <= eseg_max();
+    const bool lz4 = algo == JFS_ALGO_LZ4, fast = lz4_fast_mode();
     {
         int64_t need = 0;
-        if (split_dec) {
-            std::vector<int32_t> lens(ns), caps(ns);
-            for (int k = 0; k < ns; k++) {
-                lens[k] = h_sdesc[k].src_len;
-                caps[k] = h_sdesc[k].dst_cap;
-            }
-            need = jfs_lz4_split_scratch_bytes(ns, lens.data(), caps.data());
-        }
-        if (seg_enc) {
-            std::vector<int32_t> lens(no);
-            for (int k = 0; k < no; k++) lens[k] = h_enc[k].src_len;
-            need = std::max(need, jfs_lz4_eseg_scratch_bytes(no, lens.data()));
-        }
-        if (fast_enc) {
-            std::vector<int32_t> lens(no);
-            for (int k = 0; k < no; k++) lens[k] = h_enc[k].src_len;
-            need = std::max(need, jfs_lz4_fast_scratch_bytes(no, lens.data()));
-        }
+        if (lz4 && ns > 0) need = lz4_decode_scratch(ns, desc_lens(h_sdesc, ns).data(), desc_caps(h_sdesc, ns).data());
+        if (lz4 && no > 0) need = std::max(need, lz4_encode_scratch(no, desc_lens(h_enc, no).data(), fast));
         if (need > 0 && !s1.ensure_split(need)) return JFS_ERR_NO_MEMORY;
     }
     hipStream_t ks = ln.s_k;
     // one H2D: compressed sources, the plan and the preset result arrays
     if (hipMemcpyAsync(d, h, (size_t)o_ret, hipMemcpyHostToDevice, ks) != hipSuccess) return JFS_ERR_HIP;
     int lk = 0;
-    if (algo == JFS_ALGO_LZ4 && ns > 0) {
-        if (split_dec) {
-            std::vector<int32_t> lens(ns), caps(ns);
-            int64_t nsg = 0, max_cap = 0, norg = 0;
-            for (int k = 0; k < ns; k++) {
-                lens[k] = h_sdesc[k].src_len;
-                caps[k] = h_sdesc[k].dst_cap;
-                nsg += (std::max(lens[k], 0) + JFS_LZ4_SPLIT_SEG - 1) / JFS_LZ4_SPLIT_SEG;
-                max_cap = std::max<int64_t>(max_cap, caps[k]);
-                norg += (std::max<int64_t>(caps[k], 0) + 3) & ~3ll;
-            }
-            lk = jfs_launch_lz4_split(d_sdesc, ns, d_srcn, s1.sp, nsg, max_cap, norg, ks);
-        } else {
-            lk = jfs_launch_lz4_decode(d_sdesc, ns, d_srcn, ks);
-        }
+    if (lz4 && ns > 0) {
+        lk = launch_lz4_decode(s1, h_sdesc, d_sdesc, ns, d_srcn, ks) == JFS_OK ? 0 : -1;
     } else if (algo == JFS_ALGO_ZSTD && ns > 0) {
         lk = jfs_launch_zstd_decode(d_sdesc, ns, d_srcn, nullptr, ks);  // plans its own scratch
     }
@@ -2066,17 +1907,8 @@ int64_t compact_run(DevCtx *dev, Lane &ln, int algo, const jfs_iov *src, const s
     const jfs_compact_seg *d_seg = (const jfs_compact_seg *)(d + o_seg);
     if (lk == 0) lk = jfs_launch_gather(d_sdesc, d_srcn, ns + 1, d_plan, no, d_seg, max_total, d_ret, 0, ks);
     if (lk == 0 && codec && no > 0) {
-        if (fast_enc) {
-            std::vector<int32_t> lens(no);
-            for (int k = 0; k < no; k++) lens[k] = h_enc[k].src_len;
-            lk = jfs_launch_lz4_fast(d_enc, no, lens.data(), d_ret, s1.sp, s1.sp_cap, ks);
-        } else if (seg_enc) {
-            std::vector<int32_t> lens(no);
-            for (int k = 0; k < no; k++) lens[k] = h_enc[k].src_len;
-            lk = jfs_launch_lz4_encode_seg(d_enc, no, lens.data(), d_ret, s1.sp, s1.sp_cap, ks);
-        } else {
-            lk = launch_kernel(algo, COMPRESS, d_enc, no, d_ret, ks);
-        }
+        lk = lz4 ? (launch_lz4_encode(s1, h_enc, d_enc, no, d_ret, ks, fast) == JFS_OK ? 0 : -1)
+                 : launch_kernel(algo, COMPRESS, d_enc, no, d_ret, ks);
         // the encoder ran on every block: a failed gather's verdict replaces its result
         if (lk == 0) lk = jfs_launch_gather(d_sdesc, d_srcn, ns + 1, d_plan, no, d_seg, max_total, d_ret, 1, ks);
     }
@@ -2117,6 +1949,42 @@ int64_t compact_run(DevCtx *dev, Lane &ln, int algo, const jfs_iov *src, const s
 }
 
 std::atomic<unsigned> g_compact_turn{0};
+
+// Small-batch device launches: per-device scratch shared by every caller,
+// ordered across streams by an event (like the Zstd device decoder's).
+struct SplitScratch {
+    std::mutex mu;
+    uint8_t *p = nullptr;
+    int64_t cap = 0;
+    hipEvent_t ev_done = nullptr;
+};
+SplitScratch g_split[64], g_eseg_scr[64], g_fast_scr[64];
+
+// One LZ4 small-batch launch (nblk > 0) on the caller's stream with `need`
+// bytes of the current device's scratch in `tab`: launch(scratch, cap, stream)
+template <class Launch>
+int64_t scratch_launch(SplitScratch *tab, int dir, int nblk, int64_t need, void *stream, Launch launch) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return JFS_ERR_HIP;
+    stat_launch(JFS_ALGO_LZ4, dir, nblk);
+    SplitScratch &z = tab[dev];
+    std::lock_guard<std::mutex> lk(z.mu);
+    if (!z.ev_done && hipEventCreateWithFlags(&z.ev_done, hipEventDisableTiming) != hipSuccess) return JFS_ERR_HIP;
+    if (need > z.cap) {
+        if (hipEventSynchronize(z.ev_done) != hipSuccess) return JFS_ERR_HIP;  // earlier launches may still use it
+        if (z.p) (void)hipFree(z.p);
+        z.p = nullptr;
+        z.cap = 0;
+        int64_t want = 64ll << 20;
+        while (want < need) want <<= 1;
+        if (hipMalloc((void **)&z.p, (size_t)want) != hipSuccess) return JFS_ERR_NO_MEMORY;
+        z.cap = want;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (hipStreamWaitEvent(st, z.ev_done, 0) != hipSuccess) return JFS_ERR_HIP;
+    if (launch(z.p, z.cap, st) != 0) return JFS_ERR_HIP;
+    return hipEventRecord(z.ev_done, st) == hipSuccess ? JFS_OK : JFS_ERR_HIP;
+}
 
 }  // namespace
 
@@ -2183,12 +2051,7 @@ static int64_t batch_call(int algo, int dir, int nblk, const jfs_iov *iov, int64
                           uint32_t *crc = nullptr, uint8_t *const *csum = nullptr) {
     const int64_t t0 = steady_ns();
     const int64_t r = batch_common(algo, dir, nblk, iov, out_n, device_mask, crc, csum);
-    if (OpStats *st = op_stats(algo, dir)) {
-        st->calls.fetch_add(1, std::memory_order_relaxed);
-        if (r == JFS_OK)
-            for (int i = 0; i < nblk; i++) stat_block(st, iov[i].src_len, out_n[i]);
-        st->nanos.fetch_add((uint64_t)(steady_ns() - t0), std::memory_order_relaxed);
-    }
+    stat_call(algo, dir, r, nblk, iov, out_n, t0);
     return r;
 }
 
@@ -2247,12 +2110,7 @@ int64_t jfs_compress_seal_batch(int algo, int cipher, int nblk, const jfs_iov *i
         Aead ae{cipher, true, orig.data(), key.data(), nonce.data(), sp.data(), hdr.data()};
         rc = deal(algo, COMPRESS, todo, iov2, out_n, device_mask, &ae, crc);
     }
-    if (OpStats *st = op_stats(algo, COMPRESS)) {
-        st->calls.fetch_add(1, std::memory_order_relaxed);
-        if (rc == JFS_OK)
-            for (int i = 0; i < nblk; i++) stat_block(st, iov[i].src_len, out_n[i]);
-        st->nanos.fetch_add((uint64_t)(steady_ns() - t0), std::memory_order_relaxed);
-    }
+    stat_call(algo, COMPRESS, rc, nblk, iov, out_n, t0);
     return rc;
 }
 
@@ -2313,12 +2171,7 @@ int64_t jfs_open_decompress_batch(int algo, int cipher, int nblk, const jfs_iov 
         Aead ae{cipher, false, orig.data(), key.data(), nonce.data(), nullptr, nullptr};
         rc = deal(algo, DECOMPRESS, todo, iov2, out_n, device_mask, &ae);
     }
-    if (OpStats *st = op_stats(algo, DECOMPRESS)) {
-        st->calls.fetch_add(1, std::memory_order_relaxed);
-        if (rc == JFS_OK)
-            for (int i = 0; i < nblk; i++) stat_block(st, iov[i].src_len, out_n[i]);
-        st->nanos.fetch_add((uint64_t)(steady_ns() - t0), std::memory_order_relaxed);
-    }
+    stat_call(algo, DECOMPRESS, rc, nblk, iov, out_n, t0);
     return rc;
 }
 
@@ -2477,108 +2330,38 @@ int64_t jfs_lz4_decompress_device(const jfs_dev_block *d_blocks, int nblk, int32
     return jfs_launch_lz4_decode(d_blocks, nblk, d_ret, (hipStream_t)stream) == 0 ? JFS_OK : JFS_ERR_HIP;
 }
 
-// Small-batch device decode: per-device scratch shared by every caller,
-// ordered across streams by an event (like the Zstd device decoder's).
-struct SplitScratch {
-    std::mutex mu;
-    uint8_t *p = nullptr;
-    int64_t cap = 0;
-    hipEvent_t ev_done = nullptr;
-};
-SplitScratch g_split[64];
-
 int64_t jfs_lz4_decompress_device_small(const jfs_dev_block *d_blocks, const int32_t *src_len, const int32_t *dst_cap,
                                         int nblk, int32_t *d_ret, void *stream) {
     if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
     if (nblk < 0 || (nblk > 0 && (!src_len || !dst_cap))) return JFS_ERR_INVALID;
     if (nblk == 0) return JFS_OK;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return JFS_ERR_HIP;
-    stat_launch(JFS_ALGO_LZ4, DECOMPRESS, nblk);
-    int64_t nseg = 0, max_cap = 0, norg = 0;
-    for (int k = 0; k < nblk; k++) {
-        nseg += (std::max(src_len[k], 0) + JFS_LZ4_SPLIT_SEG - 1) / JFS_LZ4_SPLIT_SEG;
-        max_cap = std::max<int64_t>(max_cap, dst_cap[k]);
-        norg += (std::max<int64_t>(dst_cap[k], 0) + 3) & ~3ll;
-    }
-    const int64_t need = jfs_lz4_split_scratch_bytes(nblk, src_len, dst_cap);
-    SplitScratch &z = g_split[dev];
-    std::lock_guard<std::mutex> lk(z.mu);
-    if (!z.ev_done && hipEventCreateWithFlags(&z.ev_done, hipEventDisableTiming) != hipSuccess) return JFS_ERR_HIP;
-    if (need > z.cap) {
-        if (hipEventSynchronize(z.ev_done) != hipSuccess) return JFS_ERR_HIP;  // earlier launches may still use it
-        if (z.p) (void)hipFree(z.p);
-        z.p = nullptr;
-        z.cap = 0;
-        int64_t want = 64ll << 20;
-        while (want < need) want <<= 1;
-        if (hipMalloc((void **)&z.p, (size_t)want) != hipSuccess) return JFS_ERR_NO_MEMORY;
-        z.cap = want;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (hipStreamWaitEvent(st, z.ev_done, 0) != hipSuccess) return JFS_ERR_HIP;
-    if (jfs_launch_lz4_split(d_blocks, nblk, d_ret, z.p, nseg, max_cap, norg, st) != 0) return JFS_ERR_HIP;
-    return hipEventRecord(z.ev_done, st) == hipSuccess ? JFS_OK : JFS_ERR_HIP;
+    const jfs_plan::Lz4SplitGeom g = jfs_plan::lz4_split_geom(nblk, src_len, dst_cap);
+    return scratch_launch(g_split, DECOMPRESS, nblk, jfs_lz4_split_scratch_bytes(nblk, src_len, dst_cap), stream,
+                          [&](uint8_t *p, int64_t, hipStream_t st) {
+                              return jfs_launch_lz4_split(d_blocks, nblk, d_ret, p, g.nseg, g.max_cap, g.norg, st);
+                          });
 }
-
-SplitScratch g_eseg_scr[64];
 
 int64_t jfs_lz4_compress_device_small(const jfs_dev_block *d_blocks, const int32_t *src_len, int nblk, int32_t *d_ret,
                                       void *stream) {
     if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
     if (nblk < 0 || (nblk > 0 && !src_len)) return JFS_ERR_INVALID;
     if (nblk == 0) return JFS_OK;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return JFS_ERR_HIP;
-    stat_launch(JFS_ALGO_LZ4, COMPRESS, nblk);
-    const int64_t need = jfs_lz4_eseg_scratch_bytes(nblk, src_len);
-    SplitScratch &z = g_eseg_scr[dev];
-    std::lock_guard<std::mutex> lk(z.mu);
-    if (!z.ev_done && hipEventCreateWithFlags(&z.ev_done, hipEventDisableTiming) != hipSuccess) return JFS_ERR_HIP;
-    if (need > z.cap) {
-        if (hipEventSynchronize(z.ev_done) != hipSuccess) return JFS_ERR_HIP;
-        if (z.p) (void)hipFree(z.p);
-        z.p = nullptr;
-        z.cap = 0;
-        int64_t want = 64ll << 20;
-        while (want < need) want <<= 1;
-        if (hipMalloc((void **)&z.p, (size_t)want) != hipSuccess) return JFS_ERR_NO_MEMORY;
-        z.cap = want;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (hipStreamWaitEvent(st, z.ev_done, 0) != hipSuccess) return JFS_ERR_HIP;
-    if (jfs_launch_lz4_encode_seg(d_blocks, nblk, src_len, d_ret, z.p, z.cap, st) != 0) return JFS_ERR_HIP;
-    return hipEventRecord(z.ev_done, st) == hipSuccess ? JFS_OK : JFS_ERR_HIP;
+    return scratch_launch(g_eseg_scr, COMPRESS, nblk, jfs_lz4_eseg_scratch_bytes(nblk, src_len), stream,
+                          [&](uint8_t *p, int64_t cap, hipStream_t st) {
+                              return jfs_launch_lz4_encode_seg(d_blocks, nblk, src_len, d_ret, p, cap, st);
+                          });
 }
-
-SplitScratch g_fast_scr[64];
 
 int64_t jfs_lz4_compress_fast_device(const jfs_dev_block *d_blocks, const int32_t *src_len, int nblk, int32_t *d_ret,
                                      void *stream) {
     if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
     if (nblk < 0 || (nblk > 0 && !src_len)) return JFS_ERR_INVALID;
     if (nblk == 0) return JFS_OK;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return JFS_ERR_HIP;
-    stat_launch(JFS_ALGO_LZ4, COMPRESS, nblk);
-    const int64_t need = jfs_lz4_fast_scratch_bytes(nblk, src_len);
-    SplitScratch &z = g_fast_scr[dev];
-    std::lock_guard<std::mutex> lk(z.mu);
-    if (!z.ev_done && hipEventCreateWithFlags(&z.ev_done, hipEventDisableTiming) != hipSuccess) return JFS_ERR_HIP;
-    if (need > z.cap) {
-        if (hipEventSynchronize(z.ev_done) != hipSuccess) return JFS_ERR_HIP;
-        if (z.p) (void)hipFree(z.p);
-        z.p = nullptr;
-        z.cap = 0;
-        int64_t want = 64ll << 20;
-        while (want < need) want <<= 1;
-        if (hipMalloc((void **)&z.p, (size_t)want) != hipSuccess) return JFS_ERR_NO_MEMORY;
-        z.cap = want;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (hipStreamWaitEvent(st, z.ev_done, 0) != hipSuccess) return JFS_ERR_HIP;
-    if (jfs_launch_lz4_fast(d_blocks, nblk, src_len, d_ret, z.p, z.cap, st) != 0) return JFS_ERR_HIP;
-    return hipEventRecord(z.ev_done, st) == hipSuccess ? JFS_OK : JFS_ERR_HIP;
+    return scratch_launch(g_fast_scr, COMPRESS, nblk, jfs_lz4_fast_scratch_bytes(nblk, src_len), stream,
+                          [&](uint8_t *p, int64_t cap, hipStream_t st) {
+                              return jfs_launch_lz4_fast(d_blocks, nblk, src_len, d_ret, p, cap, st);
+                          });
 }
 
 int jfs_lz4_parse_mode(void) { return lz4_parse().load(std::memory_order_relaxed); }
