@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "jfs_internal.h"
+#include "lz4_put16.h"
 #include "wave.cuh"
 
 namespace jfs {
@@ -147,18 +148,19 @@ __device__ __forceinline__ uint32_t slot(const Ctx &c, int32_t pos) { return (ui
 
 // Far-match source bytes: the 6 dwords from the dword holding HBM address a.
 // A dword that lies wholly below dst's first dword holds no source byte (only
-// bytes the write mask drops) and is not read: it reads as 0.
+// bytes the write mask drops) and is not read: it reads as 0.  UNDER: some
+// lane's a may lie there (only a match's first load, source position < 4: the
+// caller decides once per batch); otherwise no lane's does and nothing is clamped.
+template <bool UNDER>
 __device__ __forceinline__ void far_load(const Ctx &c, uintptr_t a, uint32_t &d0, uint32_t &d1, uint32_t &d2,
                                          uint32_t &d3, uint32_t &d4, uint32_t &d5) {
     const uintptr_t b = a & ~(uintptr_t)3, lo = (uintptr_t)c.dst & ~(uintptr_t)3;
-    const bool under = b < lo;
+    const bool under = UNDER && b < lo;
     const gc_x4 *q = (const gc_x4 *)(under ? lo : b);
     const u32x4 v = q[0];
     const u32x2 w = *(const gc_x2 *)(q + 1);
     d0 = v.x; d1 = v.y; d2 = v.z; d3 = v.w; d4 = w.x; d5 = w.y;
-    if (__ballot(under)) {
-        if (under) { d5 = d4; d4 = d3; d3 = d2; d2 = d1; d1 = d0; d0 = 0; }
-    }
+    if (under) { d5 = d4; d4 = d3; d3 = d2; d2 = d1; d1 = d0; d0 = 0; }
 }
 
 // ---------------------------------------------------------------------------
@@ -601,65 +603,98 @@ __device__ __forceinline__ void lds_or(uint8_t *ring, uint32_t a, uint32_t v) { 
     __hip_atomic_fetch_or(reinterpret_cast<uint32_t *>(ring) + (a >> 2), v, __ATOMIC_RELAXED,
                           __HIP_MEMORY_SCOPE_WORKGROUP);
 }
+__device__ __forceinline__ void lds_or_at(uint32_t *p, uint32_t v) {
+    __hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
 
 // Write bytes [ha, ha + m) (1 <= m <= 16, ha = da & 3) of the 20-byte span
 // whose dwords are w0..w4 to the ring at slot da (dword 0 at da & ~3).
 // The batch's output span is zeroed before it is produced, so every lane ORs
 // its bytes in with whole-dword LDS atomics: lanes sharing a boundary dword
 // cannot clobber each other, and no byte stores or branches are needed.
+// WRAP = false: the caller knows (da & ~3) + 20 <= R for every lane, so the
+// five ORs share one address register (immediate offsets 0..16).
+template <bool WRAP>
 __device__ __forceinline__ void put16(Smem &s, uint32_t da, int32_t m, uint32_t w0, uint32_t w1, uint32_t w2,
                                       uint32_t w3, uint32_t w4) {
     uint8_t *ring = s.ring;
-    const int32_t ha = (int32_t)(da & 3u), e8 = 8 * (ha + m);  // byte span [ha, ha + m) of the 20 bytes, in bits
-    const uint32_t D0 = da & ~3u;
-    // lomask(k) = high half of 0x00000000FFFFFFFF << 8k (k clamped to [0, 4])
-    auto lm = [](int32_t b) -> uint32_t {
-        const uint32_t sh = (uint32_t)(b < 0 ? 0 : b > 32 ? 32 : b);
-        return (uint32_t)((0xFFFFFFFFull << sh) >> 32);
-    };
-    lds_or(ring, D0, w0 & lm(e8) & ~lm(8 * ha));
-    lds_or(ring, (D0 + 4) & RMASK, w1 & lm(e8 - 32));
-    lds_or(ring, (D0 + 8) & RMASK, w2 & lm(e8 - 64));
-    lds_or(ring, (D0 + 12) & RMASK, w3 & lm(e8 - 96));
-    lds_or(ring, (D0 + 16) & RMASK, w4 & lm(e8 - 128));
+    const Put16Masks k = put16_masks(da & 3u, (uint32_t)m);
+    if constexpr (WRAP) {
+        const uint32_t D0 = da & ~3u;
+        lds_or(ring, D0, w0 & k.k[0]);
+        lds_or(ring, (D0 + 4) & RMASK, w1 & k.k[1]);
+        lds_or(ring, (D0 + 8) & RMASK, w2 & k.k[2]);
+        lds_or(ring, (D0 + 12) & RMASK, w3 & k.k[3]);
+        lds_or(ring, (D0 + 16) & RMASK, w4 & k.k[4]);
+    } else {
+        uint32_t *p = reinterpret_cast<uint32_t *>(ring) + (da >> 2);  // constant element offsets: one address
+        lds_or_at(p, w0 & k.k[0]);
+        lds_or_at(p + 1, w1 & k.k[1]);
+        lds_or_at(p + 2, w2 & k.k[2]);
+        lds_or_at(p + 3, w3 & k.k[3]);
+        lds_or_at(p + 4, w4 & k.k[4]);
+    }
 }
 
 // Zero ring bytes of output [O0, O1) (bytes below O0 in the first dword are kept).
+// WRAP = false: slot(O0) + (O1 - O0) + 4 <= R.
+template <bool WRAP>
 __device__ __forceinline__ void zero_span(Smem &s, const Ctx &c, int32_t O0, int32_t O1) {
     const int l = lane_id();
     const uint32_t a = slot(c, O0), h = a & 3u;
-    const int32_t A = O0 + (int32_t)((4u - h) & 3u);  // first dword-aligned position >= O0
     if (l == 0 && h)
         __hip_atomic_fetch_and(reinterpret_cast<uint32_t *>(s.ring) + (a >> 2), lomask((int32_t)h), __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_WORKGROUP);
-    for (int32_t x = A + 4 * l; x < O1; x += 256) *(uint32_t *)(s.ring + slot(c, x)) = 0u;
+    if constexpr (WRAP) {
+        const int32_t A = O0 + (int32_t)((4u - h) & 3u);  // first dword-aligned position >= O0
+        for (int32_t x = A + 4 * l; x < O1; x += 256) *(uint32_t *)(s.ring + slot(c, x)) = 0u;
+    } else {
+        const uint32_t e = a + (uint32_t)(O1 - O0);
+        for (uint32_t x = ((a + 3u) & ~3u) + 4u * (uint32_t)l; x < e; x += 256) *(uint32_t *)(s.ring + x) = 0u;
+    }
 }
 
 // Copy m (1..16) bytes from LDS source byte address sa to ring slot da.
-// RING: sa is a ring slot (dword reads wrap); else an offset into Smem.
-template <bool RING>
+// RING: sa is a ring slot (dword reads wrap, decided for the whole wave: the
+// six reads of a lane cross the ring's end for few sources); else an offset
+// into Smem.  WRAP: as for put16 (the destination side).
+template <bool RING, bool WRAP>
 __device__ __forceinline__ void copy16(Smem &s, uint32_t sa, uint32_t da, int32_t m) {
     const uint8_t *lds = (const uint8_t *)&s;
     const uint32_t ha = da & 3u;
-    const uint32_t sb = sa - ha, S0 = sb & ~3u, sh = sb & 3u;
+    const uint32_t sb = RING ? (sa - ha) & RMASK : sa - ha, S0 = sb & ~3u, sh = sb & 3u;
     uint32_t r[6];
+    if (RING && __ballot(S0 > (uint32_t)(R - 24))) {
 #pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        const uint32_t a = RING ? ((S0 + 4 * j) & RMASK) : (S0 + 4 * j);
-        r[j] = *(const uint32_t *)(lds + a);
+        for (int j = 0; j < 6; ++j) r[j] = *(const uint32_t *)(lds + ((S0 + 4 * j) & RMASK));
+    } else {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) r[j] = *(const uint32_t *)(lds + S0 + 4 * j);
     }
-    put16(s, da, m, __builtin_amdgcn_alignbyte(r[1], r[0], sh), __builtin_amdgcn_alignbyte(r[2], r[1], sh),
-          __builtin_amdgcn_alignbyte(r[3], r[2], sh), __builtin_amdgcn_alignbyte(r[4], r[3], sh),
-          __builtin_amdgcn_alignbyte(r[5], r[4], sh));
+    put16<WRAP>(s, da, m, __builtin_amdgcn_alignbyte(r[1], r[0], sh), __builtin_amdgcn_alignbyte(r[2], r[1], sh),
+                __builtin_amdgcn_alignbyte(r[3], r[2], sh), __builtin_amdgcn_alignbyte(r[4], r[3], sh),
+                __builtin_amdgcn_alignbyte(r[5], r[4], sh));
 }
 
 
 // Whole-wave copy of len bytes to output op from output op - D (all inside the
 // ring), in chunks of at most D bytes so that self-overlapping matches repeat
 // their period; plain byte stores (the bytes are not written by anyone else).
+// WRAP = false: the destination does not cross the ring's end; when the source
+// does not either (a scalar test per match) both slots are computed once and
+// stepped by an add.
+template <bool WRAP>
 __device__ __forceinline__ void wave_near(Smem &s, const Ctx &c, int32_t op, int32_t D, int32_t len) {
     const int l = lane_id();
     const int32_t step = D < 64 ? D : 64;
+    const uint32_t ss = slot(c, op - D);
+    if (!WRAP && ss + (uint32_t)len <= (uint32_t)R) {
+        const int32_t back = (int32_t)ss - (int32_t)slot(c, op);
+        uint8_t *d = s.ring + slot(c, op) + l;
+        for (int32_t left = len; left > 0; left -= step, d += step)
+            if (l < (left < step ? left : step)) d[0] = d[back];
+        return;
+    }
     for (int32_t k = 0; k < len; k += step) {
         const int32_t i = k + l;
         if (l < step && i < len) s.ring[slot(c, op + i)] = s.ring[slot(c, op + i - D)];
@@ -676,15 +711,26 @@ __device__ __forceinline__ void wave_lit(Smem &s, const Ctx &c, int32_t op, uint
 
 // One lane-parallel batch: lanes with act hold consecutive tokens producing
 // output [O0, O1), O1 - O0 <= BSPAN, every ll/ml <= LMAX.
+// WRAP = false: slot(O0) + (O1 - O0) + 20 <= R, i.e. no ring write of the
+// batch (the 20-byte reach of its last put16 included) crosses the ring's end:
+// destination slots need no mask.
+template <bool WRAP>
 __device__ __forceinline__ void batch(Smem &s, Ctx &c, bool act, int32_t o, uint32_t ll, uint32_t ml, uint32_t off,
                                       uint32_t litr, int32_t O0, int32_t O1 PROF_ARG) {
     // sources below hz come from HBM: the ring slots of [hz, O1) are intact
     // (zero_span may clear up to 3 bytes past O1, i.e. the slots of O1 - R ..)
     const int32_t hz = O1 + 4 - R;
+    // o is opaque here: slots and masks derived from it are computed in the
+    // batch that uses them, not hoisted for both variants out of the caller's
+    // batch loop (which runs once or twice) at the price of VGPR spills
+    asm volatile("" : "+v"(o));
     PCOUNT(14, 1);
     if (O0 - c.F >= FLUSH_T) flush_to_line(s, c, O0);
-    if constexpr (!(DIAG & D_SKIP_ZERO)) zero_span(s, c, O0, O1);
+    if constexpr (!(DIAG & D_SKIP_ZERO)) zero_span<WRAP>(s, c, O0, O1);
     const int32_t ms = o + (int32_t)ll, msrc = ms - (int32_t)off;
+    // destination slot of an output position in [O0, O1): one add when the span does not wrap
+    const uint32_t sbias = c.dmis - (((uint32_t)O0 + c.dmis) & ~(uint32_t)RMASK);
+    auto dslot = [&](int32_t pos) -> uint32_t { return WRAP ? slot(c, pos) : (uint32_t)pos + sbias; };
     const bool hasm = act && ml > 0;
     const bool zero = hasm && off == 0;
     const bool far = hasm && off != 0 && msrc < hz;
@@ -699,14 +745,19 @@ __device__ __forceinline__ void batch(Smem &s, Ctx &c, bool act, int32_t o, uint
     uint32_t fd0 = 0, fd1 = 0, fd2 = 0, fd3 = 0, fd4 = 0, fd5 = 0;
     const uint32_t fha = slot(c, ms) & 3u;
     if (__ballot(far)) {
-        if (far) far_load(c, (uintptr_t)(c.dst + msrc) - fha, fd0, fd1, fd2, fd3, fd4, fd5);
+        // a first load can start below dst's first dword only from a source position < 4
+        if (__ballot(far && msrc < 4)) {
+            if (far) far_load<true>(c, (uintptr_t)(c.dst + msrc) - fha, fd0, fd1, fd2, fd3, fd4, fd5);
+        } else {
+            if (far) far_load<false>(c, (uintptr_t)(c.dst + msrc) - fha, fd0, fd1, fd2, fd3, fd4, fd5);
+        }
     }
     // literal runs (source: staged window, addressed as ring + R + litr)
     for (uint32_t k = 0; !(DIAG & D_SKIP_LIT) && __ballot(act && k < ll); k += 16) {
         PCOUNT(16, 1);
         if (act && k < ll) {
             const int32_t m = ll - k < 16u ? (int32_t)(ll - k) : 16;
-            copy16<false>(s, c.cwoff + litr + k, slot(c, o + (int32_t)k), m);
+            copy16<false, WRAP>(s, c.cwoff + litr + k, dslot(o + (int32_t)k), m);
         }
     }
     PSTAMP(4);
@@ -716,15 +767,17 @@ __device__ __forceinline__ void batch(Smem &s, Ctx &c, bool act, int32_t o, uint
             PCOUNT(17, 1);
             if (far && k < ml) {
                 const int32_t m = ml - k < 16u ? (int32_t)(ml - k) : 16;
-                const uint32_t da = slot(c, ms + (int32_t)k);  // da & 3 == fha
+                const uint32_t da = dslot(ms + (int32_t)k);  // da & 3 == fha
                 const uint32_t sh = (uint32_t)((uintptr_t)(c.dst + msrc + (int32_t)k) - fha) & 3u;
-                put16(s, da, m, __builtin_amdgcn_alignbyte(fd1, fd0, sh), __builtin_amdgcn_alignbyte(fd2, fd1, sh),
-                      __builtin_amdgcn_alignbyte(fd3, fd2, sh), __builtin_amdgcn_alignbyte(fd4, fd3, sh),
-                      __builtin_amdgcn_alignbyte(fd5, fd4, sh));
+                put16<WRAP>(s, da, m, __builtin_amdgcn_alignbyte(fd1, fd0, sh),
+                            __builtin_amdgcn_alignbyte(fd2, fd1, sh), __builtin_amdgcn_alignbyte(fd3, fd2, sh),
+                            __builtin_amdgcn_alignbyte(fd4, fd3, sh), __builtin_amdgcn_alignbyte(fd5, fd4, sh));
             }
             const bool more = far && k + 16 < ml;
             if (__ballot(more)) {
-                if (more) far_load(c, (uintptr_t)(c.dst + msrc + (int32_t)k + 16) - fha, fd0, fd1, fd2, fd3, fd4, fd5);
+                // later loads lie above the first: never below dst
+                if (more)
+                    far_load<false>(c, (uintptr_t)(c.dst + msrc + (int32_t)k + 16) - fha, fd0, fd1, fd2, fd3, fd4, fd5);
             }
         }
     }
@@ -778,7 +831,7 @@ __device__ __forceinline__ void batch(Smem &s, Ctx &c, bool act, int32_t o, uint
             PCOUNT(15, 1);
             if (go) {
                 const int32_t m = rem < 16 ? (rem < D ? rem : D) : (D < 16 ? D : 16);
-                copy16<true>(s, slot(c, pos - D), slot(c, pos), m);
+                copy16<true, WRAP>(s, slot(c, pos - D), dslot(pos), m);
                 pos += m;
                 rem -= m;
                 if (rem <= 0) pend = false;
@@ -787,7 +840,7 @@ __device__ __forceinline__ void batch(Smem &s, Ctx &c, bool act, int32_t o, uint
         for (uint64_t pmk = __ballot(pend); pmk; pmk &= pmk - 1) {
             const int j = (int)__builtin_ctzll(pmk);
             PCOUNT(19, 1);
-            wave_near(s, c, (int32_t)readlane((uint32_t)pos, j), (int32_t)readlane((uint32_t)D, j),
+            wave_near<WRAP>(s, c, (int32_t)readlane((uint32_t)pos, j), (int32_t)readlane((uint32_t)D, j),
                       (int32_t)readlane((uint32_t)rem, j));
         }
     }
@@ -855,7 +908,13 @@ __device__ __forceinline__ uint32_t copy_tokens(Smem &s, Ctx &c, uint32_t T, int
             const bool act = (uint32_t)l >= j && (uint32_t)l < eb;
             const int32_t O1 = (int32_t)readlane((uint32_t)endo, (int)eb - 1);
             PSTAMP(3);
-            if constexpr (!(DIAG & D_NOCOPY)) batch(s, c, act, o, ll, ml, off, litr, oj, O1 PROF_PASS);
+            if constexpr (!(DIAG & D_NOCOPY)) {
+                // wrap-free ring addressing when no write of the batch reaches the ring's end
+                if (slot(c, oj) + (uint32_t)(O1 - oj) + 20u <= (uint32_t)R)
+                    batch<false>(s, c, act, o, ll, ml, off, litr, oj, O1 PROF_PASS);
+                else
+                    batch<true>(s, c, act, o, ll, ml, off, litr, oj, O1 PROF_PASS);
+            }
             j = eb;
         }
         if (bm) {
