@@ -257,6 +257,19 @@ int jfs_zstd_split_counts(uint64_t *out, int reset);
 /* Zstd frame per block; ret[i] = frame size, or -2 when dst_cap < CompressBound(src_len).
  * Synchronous with respect to `stream` (it uses per-device scratch). */
 int64_t jfs_zstd_compress_device(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, void *stream);
+/* Fast Zstd encode (throughput mode), the contract of jfs_zstd_compress_device:
+ * ret[i] = size of a valid RFC 8878 frame (one frame, content size present, no
+ * checksum) that ZSTD_decompress decodes back to src, or -2 when dst_cap <
+ * CompressBound(src_len) (no byte of that dst is written).  NOT libzstd's
+ * bytes: every 128 KiB block is cut into independent 64 KiB chunks that are
+ * parsed 64 positions at a time, and repeat-offset codes never reach outside
+ * their block, so no parse chain is longer than a chunk and nothing is parsed
+ * twice.  The bytes depend on the input bytes alone (not on the batch, the
+ * frame's index, the device or alignment); the size never exceeds
+ * jfs_compress_bound(ZSTD, n); src_len == 0 gives the exact encoder's frame.
+ * Synchronous with respect to `stream` (it uses per-device scratch).  Does not
+ * consult jfs_zstd_parse_mode. */
+int64_t jfs_zstd_compress_fast_device(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, void *stream);
 
 /* CRC-32C (Castagnoli) of device-resident blocks.
  * d_blocks[i].src / src_len: the data.  d_crc[i] (if d_crc != NULL) receives
@@ -441,6 +454,20 @@ int jfs_gpu_mode(void);
 #define JFS_LZ4_PARSE_FAST 1
 int jfs_lz4_parse_mode(void);
 int jfs_set_lz4_parse_mode(int mode);
+
+/* Zstd parse of the same HOST-buffer compress calls: JFS_ZSTD_PARSE_EXACT
+ * (default) writes ZSTD_compress(level 1)'s bytes, JFS_ZSTD_PARSE_FAST the
+ * frames of jfs_zstd_compress_fast_device -- ordinary Zstd frames to every
+ * reader, and per-block results keep their meaning.  The device-resident entry
+ * points above do what their comments say in either mode.  The initial value
+ * is read once from JFS_ZSTD_PARSE = "exact" | "fast" (case-insensitive;
+ * anything else, or unset: exact).  jfs_set_zstd_parse_mode returns the
+ * previous mode, or -1 for an unknown value (which changes nothing); it is
+ * atomic and applies to calls that start afterwards. */
+#define JFS_ZSTD_PARSE_EXACT 0
+#define JFS_ZSTD_PARSE_FAST 1
+int jfs_zstd_parse_mode(void);
+int jfs_set_zstd_parse_mode(int mode);
 
 /* Per-codec counters (the data behind cachedStore's object_request_data_bytes
  * and block-size metrics, cached_store.go:931-974).  Index algo * 2 + dir,

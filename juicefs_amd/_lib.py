@@ -40,12 +40,16 @@ EXPORTS = [
     "jfs_test_spread_locking", "jfs_compress_batch_mixed", "jfs_decompress_batch_mixed",
     "jfs_gather_device", "jfs_lz4_compact_device", "jfs_compact_batch",
     "jfs_lz4_compress_fast_device", "jfs_lz4_parse_mode", "jfs_set_lz4_parse_mode",
+    "jfs_zstd_compress_fast_device", "jfs_zstd_parse_mode", "jfs_set_zstd_parse_mode",
 ]
 # the hook include/jfs_gpucodec_lz4_fast_test.h declares (the fast LZ4 encoder's host twin)
 LZ4_FAST_TEST_EXPORTS = ["jfs_test_lz4_fast_host"]
+# the hooks include/jfs_gpucodec_zstd_fast_test.h declares (the fast Zstd parse: host twin, kernels)
+ZSTD_FAST_TEST_EXPORTS = ["jfs_test_zstd_fast_host_seqs", "jfs_test_zstd_fast_seqs_device"]
 
 MODE_OFF, MODE_AUTO, MODE_FORCE = 0, 1, 2
 LZ4_PARSE_EXACT, LZ4_PARSE_FAST = 0, 1
+ZSTD_PARSE_EXACT, ZSTD_PARSE_FAST = 0, 1
 CIPHER_AES256GCM, CIPHER_CHACHA20POLY1305, CIPHER_SM4GCM = 0, 1, 2
 STATS_N = 6  # index algo * 2 + dir (0 compress, 1 decompress)
 
@@ -111,7 +115,7 @@ def load() -> ctypes.CDLL:
         f.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(JfsIov), ctypes.POINTER(i64), u32]
         f.restype = i64
     for f in (lib.jfs_lz4_decompress_device, lib.jfs_lz4_compress_device, lib.jfs_zstd_decompress_device,
-              lib.jfs_zstd_compress_device):
+              lib.jfs_zstd_compress_device, lib.jfs_zstd_compress_fast_device):
         f.argtypes = [vp, ctypes.c_int, vp, vp]
         f.restype = i64
     lib.jfs_lz4_decompress_device_small.argtypes = [vp, vp, vp, ctypes.c_int, vp, vp]
@@ -130,6 +134,13 @@ def load() -> ctypes.CDLL:
     lib.jfs_set_lz4_parse_mode.restype = ctypes.c_int
     lib.jfs_test_lz4_fast_host.argtypes = [vp, i64, vp, i64]
     lib.jfs_test_lz4_fast_host.restype = i64
+    lib.jfs_zstd_parse_mode.argtypes = []
+    lib.jfs_zstd_parse_mode.restype = ctypes.c_int
+    lib.jfs_set_zstd_parse_mode.argtypes = [ctypes.c_int]
+    lib.jfs_set_zstd_parse_mode.restype = ctypes.c_int
+    for f in (lib.jfs_test_zstd_fast_host_seqs, lib.jfs_test_zstd_fast_seqs_device):
+        f.argtypes = [vp, i64, vp, i64, vp, vp]
+        f.restype = i64
     lib.jfs_lz4_eseg_counts.argtypes = [vp, ctypes.c_int]
     lib.jfs_lz4_eseg_counts.restype = ctypes.c_int
     lib.jfs_cipher_from_name.argtypes = [ctypes.c_char_p]

@@ -244,6 +244,56 @@ def lz4_fast_host(src) -> bytes:
     return dst.raw[:n]
 
 
+_ZSTD_PARSE = {"exact": L.ZSTD_PARSE_EXACT, "fast": L.ZSTD_PARSE_FAST}
+
+
+@contextlib.contextmanager
+def zstd_parse_mode(mode: str):
+    """Hold the Zstd parse of the host-buffer compress calls at "exact"
+    (ZSTD_compress level 1's bytes) or "fast" (jfs_zstd_compress_fast_device's
+    frames) and put the previous mode back on exit.  The mode is process-wide
+    (jfs_set_zstd_parse_mode)."""
+    if mode not in _ZSTD_PARSE:
+        raise ValueError(f"zstd parse mode {mode!r}: expected 'exact' or 'fast'")
+    lib = L.load()
+    prev = lib.jfs_set_zstd_parse_mode(_ZSTD_PARSE[mode])
+    try:
+        yield
+    finally:
+        lib.jfs_set_zstd_parse_mode(prev)
+
+
+def zstd_fast_seqs(src, device_ptr: int | None = None):
+    """The fast Zstd parse's sequence records (test infrastructure): per 128 KiB
+    block of src a (records, nl) pair, records = [(ll, ml, Offset_Value)] and
+    nl the block's literal count.  From the host twin
+    (jfs_test_zstd_fast_host_seqs), or, with device_ptr = the address of src's
+    copy in device memory, from the kernels (jfs_test_zstd_fast_seqs_device)."""
+    import numpy as np
+    lib = L.load()
+    n = len(src)
+    nb = (n + (128 << 10) - 1) // (128 << 10)
+    out = np.zeros(n // 4 + 4 * nb + 4, dtype=np.uint64)
+    ns = np.zeros(nb + 1, dtype=np.int32)
+    nl = np.zeros(nb + 1, dtype=np.int32)
+    if device_ptr is None:
+        keep = np.frombuffer(src, dtype=np.uint8) if n else np.zeros(1, dtype=np.uint8)
+        total = int(lib.jfs_test_zstd_fast_host_seqs(keep.ctypes.data, n, out.ctypes.data, len(out), ns.ctypes.data,
+                                                     nl.ctypes.data))
+    else:
+        total = int(lib.jfs_test_zstd_fast_seqs_device(device_ptr, n, out.ctypes.data, len(out), ns.ctypes.data,
+                                                       nl.ctypes.data))
+    if total < 0:
+        raise RuntimeError(f"fast Zstd parse hook failed ({total})")
+    blocks, at = [], 0
+    for k in range(nb):
+        r = out[at:at + int(ns[k])]
+        at += int(ns[k])
+        blocks.append(([(int(x) & 0x1FFFF, ((int(x) >> 17) & 0x1FFFF) + 3, int(x) >> 34) for x in r], int(nl[k])))
+    assert at == total
+    return blocks
+
+
 def compact_plan(slices, block_size: int, src_block_size: int | None = None):
     """The gather plan of pkg/vfs/compact.go:54-108 (Compact + readSlice).
 

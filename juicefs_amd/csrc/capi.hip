@@ -300,6 +300,19 @@ std::atomic<int> &lz4_parse() {
 }
 inline bool lz4_fast_mode() { return lz4_parse().load(std::memory_order_relaxed) == JFS_LZ4_PARSE_FAST; }
 
+// JFS_ZSTD_PARSE (include/jfs_gpucodec.h): exact (default) | fast
+std::atomic<int> &zstd_parse() {
+    static std::atomic<int> m{[] {
+        const char *e = getenv("JFS_ZSTD_PARSE");
+        if (!e) return JFS_ZSTD_PARSE_EXACT;
+        std::string v(e);
+        for (auto &ch : v) ch = (char)tolower((unsigned char)ch);
+        return v == "fast" ? JFS_ZSTD_PARSE_FAST : JFS_ZSTD_PARSE_EXACT;
+    }()};
+    return m;
+}
+inline int zstd_parse_now() { return zstd_parse().load(std::memory_order_relaxed); }
+
 // JFS_GPU_DEVICES: "all" (default), a comma list of ordinals, or a 0x mask
 uint64_t device_select_mask() {
     const char *e = getenv("JFS_GPU_DEVICES");
@@ -701,11 +714,13 @@ int eseg_max() {
     return v;
 }
 
-int launch_kernel(int algo, int dir, const jfs_dev_block *d_desc, int nblk, int32_t *d_ret, hipStream_t st) {
+// zparse: the Zstd parse mode of the call this launch belongs to (Zstd compress only)
+int launch_kernel(int algo, int dir, const jfs_dev_block *d_desc, int nblk, int32_t *d_ret, hipStream_t st,
+                  int zparse) {
     if (algo == JFS_ALGO_LZ4 && dir == DECOMPRESS) return jfs_launch_lz4_decode(d_desc, nblk, d_ret, st);
     if (algo == JFS_ALGO_LZ4 && dir == COMPRESS) return jfs_launch_lz4_encode(d_desc, nblk, d_ret, st);
     if (algo == JFS_ALGO_ZSTD && dir == DECOMPRESS) return jfs_launch_zstd_decode(d_desc, nblk, d_ret, nullptr, st);
-    if (algo == JFS_ALGO_ZSTD && dir == COMPRESS) return jfs_launch_zstd_encode(d_desc, nblk, d_ret, st);
+    if (algo == JFS_ALGO_ZSTD && dir == COMPRESS) return jfs_launch_zstd_encode(d_desc, nblk, d_ret, st, zparse);
     return -1;
 }
 
@@ -820,6 +835,7 @@ struct BatchRun {
     const bool zplan;                // Zstd decode: the per-input scratch plan (ZInfo) rides in the chunk
     const int64_t zib;
     const bool lz4_fast;  // the parse mode when this batch started
+    const int zparse;     // and the Zstd one
     const jfs_plan::Pieces pieces{NPIECE, byte_npiece()};
     std::vector<jfs_plan::Block> blk;  // staged input bytes and capacity per block
     jfs_plan::Plan plan;
@@ -830,7 +846,7 @@ struct BatchRun {
         : dev(dev), ln(ln), other(dev->lane[(&ln - dev->lane + 1) % NLANE]), algo(algo), dir(dir), iov(iov), out(out),
           ae(ae), crc_out(crc_out), csum_out(dir == DECOMPRESS && !ae ? csum : nullptr),
           zplan(algo == JFS_ALGO_ZSTD && dir == DECOMPRESS && !ae), zib(zplan ? (int64_t)jfs_zstd_info_bytes() : 0),
-          lz4_fast(lz4_fast_mode()), blk(nblk) {
+          lz4_fast(lz4_fast_mode()), zparse(zstd_parse_now()), blk(nblk) {
         for (int i = 0; i < nblk; i++) blk[i] = {iov[i].src_len, ae ? iov[i].dst_cap : staged_cap(algo, dir, iov[i])};
         const int64_t limit =
             (algo == JFS_ALGO_LZ4 || algo == JFS_ALGO_ZSTD) && dir == COMPRESS && !ae ? chunk_limit_lz4c()
@@ -1001,7 +1017,7 @@ struct BatchRun {
         else if (algo == JFS_ALGO_LZ4)
             r = launch_lz4_encode(sl, h_desc, d_desc, n, d_ret, ks, lz4_fast);
         else
-            r = launch_rc(launch_kernel(algo, dir, d_desc, n, d_ret, ks));
+            r = launch_rc(launch_kernel(algo, dir, d_desc, n, d_ret, ks, zparse));
         if (r != JFS_OK) return r;
         if (dir == COMPRESS && !run_crc(c, L, sl, d_ret, ks)) return JFS_ERR_HIP;
         if (!run_csum(c, L, sl, d_ret, ks)) return JFS_ERR_HIP;
@@ -1066,7 +1082,7 @@ struct BatchRun {
         int64_t r = JFS_OK;
         if (ae->seal) {
             if (algo == JFS_ALGO_LZ4) r = launch_lz4_encode(sl, h_desc, d_desc, n, d_ret, ks, lz4_fast);
-            else if (algo != JFS_ALGO_NONE) r = launch_rc(launch_kernel(algo, COMPRESS, d_desc, n, d_ret, ks));
+            else if (algo != JFS_ALGO_NONE) r = launch_rc(launch_kernel(algo, COMPRESS, d_desc, n, d_ret, ks, zparse));
             if (r == JFS_OK)
                 r = launch_rc(
                     jfs_launch_aead(ae->cipher, d_ad, n, 0, d_r2, algo != JFS_ALGO_NONE ? d_ret : nullptr, ks));
@@ -1908,7 +1924,7 @@ int64_t compact_run(DevCtx *dev, Lane &ln, int algo, const jfs_iov *src, const s
     if (lk == 0) lk = jfs_launch_gather(d_sdesc, d_srcn, ns + 1, d_plan, no, d_seg, max_total, d_ret, 0, ks);
     if (lk == 0 && codec && no > 0) {
         lk = lz4 ? (launch_lz4_encode(s1, h_enc, d_enc, no, d_ret, ks, fast) == JFS_OK ? 0 : -1)
-                 : launch_kernel(algo, COMPRESS, d_enc, no, d_ret, ks);
+                 : launch_kernel(algo, COMPRESS, d_enc, no, d_ret, ks, zstd_parse_now());
         // the encoder ran on every block: a failed gather's verdict replaces its result
         if (lk == 0) lk = jfs_launch_gather(d_sdesc, d_srcn, ns + 1, d_plan, no, d_seg, max_total, d_ret, 1, ks);
     }
@@ -2380,7 +2396,22 @@ int64_t jfs_lz4_compress_device(const jfs_dev_block *d_blocks, int nblk, int32_t
 int64_t jfs_zstd_compress_device(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, void *stream) {
     if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
     stat_launch(JFS_ALGO_ZSTD, COMPRESS, nblk);
-    return jfs_launch_zstd_encode(d_blocks, nblk, d_ret, (hipStream_t)stream) == 0 ? JFS_OK : JFS_ERR_HIP;
+    return jfs_launch_zstd_encode(d_blocks, nblk, d_ret, (hipStream_t)stream, JFS_ZSTD_PARSE_EXACT) == 0 ? JFS_OK
+                                                                                                         : JFS_ERR_HIP;
+}
+
+int64_t jfs_zstd_compress_fast_device(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, void *stream) {
+    if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
+    stat_launch(JFS_ALGO_ZSTD, COMPRESS, nblk);
+    return jfs_launch_zstd_encode(d_blocks, nblk, d_ret, (hipStream_t)stream, JFS_ZSTD_PARSE_FAST) == 0 ? JFS_OK
+                                                                                                        : JFS_ERR_HIP;
+}
+
+int jfs_zstd_parse_mode(void) { return zstd_parse_now(); }
+
+int jfs_set_zstd_parse_mode(int mode) {
+    if (mode != JFS_ZSTD_PARSE_EXACT && mode != JFS_ZSTD_PARSE_FAST) return -1;
+    return zstd_parse().exchange(mode);
 }
 
 int64_t jfs_zstd_decompress_device(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, void *stream) {

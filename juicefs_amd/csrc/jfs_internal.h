@@ -36,7 +36,9 @@ int jfs_launch_lz4_encode_seg(const jfs_dev_block *d_blocks, int nblk, const int
 int64_t jfs_lz4_fast_scratch_bytes(int nblk, const int32_t *lens);
 int jfs_launch_lz4_fast(const jfs_dev_block *d_blocks, int nblk, const int32_t *lens, int32_t *d_ret, void *scratch,
                         int64_t scratch_cap, hipStream_t stream);
-int jfs_launch_zstd_encode(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, hipStream_t stream);
+// parse_mode: JFS_ZSTD_PARSE_EXACT (libzstd's bytes) or JFS_ZSTD_PARSE_FAST (zstd_fast.hip: valid frames, not libzstd's bytes)
+int jfs_launch_zstd_encode(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, hipStream_t stream,
+                           int parse_mode);
 int jfs_launch_zstd_decode(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, uint8_t *d_scratch,
                            hipStream_t stream);
 // d_split: the small-batch path's scratch (jfs_zstd_split_bytes), or null;

@@ -80,94 +80,15 @@
 
 #include "jfs_internal.h"
 #include "wave.cuh"
+#include "zstd_l1.h"
 
 namespace jfs {
 namespace zl1 {
 
-constexpr int32_t BLK = 128 << 10;  // ZSTD_BLOCKSIZE_MAX
 #ifndef JFS_ZL1_PB
 #define JFS_ZL1_PB 64  // search iterations tried at once right after a match
 #endif
 
-// ---------------------------------------------------------------------------
-// parameters: ZSTD_getCParams(1, n, 0) (level-1 row of the size tier, then
-// ZSTD_adjustCParams_internal); strategy fast, targetLength 0 (step 2)
-// ---------------------------------------------------------------------------
-struct Params {
-    uint32_t wlog, hlog, mls;
-};
-__host__ __device__ inline uint32_t hbit(uint32_t v) { return 31u - (uint32_t)__builtin_clz(v); }
-__host__ __device__ inline Params params_of(int64_t n) {
-    Params p;
-    if (n > (256 << 10)) { p.wlog = 19; p.hlog = 14; p.mls = 7; }
-    else if (n > (128 << 10)) { p.wlog = 18; p.hlog = 14; p.mls = 6; }
-    else if (n > (16 << 10)) { p.wlog = 17; p.hlog = 13; p.mls = 6; }
-    else { p.wlog = 14; p.hlog = 15; p.mls = 5; }
-    const uint32_t t = (uint32_t)n;
-    const uint32_t srclog = t < 64 ? 6u : hbit(t - 1) + 1;
-    if (p.wlog > srclog) p.wlog = srclog;
-    if (p.hlog > p.wlog + 1) p.hlog = p.wlog + 1;
-    if (p.wlog < 10) p.wlog = 10;
-    return p;
-}
-__host__ __device__ inline int64_t zbound(int64_t n) { return n + (n >> 8) + (n < BLK ? (BLK - n) >> 11 : 0); }
-
-// per frame / per block records (host-built, device-updated)
-struct FInfo {
-    const uint8_t *src;
-    uint8_t *dst;
-    int32_t n, cap;
-    int32_t nb, b0;  // blocks, index of the first in the block array
-    uint32_t wlog, hlog, mls;
-    int32_t status;  // 0 done, 1 parse again (a confirmation guess was wrong), -2 dst too small
-};
-enum : int32_t { F_NOCOMP = 1, F_RLE = 2, F_ASSUMED = 4, F_LASTNC = 8 };
-struct BInfo {
-    int64_t seq_off;  // u64 records in the sequence scratch
-    int64_t lit_off;  // bytes: literals (bsz), then the sequences section (bsz + 512)
-    int32_t frame, bs, be;
-    int32_t ns, nl;                    // sequences, literals
-    uint32_t rin0, rin1, rout0, rout1;  // repeat offsets in / out (offset_1, offset_2)
-    int32_t flags;
-    int32_t conf;   // outcome known from an earlier pass: 0 unknown, 1 confirmed, 2 not
-    int32_t secsz;  // sequences section bytes, -1 = larger than the block
-};
-constexpr int64_t SEC_EXTRA = 512;
-__host__ __device__ inline int64_t seq_cap(int32_t bsz) { return bsz / 4 + 4; }
-
-// sequence record: ll | mlb << 17 | Offset_Value << 34
-__device__ __forceinline__ uint64_t seq_pack(uint32_t ll, uint32_t mlb, uint32_t ofv) {
-    return (uint64_t)ll | ((uint64_t)mlb << 17) | ((uint64_t)ofv << 34);
-}
-
-// ---------------------------------------------------------------------------
-// source access through a buffer resource: the descriptor covers exactly the
-// dwords that hold input bytes, so every load is range-checked by the
-// hardware (out-of-range dwords read 0, nothing past the input is touched)
-// and needs only a 32-bit offset -- no per-load guards or 64-bit address math
-// ---------------------------------------------------------------------------
-struct Src {
-    __amdgpu_buffer_rsrc_t r;
-    int32_t sh;  // input byte 0 sits at byte sh of the first dword
-};
-__device__ __forceinline__ Src make_src(const uint8_t *p, int32_t n) {
-    Src s;
-    const uintptr_t a = (uintptr_t)p;
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)(a & ~(uintptr_t)3));
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-    s.sh = (int32_t)__builtin_amdgcn_readfirstlane((uint32_t)(a & 3u));
-    const int32_t nb = n > 0 ? (int32_t)((n + s.sh + 3) & ~3) : 0;
-    s.r = __builtin_amdgcn_make_buffer_rsrc((void *)(((uintptr_t)hi << 32) | lo), 0,
-                                            (int)__builtin_amdgcn_readfirstlane((uint32_t)nb), 0x00020000);
-    return s;
-}
-__device__ __forceinline__ uint32_t ldw(const Src &S, int32_t byteoff) {
-    return __builtin_amdgcn_raw_buffer_load_b32(S.r, (uint32_t)byteoff, 0, 0);
-}
-// byte at position p
-__device__ __forceinline__ uint32_t ldb(const Src &S, int32_t p) {
-    return __builtin_amdgcn_raw_buffer_load_b8(S.r, (uint32_t)(p + S.sh), 0, 0);
-}
 // 16 bytes at position p (p >= -3; bytes before the input read 0).  A
 // negative offset must never reach a buffer instruction: the compiler merges
 // the five loads into wider ones and the whole merged load would read 0.
@@ -2372,8 +2293,14 @@ int spec_max_blocks() {
     return v;
 }
 
-extern "C" int jfs_launch_zstd_encode(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, hipStream_t stream) {
+// parse_mode: JFS_ZSTD_PARSE_EXACT, libzstd's level-1 bytes (everything below);
+// JFS_ZSTD_PARSE_FAST, the chunk-parallel parse of zstd_fast.hip in
+// front of the same entropy stage: one pass, no speculative rounds, no parse-again loop
+extern "C" int jfs_launch_zstd_encode(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, hipStream_t stream,
+                                      int parse_mode) {
     if (nblk <= 0) return 0;
+    if (parse_mode != JFS_ZSTD_PARSE_EXACT && parse_mode != JFS_ZSTD_PARSE_FAST) return -1;
+    const bool fast = parse_mode == JFS_ZSTD_PARSE_FAST;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -1;
     // a free scratch of this device (blocking on the first only if both are taken)
@@ -2442,7 +2369,7 @@ extern "C" int jfs_launch_zstd_encode(const jfs_dev_block *d_blocks, int nblk, i
     std::vector<SpecB> slots;
     std::vector<std::pair<uint32_t, std::pair<int, int>>> sgrp;  // hashLog -> (first slot, slots)
     int32_t segsz = BLK;
-    {
+    if (!fast) {
         int64_t cand = 0, fmax = 0;
         for (int f = 0; f < nblk; f++)
             if (fi[f].status == 0 && fi[f].nb >= 2 && fi[f].n >= 65536) {
@@ -2494,7 +2421,9 @@ extern "C" int jfs_launch_zstd_encode(const jfs_dev_block *d_blocks, int nblk, i
     const size_t spb = nsb ? a256(sizeof(int32_t) * (3 * (size_t)nsf + nspb + 16)) + a256(sizeof(SpecB) * nsb) +
                                  2 * a256(sizeof(uint32_t) * SPEC_TSZ * (size_t)nsb) + a256(sizeof(int32_t) * (maxseg + 3))
                            : 0;
-    if (!z.grow(fb + bb + lb + sb + yb + hb + tb + spb)) return -1;
+    // fast parse: records and trailing literals per chunk (two chunks a block)
+    const size_t cmb = fast ? a256(sizeof(int32_t) * 4 * (size_t)std::max(nbk, 1)) : 0;
+    if (!z.grow(fb + bb + lb + sb + yb + hb + tb + spb + cmb)) return -1;
     uint8_t *p = z.d;
     FInfo *d_fi = (FInfo *)p;
     p += fb;
@@ -2524,6 +2453,7 @@ extern "C" int jfs_launch_zstd_encode(const jfs_dev_block *d_blocks, int nblk, i
         p += a256(sizeof(uint32_t) * SPEC_TSZ * (size_t)nsb);
         d_any = (int32_t *)p;
     }
+    int32_t *d_cmeta = fast ? (int32_t *)p : nullptr;  // (no speculative scratch in a fast launch)
     if (hipMemcpyAsync(d_fi, fi.data(), sizeof(FInfo) * nblk, hipMemcpyHostToDevice, stream) != hipSuccess) return -1;
     if (nbk > 0 && hipMemcpyAsync(d_bi, bi.data(), sizeof(BInfo) * nbk, hipMemcpyHostToDevice, stream) != hipSuccess)
         return -1;
@@ -2534,6 +2464,34 @@ extern "C" int jfs_launch_zstd_encode(const jfs_dev_block *d_blocks, int nblk, i
     for (int f = 0; f < nblk; f++)
         if (fi[f].status < 0) hret[f] = -2;
     if (hipMemcpyAsync(d_ret, hret.data(), sizeof(int32_t) * nblk, hipMemcpyHostToDevice, stream) != hipSuccess) return -1;
+    if (fast) {
+        // every frame's blocks parse at once and take nothing from each other
+        // (zfast_seq hands on the repeat offsets it was handed, so zl1_litdec
+        // never reports status 1): parse, sequences, literals, bytes, done
+        std::vector<int32_t> lists(todo);
+        for (int f : todo)
+            for (int k = 0; k < fi[f].nb; k++) lists.push_back(fi[f].b0 + k);
+        const int nfl = (int)todo.size(), nbl = (int)lists.size() - nfl;
+        if (lists.empty()) return hipStreamSynchronize(stream) == hipSuccess ? 0 : -1;
+        if (hipMemcpyAsync(d_list, lists.data(), sizeof(int32_t) * lists.size(), hipMemcpyHostToDevice, stream) !=
+            hipSuccess)
+            return -1;
+        const int32_t *d_bl = d_list + nfl;
+        if (nbl > 0) {
+            if (launch_zfast(d_fi, d_bi, d_bl, nbl, d_seq, d_cmeta, stream) != 0) return -1;
+            hipLaunchKernelGGL(zl1_seq_kernel, dim3((unsigned)nbl), dim3(64), 0, stream, d_fi, d_bl, d_bi, d_seq,
+                               d_bytes, d_hist);
+            hipLaunchKernelGGL(zl1_lithuf_kernel, dim3((unsigned)nbl), dim3(64), 0, stream, d_fi, d_bl, d_bi, d_hist,
+                               d_lt);
+        }
+        hipLaunchKernelGGL(zl1_litdec_kernel, dim3((unsigned)nfl), dim3(64), 0, stream, d_fi, d_list, d_bi, d_hist, d_lt,
+                           d_ret);
+        if (nbl > 0)
+            hipLaunchKernelGGL(zl1_litwrite_kernel, dim3((unsigned)nbl), dim3(64), 0, stream, d_fi, d_bl, d_bi, d_bytes,
+                               d_lt);
+        if (hipGetLastError() != hipSuccess) return -1;
+        return hipStreamSynchronize(stream) == hipSuccess ? 0 : -1;
+    }
     std::vector<char> spec_f(nblk, 0);
     for (int f : sf) spec_f[f] = 1;
     for (int pass = 0; pass <= nbk + 1 && !todo.empty(); pass++) {

@@ -126,6 +126,15 @@ def zstd_compress(desc: torch.Tensor, ret: torch.Tensor, stream=None):
            "jfs_zstd_compress_device")
 
 
+def zstd_compress_fast(desc: torch.Tensor, ret: torch.Tensor, stream=None):
+    """jfs_zstd_compress_fast_device: the throughput encoder (independent 64 KiB
+    chunks, block-local repeat offsets).  Valid Zstd frames, not libzstd's
+    bytes; host-synchronous like zstd_compress."""
+    n = desc.numel() // DESC_DTYPE.itemsize
+    _check(L.load().jfs_zstd_compress_fast_device(desc.data_ptr(), n, ret.data_ptr(), _stream_ptr(stream)),
+           "jfs_zstd_compress_fast_device")
+
+
 def crc32c(desc: torch.Tensor, crc: torch.Tensor | None = None, ret: torch.Tensor | None = None,
            seg_bytes: int = 0, stream=None):
     """CRC-32C per descriptor (jfs_crc32c_device): whole-block values into
