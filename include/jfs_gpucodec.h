@@ -416,6 +416,40 @@ int64_t jfs_compact_batch(int algo, int nsrc, const jfs_iov *src, int nout, cons
                           const int32_t *seg_first /* nout+1 */, const jfs_compact_seg *seg, int64_t *src_n,
                           int64_t *out_n, uint32_t *crc /* may be NULL */, uint32_t device_mask);
 
+/* jfs_compact_batch for a volume with object encryption: every stored object
+ * is an envelope (see jfs_compress_seal_batch), so the chain is open -> decode
+ * -> gather -> encode -> seal, on one device, and only sealed bytes cross the
+ * host link.  The plan, the jfs_iov conventions, the per-block error policy,
+ * the device choice, the stats and "current device unchanged on return" are
+ * jfs_compact_batch's.
+ *   src[i].src/src_len is the whole stored envelope, src_keys[i] the data key
+ *   the caller unwrapped from its header (as for jfs_open_decompress_batch),
+ *   src[i].dst_cap the block size.  src_n[i] = exactly what
+ *   jfs_open_decompress_batch(algo, cipher, ..) returns for that envelope and
+ *   key: JFS_ERR_CORRUPT for a header jfs_envelope_parse rejects, JFS_ERR_AUTH
+ *   when the tag does not verify, else the codec's own result.
+ *   out[j].dst/dst_cap receives the whole envelope of new block j, built from
+ *   out_p[j] (data key, nonce, wrapped key).  out_n[j] = what
+ *   jfs_compress_seal_batch(algo, cipher, ..) returns for the gathered bytes
+ *   with the same out_p[j] and dst_cap, byte for byte (its answer to a dst_cap
+ *   below jfs_envelope_bound and the current JFS_LZ4_PARSE / JFS_ZSTD_PARSE
+ *   mode included), or JFS_ERR_CORRUPT when a source feeding block j failed
+ *   (a source that does not authenticate is a failed source) or is shorter
+ *   than a segment needs; this wins over the block's own error.  Nothing is
+ *   written to out[j].dst for a failed block.  crc[j] (crc may be NULL) = the
+ *   CRC-32C of the whole envelope, computed on the GPU; 0 for a failed block.
+ * A FRESH data key / nonce pair per output is the caller's duty, as on the PUT
+ * path (encrypt.go:230-243): sealing two blocks under one key and nonce breaks
+ * the AEAD; never reuse a source's.
+ * Checked on the host first (JFS_ERR_INVALID): everything jfs_compact_batch
+ * rejects, an unknown cipher, a NULL src_keys / out_p with nsrc / nout > 0, a
+ * NULL src_keys[i], a NULL out_p[j].key or nonce, wrapped_len outside
+ * 0..65535, wrapped NULL with wrapped_len > 0; then JFS_ERR_NO_DEVICE. */
+int64_t jfs_compact_seal_batch(int algo, int cipher, int nsrc, const jfs_iov *src, const uint8_t *const *src_keys,
+                               int nout, const jfs_iov *out, const jfs_seal_param *out_p,
+                               const int32_t *seg_first /* nout+1 */, const jfs_compact_seg *seg, int64_t *src_n,
+                               int64_t *out_n, uint32_t *crc /* may be NULL */, uint32_t device_mask);
+
 /* ---- Runtime / utilities ------------------------------------------------- */
 
 /* Number of usable gfx950 devices (0 when none; never an error).  Only the
@@ -440,7 +474,7 @@ int jfs_gpu_mode(void);
 
 /* LZ4 parse of the HOST-buffer compress calls (jfs_compress and its
  * coalescer, jfs_compress_batch / _crc / _mixed, jfs_compress_seal_batch, the
- * encode step of jfs_compact_batch): JFS_LZ4_PARSE_EXACT (default) writes
+ * encode step of jfs_compact_batch / jfs_compact_seal_batch): JFS_LZ4_PARSE_EXACT (default) writes
  * LZ4_compress_default's bytes, JFS_LZ4_PARSE_FAST the blocks of
  * jfs_lz4_compress_fast_device -- ordinary LZ4 blocks to every reader, and
  * per-block results keep their meaning (JFS_ERR_COMPRESS_FAIL when a block

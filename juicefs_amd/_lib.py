@@ -38,7 +38,7 @@ EXPORTS = [
     "jfs_aead_open_device", "jfs_envelope_bound", "jfs_envelope_parse", "jfs_compress_seal_batch",
     "jfs_open_decompress_batch", "jfs_compress_batch_crc", "jfs_decompress_batch_csum", "jfs_deal_plan",
     "jfs_test_spread_locking", "jfs_compress_batch_mixed", "jfs_decompress_batch_mixed",
-    "jfs_gather_device", "jfs_lz4_compact_device", "jfs_compact_batch",
+    "jfs_gather_device", "jfs_lz4_compact_device", "jfs_compact_batch", "jfs_compact_seal_batch",
     "jfs_lz4_compress_fast_device", "jfs_lz4_parse_mode", "jfs_set_lz4_parse_mode",
     "jfs_zstd_compress_fast_device", "jfs_zstd_parse_mode", "jfs_set_zstd_parse_mode",
 ]
@@ -189,6 +189,12 @@ def load() -> ctypes.CDLL:
                                       ctypes.POINTER(JfsIov), ctypes.POINTER(i32), ctypes.POINTER(JfsCompactSeg),
                                       ctypes.POINTER(i64), ctypes.POINTER(i64), vp, u32]
     lib.jfs_compact_batch.restype = i64
+    lib.jfs_compact_seal_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(JfsIov),
+                                           ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.POINTER(JfsIov),
+                                           ctypes.POINTER(JfsSealParam), ctypes.POINTER(i32),
+                                           ctypes.POINTER(JfsCompactSeg), ctypes.POINTER(i64), ctypes.POINTER(i64),
+                                           vp, u32]
+    lib.jfs_compact_seal_batch.restype = i64
     lib.jfs_release_staging.argtypes = []
     lib.jfs_release_staging.restype = None
     lib.jfs_device_count.argtypes = []

@@ -749,6 +749,23 @@ struct Aead {
     }
 };
 
+// The envelope header of one sealed block (encrypt.go:244-254:
+// be16(len(wrapped)) | len(nonce) | wrapped | nonce), host-known: its CRC-32C
+// (the seed of the payload's checksum on the device) and its bytes
+uint32_t seal_header_crc(const jfs_seal_param &p) {
+    const uint8_t h3[3] = {(uint8_t)(p.wrapped_len >> 8), (uint8_t)(p.wrapped_len & 0xFF), 12};
+    uint32_t v = host_crc32c(0, h3, 3);
+    v = host_crc32c(v, p.wrapped, p.wrapped_len);
+    return host_crc32c(v, p.nonce, 12);
+}
+void seal_header_write(uint8_t *dst, const jfs_seal_param &p) {
+    dst[0] = (uint8_t)(p.wrapped_len >> 8);
+    dst[1] = (uint8_t)(p.wrapped_len & 0xFF);
+    dst[2] = 12;
+    if (p.wrapped_len > 0) memcpy(dst + 3, p.wrapped, (size_t)p.wrapped_len);
+    memcpy(dst + 3 + p.wrapped_len, p.nonce, 12);
+}
+
 // What every run on a lane begins and ends with: the caller's device is kept
 // and the lane's selected, the device's counters and idle clock move on, the
 // staging janitor runs; the idle clock starts anew when the run ends.
@@ -913,14 +930,7 @@ struct BatchRun {
         for (int i = c.s; i < c.e; i++) {
             const int k = i - c.s;
             h_cd[k] = jfs_dev_block{Layout::at(sl.d, L.out) + plan.out_off[i], nullptr, 0, 0};
-            h_seed[k] = 0;
-            if (ae && ae->seal) {
-                const jfs_seal_param &p = ae->sp[i];
-                const uint8_t h3[3] = {(uint8_t)(p.wrapped_len >> 8), (uint8_t)(p.wrapped_len & 0xFF), 12};
-                uint32_t v = host_crc32c(0, h3, 3);
-                v = host_crc32c(v, p.wrapped, p.wrapped_len);
-                h_seed[k] = host_crc32c(v, ae->nonce[i], 12);
-            }
+            h_seed[k] = ae && ae->seal ? seal_header_crc(ae->sp[i]) : 0;
         }
         return h2d(Layout::at(sl.d, L.crc_desc), h_cd, L.crc - L.crc_desc);  // descriptors and seeds
     }
@@ -1134,12 +1144,7 @@ struct BatchRun {
                     } else if (hdr + rc + 16 > o.dst_cap) {
                         out[i] = JFS_ERR_SHORT_BUFFER;
                     } else {
-                        const jfs_seal_param &p = ae->sp[i];
-                        o.dst[0] = (uint8_t)(p.wrapped_len >> 8);
-                        o.dst[1] = (uint8_t)(p.wrapped_len & 0xFF);
-                        o.dst[2] = 12;
-                        if (p.wrapped_len > 0) memcpy(o.dst + 3, p.wrapped, (size_t)p.wrapped_len);
-                        memcpy(o.dst + 3 + p.wrapped_len, ae->nonce[i], 12);
+                        seal_header_write(o.dst, ae->sp[i]);
                         jobs.push_back({o.dst + hdr, h_out + out_off[i], rc + 16});
                         out[i] = hdr + rc + 16;
                     }
@@ -1964,6 +1969,253 @@ int64_t compact_run(DevCtx *dev, Lane &ln, int algo, const jfs_iov *src, const s
     return JFS_OK;
 }
 
+// ---------------------------------------------------------------------------
+// compaction of an encrypted volume: open -> decode -> gather -> encode -> seal
+// on one device (jfs_compact_seal_batch)
+// ---------------------------------------------------------------------------
+// One source / output the device works on, as CompactSrc / CompactOut.
+struct SealedSrc {
+    int idx;
+    int64_t off;   // sealed payload (ciphertext || tag) = src[off, off + pay)
+    int64_t noff;  // its 12-byte nonce inside the envelope header
+    int64_t pay;
+    int64_t cap;   // staged decode capacity
+};
+struct SealedOut {
+    int idx;
+    int64_t total;  // gathered bytes
+    int64_t bound;  // encoder capacity (the codec's bound of total); the payload area holds bound + 16
+    int64_t hdr;    // envelope header bytes
+};
+
+// compact_run's chain with an AEAD open in front of the decoders and a seal
+// behind the encoders, still one pass on the lane's kernel stream: payloads,
+// keys and the plan H2D, open in place, decode, the opens' verdicts merged into
+// the source lengths, gather, encode into the envelope's payload area, seal in
+// place (lengths from the encoder on the device), checksums seeded with the
+// header's, results D2H, then exactly the sealed bytes D2H; the host writes
+// the headers.  Staging as compact_run.  Per-block results follow
+// BatchRun::finish's rules for sealed batches, so they equal
+// jfs_open_decompress_batch's and jfs_compress_seal_batch's.
+int64_t compact_seal_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src,
+                         const uint8_t *const *src_keys, const std::vector<SealedSrc> &ss,
+                         const std::vector<int> &src_map, const jfs_iov *out, const jfs_seal_param *out_p,
+                         const std::vector<SealedOut> &oo, const int32_t *seg_first, const jfs_compact_seg *seg,
+                         int64_t *src_n, int64_t *out_n, uint32_t *crc) {
+    LaneRun scope(dev, ln, algo * 2 + COMPRESS, (uint64_t)(ss.size() + oo.size()));
+    const bool codec = algo != JFS_ALGO_NONE;
+    const int ns = (int)ss.size(), no = (int)oo.size();
+    const int klen = jfs_cipher_key_size(cipher);
+    // staged area, mirrored pinned / HBM: [sealed source payloads | meta | sealed output payloads]
+    // meta: compact_run's descriptors, the AEAD descriptors of both sides, one
+    // 64-byte key | nonce cell per block, the checksum seeds and the preset
+    // source lengths; then what only the device writes: the opens' results,
+    // the outputs' results (encoder / gather, seal) and the checksums
+    std::vector<int64_t> in_off(ns), out_off(no), dec_off(ns), gat_off(no);
+    int64_t tin = 0, tout = 0, scratch = 0, nseg = 0;
+    int32_t max_total = 0;
+    for (int k = 0; k < ns; k++) {
+        in_off[k] = tin;
+        tin += align16(ss[k].pay);
+        if (codec) {
+            dec_off[k] = scratch;
+            scratch += align16(ss[k].cap);
+        }
+    }
+    for (int k = 0; k < no; k++) {
+        out_off[k] = tout;
+        tout += align16(oo[k].bound + 16);
+        if (codec) {
+            gat_off[k] = scratch;
+            scratch += align16(oo[k].total);
+        }
+        nseg += seg_first[oo[k].idx + 1] - seg_first[oo[k].idx];
+        max_total = (int32_t)std::max<int64_t>(max_total, oo[k].total);
+    }
+    const int64_t blk_b = (int64_t)sizeof(jfs_dev_block), aead_b = (int64_t)sizeof(jfs_aead_block);
+    const int64_t o_sdesc = tin;
+    const int64_t o_plan = o_sdesc + align16((ns + 1) * blk_b);
+    const int64_t o_seg = o_plan + align16((int64_t)no * (int64_t)sizeof(jfs_compact_out));
+    const int64_t o_enc = o_seg + align16(nseg * (int64_t)sizeof(jfs_compact_seg));
+    const int64_t o_cd = o_enc + align16(no * blk_b);
+    const int64_t o_sad = o_cd + align16(no * blk_b);
+    const int64_t o_oad = o_sad + align16(ns * aead_b);
+    const int64_t o_kn = o_oad + align16(no * aead_b);
+    const int64_t o_seed = o_kn + 64 * (int64_t)(ns + no);
+    const int64_t o_srcn = o_seed + align16((int64_t)no * 4);
+    const int64_t o_open = o_srcn + align16((int64_t)(ns + 1) * 4);
+    const int64_t o_ret = o_open + align16((int64_t)ns * 4);
+    const int64_t o_r2 = o_ret + align16((int64_t)no * 4);
+    const int64_t o_crc = o_r2 + align16((int64_t)no * 4);
+    const int64_t o_out = o_crc + align16((int64_t)no * 4);
+    Slot &sl = ln.slot[0];
+    if (!sl.ensure(o_out + tout)) return JFS_ERR_NO_MEMORY;
+    if (codec && !sl.ensure_split(std::max<int64_t>(scratch, 16))) return JFS_ERR_NO_MEMORY;
+    uint8_t *h = sl.h, *d = sl.d;
+    jfs_dev_block *h_sdesc = (jfs_dev_block *)(h + o_sdesc), *h_enc = (jfs_dev_block *)(h + o_enc),
+                  *h_cd = (jfs_dev_block *)(h + o_cd);
+    jfs_aead_block *h_sad = (jfs_aead_block *)(h + o_sad), *h_oad = (jfs_aead_block *)(h + o_oad);
+    jfs_compact_out *h_plan = (jfs_compact_out *)(h + o_plan);
+    jfs_compact_seg *h_seg = (jfs_compact_seg *)(h + o_seg);
+    uint32_t *h_seed = (uint32_t *)(h + o_seed);
+    int32_t *h_srcn = (int32_t *)(h + o_srcn);
+    const int32_t *h_open = (const int32_t *)(h + o_open), *h_ret = (const int32_t *)(h + o_ret),
+                  *h_r2 = (const int32_t *)(h + o_r2);
+    const uint32_t *h_crc = (const uint32_t *)(h + o_crc);
+    const jfs_dev_block *d_sdesc = (const jfs_dev_block *)(d + o_sdesc), *d_enc = (const jfs_dev_block *)(d + o_enc),
+                        *d_cd = (const jfs_dev_block *)(d + o_cd);
+    const jfs_aead_block *d_sad = (const jfs_aead_block *)(d + o_sad), *d_oad = (const jfs_aead_block *)(d + o_oad);
+    int32_t *d_srcn = (int32_t *)(d + o_srcn), *d_open = (int32_t *)(d + o_open), *d_ret = (int32_t *)(d + o_ret),
+            *d_r2 = (int32_t *)(d + o_r2);
+    std::vector<CopyJob> jobs;
+    for (int k = 0; k < ns; k++) {
+        const jfs_iov &v = src[ss[k].idx];
+        const int64_t pay = ss[k].pay, plain = pay - 16;  // pay >= 16: the host answered shorter ones
+        jobs.push_back({h + in_off[k], v.src + ss[k].off, pay});
+        uint8_t *cell = h + o_kn + 64 * (int64_t)k, *d_cell = d + o_kn + 64 * (int64_t)k;
+        memcpy(cell, src_keys[ss[k].idx], (size_t)klen);
+        memcpy(cell + 32, v.src + ss[k].noff, 12);
+        // open in place over the staged payload; the codec reads the plaintext
+        // ("none": the opened payload is the decoded block)
+        h_sad[k] = jfs_aead_block{d + in_off[k], d + in_off[k], (int32_t)pay, (int32_t)pay, d_cell, d_cell + 32};
+        uint8_t *dec = codec ? sl.sp + dec_off[k] : d + in_off[k];
+        h_sdesc[k] = jfs_dev_block{d + in_off[k], dec, (int32_t)plain, (int32_t)(codec ? ss[k].cap : plain)};
+        h_srcn[k] = codec ? -1 : (int32_t)plain;  // a decoder overwrites it
+    }
+    h_sdesc[ns] = jfs_dev_block{nullptr, nullptr, 0, 0};
+    h_srcn[ns] = -1;
+    par_copy(jobs);
+    int64_t sg = 0;
+    for (int k = 0; k < no; k++) {
+        const int j = oo[k].idx;
+        const jfs_seal_param &p = out_p[j];
+        const int cnt = seg_first[j + 1] - seg_first[j];
+        uint8_t *pay = d + o_out + out_off[k];  // the envelope's payload area: bound + 16 bytes
+        uint8_t *gat = codec ? sl.sp + gat_off[k] : pay;
+        h_plan[k] = jfs_compact_out{gat, (int32_t)oo[k].total, (int32_t)sg, cnt, 0};
+        for (int q = 0; q < cnt; q++) {
+            jfs_compact_seg s = seg[seg_first[j] + q];
+            if (s.src >= 0) s.src = src_map[s.src] >= 0 ? src_map[s.src] : ns;
+            h_seg[sg + q] = s;
+        }
+        sg += cnt;
+        h_enc[k] = jfs_dev_block{gat, pay, (int32_t)oo[k].total, (int32_t)oo[k].bound};
+        h_cd[k] = jfs_dev_block{pay, nullptr, 0, 0};
+        uint8_t *cell = h + o_kn + 64 * (int64_t)(ns + k), *d_cell = d + o_kn + 64 * (int64_t)(ns + k);
+        memcpy(cell, p.key, (size_t)klen);
+        memcpy(cell + 32, p.nonce, 12);
+        // seal in place; with a codec the length comes from the encoder on the device
+        h_oad[k] = jfs_aead_block{pay, pay, (int32_t)oo[k].total, (int32_t)(oo[k].bound + 16), d_cell, d_cell + 32};
+        h_seed[k] = seal_header_crc(p);
+    }
+    // the small-batch LZ4 decoder and encoder share slot 1's scratch (see compact_run)
+    Slot &s1 = ln.slot[1];
+    const bool lz4 = algo == JFS_ALGO_LZ4, fast = lz4_fast_mode();
+    {
+        int64_t need = 0;
+        if (lz4 && ns > 0) need = lz4_decode_scratch(ns, desc_lens(h_sdesc, ns).data(), desc_caps(h_sdesc, ns).data());
+        if (lz4 && no > 0) need = std::max(need, lz4_encode_scratch(no, desc_lens(h_enc, no).data(), fast));
+        if (need > 0 && !s1.ensure_split(need)) return JFS_ERR_NO_MEMORY;
+    }
+    hipStream_t ks = ln.s_k;
+    // one H2D: sealed payloads, the plan, keys and the preset source lengths
+    if (hipMemcpyAsync(d, h, (size_t)o_open, hipMemcpyHostToDevice, ks) != hipSuccess) return JFS_ERR_HIP;
+    int lk = 0;
+    if (ns > 0) lk = jfs_launch_aead(cipher, d_sad, ns, 1, d_open, nullptr, ks);
+    if (lk == 0 && lz4 && ns > 0) {
+        lk = launch_lz4_decode(s1, h_sdesc, d_sdesc, ns, d_srcn, ks) == JFS_OK ? 0 : -1;
+    } else if (lk == 0 && algo == JFS_ALGO_ZSTD && ns > 0) {
+        lk = jfs_launch_zstd_decode(d_sdesc, ns, d_srcn, nullptr, ks);  // ciphertext on the host: it plans its own scratch
+    }
+    // a failed open left zeros, which may decode (for "none" they are the block): its verdict replaces the length
+    if (lk == 0) lk = jfs_launch_chain_merge(d_open, ns, d_srcn, ks);
+    const jfs_compact_out *d_plan = (const jfs_compact_out *)(d + o_plan);
+    const jfs_compact_seg *d_seg = (const jfs_compact_seg *)(d + o_seg);
+    if (lk == 0) lk = jfs_launch_gather(d_sdesc, d_srcn, ns + 1, d_plan, no, d_seg, max_total, d_ret, 0, ks);
+    if (lk == 0 && codec && no > 0) {
+        lk = lz4 ? (launch_lz4_encode(s1, h_enc, d_enc, no, d_ret, ks, fast) == JFS_OK ? 0 : -1)
+                 : launch_kernel(algo, COMPRESS, d_enc, no, d_ret, ks, zstd_parse_now());
+        // the encoder ran on every block: a failed gather's verdict replaces its result
+        if (lk == 0) lk = jfs_launch_gather(d_sdesc, d_srcn, ns + 1, d_plan, no, d_seg, max_total, d_ret, 1, ks);
+    }
+    // "none": the length is the planned total; the seal also runs over a block
+    // whose gather failed (its verdict in d_ret decides on the host)
+    if (lk == 0 && no > 0) lk = jfs_launch_aead(cipher, d_oad, no, 0, d_r2, codec ? d_ret : nullptr, ks);
+    if (lk == 0 && crc && no > 0)
+        lk = jfs_launch_crc32c_lens(d_cd, no, d_r2, (const uint32_t *)(d + o_seed), (uint32_t *)(d + o_crc), ks);
+    if (lk != 0 || hipMemcpyAsync(h + o_srcn, d + o_srcn, (size_t)(o_out - o_srcn), hipMemcpyDeviceToHost, ks) !=
+                       hipSuccess ||
+        hipStreamSynchronize(ks) != hipSuccess) {
+        (void)hipStreamSynchronize(ks);
+        return JFS_ERR_HIP;
+    }
+    for (int k = 0; k < ns; k++)  // aead.Open first (encrypt.go:283), then the codec
+        src_n[ss[k].idx] = h_open[k] < 0 ? JFS_ERR_AUTH
+                           : codec       ? finish_result(algo, DECOMPRESS, h_srcn[k])
+                                         : (int64_t)h_srcn[k];
+    std::vector<int64_t> res(no);
+    for (int k = 0; k < no; k++) {
+        const int32_t raw = h_ret[k];
+        int64_t r;
+        if (raw == JFS_CHAIN_FAILED) r = JFS_ERR_CORRUPT;
+        else if (codec) r = finish_result(algo, COMPRESS, raw);
+        else r = raw >= 0 ? (int64_t)raw : JFS_ERR_INVALID;
+        if (r >= 0 && h_r2[k] != r + 16) r = JFS_ERR_HIP;
+        else if (r >= 0 && oo[k].hdr + r + 16 > out[oo[k].idx].dst_cap) r = JFS_ERR_SHORT_BUFFER;
+        res[k] = r;
+        // exactly the sealed bytes come back
+        if (r >= 0 && hipMemcpyAsync(h + o_out + out_off[k], d + o_out + out_off[k], (size_t)(r + 16),
+                                     hipMemcpyDeviceToHost, ks) != hipSuccess) {
+            (void)hipStreamSynchronize(ks);
+            return JFS_ERR_HIP;
+        }
+    }
+    if (hipStreamSynchronize(ks) != hipSuccess) return JFS_ERR_HIP;
+    jobs.clear();
+    for (int k = 0; k < no; k++) {
+        const int j = oo[k].idx;
+        const int64_t r = res[k];
+        if (r >= 0) {
+            seal_header_write(out[j].dst, out_p[j]);
+            jobs.push_back({out[j].dst + oo[k].hdr, h + o_out + out_off[k], r + 16});
+        }
+        out_n[j] = r >= 0 ? oo[k].hdr + r + 16 : r;
+        if (crc) crc[j] = r >= 0 ? h_crc[k] : 0u;
+    }
+    par_copy(jobs);
+    return JFS_OK;
+}
+
+// The plan checks jfs_compact_batch and jfs_compact_seal_batch share (before
+// any device is touched); total[j] = output j's gathered bytes.
+bool compact_plan_ok(int algo, int nsrc, const jfs_iov *src, int nout, const jfs_iov *out, const int32_t *seg_first,
+                     const jfs_compact_seg *seg, const int64_t *src_n, const int64_t *out_n,
+                     std::vector<int64_t> &total) {
+    if (algo != JFS_ALGO_NONE && algo != JFS_ALGO_LZ4 && algo != JFS_ALGO_ZSTD) return false;
+    if (nsrc < 0 || nout < 0 || (nsrc > 0 && (!src || !src_n)) || (nout > 0 && (!out || !out_n || !seg_first)))
+        return false;
+    for (int i = 0; i < nsrc; i++) {
+        const jfs_iov &v = src[i];
+        if (v.src_len < 0 || v.dst_cap < 0 || v.src_len > INT32_MAX || v.dst_cap > INT32_MAX || (v.src_len > 0 && !v.src))
+            return false;
+    }
+    total.assign(nout, 0);
+    for (int j = 0; j < nout; j++) {
+        if (out[j].dst_cap < 0 || (out[j].dst_cap > 0 && !out[j].dst)) return false;
+        if (seg_first[j] < 0 || seg_first[j + 1] < seg_first[j] || (seg_first[j + 1] > seg_first[j] && !seg))
+            return false;
+        for (int k = seg_first[j]; k < seg_first[j + 1]; k++) {
+            const jfs_compact_seg &s = seg[k];
+            if (s.len <= 0 || (int64_t)s.dst_off != total[j] || s.src < -1 || s.src >= nsrc ||
+                (s.src >= 0 && s.src_off < 0))
+                return false;
+            total[j] += s.len;
+            if (total[j] > INT32_MAX) return false;
+        }
+    }
+    return true;
+}
+
 std::atomic<unsigned> g_compact_turn{0};
 
 // Small-batch device launches: per-device scratch shared by every caller,
@@ -2522,28 +2774,8 @@ int64_t jfs_compact_batch(int algo, int nsrc, const jfs_iov *src, int nout, cons
                           const int32_t *seg_first, const jfs_compact_seg *seg, int64_t *src_n, int64_t *out_n,
                           uint32_t *crc, uint32_t device_mask) {
     // the whole plan is checked before any device is touched
-    if (algo != JFS_ALGO_NONE && algo != JFS_ALGO_LZ4 && algo != JFS_ALGO_ZSTD) return JFS_ERR_INVALID;
-    if (nsrc < 0 || nout < 0 || (nsrc > 0 && (!src || !src_n)) || (nout > 0 && (!out || !out_n || !seg_first)))
-        return JFS_ERR_INVALID;
-    for (int i = 0; i < nsrc; i++) {
-        const jfs_iov &v = src[i];
-        if (v.src_len < 0 || v.dst_cap < 0 || v.src_len > INT32_MAX || v.dst_cap > INT32_MAX || (v.src_len > 0 && !v.src))
-            return JFS_ERR_INVALID;
-    }
-    std::vector<int64_t> total(nout, 0);
-    for (int j = 0; j < nout; j++) {
-        if (out[j].dst_cap < 0 || (out[j].dst_cap > 0 && !out[j].dst)) return JFS_ERR_INVALID;
-        if (seg_first[j] < 0 || seg_first[j + 1] < seg_first[j] || (seg_first[j + 1] > seg_first[j] && !seg))
-            return JFS_ERR_INVALID;
-        for (int k = seg_first[j]; k < seg_first[j + 1]; k++) {
-            const jfs_compact_seg &s = seg[k];
-            if (s.len <= 0 || (int64_t)s.dst_off != total[j] || s.src < -1 || s.src >= nsrc ||
-                (s.src >= 0 && s.src_off < 0))
-                return JFS_ERR_INVALID;
-            total[j] += s.len;
-            if (total[j] > INT32_MAX) return JFS_ERR_INVALID;
-        }
-    }
+    std::vector<int64_t> total;
+    if (!compact_plan_ok(algo, nsrc, src, nout, out, seg_first, seg, src_n, out_n, total)) return JFS_ERR_INVALID;
     std::vector<DevCtx *> ds;
     for (DevCtx *d : devices())
         if (device_mask == 0 || (d->id < 32 && (device_mask >> d->id) & 1u)) ds.push_back(d);
@@ -2586,6 +2818,99 @@ int64_t jfs_compact_batch(int algo, int nsrc, const jfs_iov *src, int nout, cons
     if (rc != JFS_OK) {  // the chain did not run: every block it held reports why
         for (const CompactSrc &s : ss) src_n[s.idx] = rc;
         for (const CompactOut &o : oo) out_n[o.idx] = rc;
+    }
+    const uint64_t ns = (uint64_t)(steady_ns() - t0);
+    if (OpStats *st = op_stats(algo, DECOMPRESS)) {
+        st->calls.fetch_add(1, std::memory_order_relaxed);
+        if (!ss.empty()) st->batches.fetch_add(1, std::memory_order_relaxed);
+        for (int i = 0; i < nsrc; i++) stat_block(st, src[i].src_len, src_n[i]);
+    }
+    if (OpStats *st = op_stats(algo, COMPRESS)) {
+        st->calls.fetch_add(1, std::memory_order_relaxed);
+        if (!oo.empty()) st->batches.fetch_add(1, std::memory_order_relaxed);
+        for (int j = 0; j < nout; j++) stat_block(st, total[j], out_n[j]);
+        st->nanos.fetch_add(ns, std::memory_order_relaxed);
+    }
+    return JFS_OK;
+}
+
+int64_t jfs_compact_seal_batch(int algo, int cipher, int nsrc, const jfs_iov *src, const uint8_t *const *src_keys,
+                               int nout, const jfs_iov *out, const jfs_seal_param *out_p, const int32_t *seg_first,
+                               const jfs_compact_seg *seg, int64_t *src_n, int64_t *out_n, uint32_t *crc,
+                               uint32_t device_mask) {
+    // the plan, the keys and the seal parameters are checked before any device is touched
+    std::vector<int64_t> total;
+    if (!compact_plan_ok(algo, nsrc, src, nout, out, seg_first, seg, src_n, out_n, total)) return JFS_ERR_INVALID;
+    if (jfs_cipher_key_size(cipher) < 0) return JFS_ERR_INVALID;
+    if ((nsrc > 0 && !src_keys) || (nout > 0 && !out_p)) return JFS_ERR_INVALID;
+    for (int i = 0; i < nsrc; i++)
+        if (!src_keys[i]) return JFS_ERR_INVALID;
+    for (int j = 0; j < nout; j++) {
+        const jfs_seal_param &q = out_p[j];
+        if (!q.key || !q.nonce || q.wrapped_len < 0 || q.wrapped_len > 65535 || (q.wrapped_len > 0 && !q.wrapped))
+            return JFS_ERR_INVALID;
+    }
+    std::vector<DevCtx *> ds;
+    for (DevCtx *d : devices())
+        if (device_mask == 0 || (d->id < 32 && (device_mask >> d->id) & 1u)) ds.push_back(d);
+    if (ds.empty()) return JFS_ERR_NO_DEVICE;
+    const int64_t t0 = steady_ns();
+    // what jfs_open_decompress_batch answers before the device runs
+    std::vector<SealedSrc> ss;
+    std::vector<int> src_map(nsrc, -1);
+    for (int i = 0; i < nsrc; i++) {
+        const jfs_iov &v = src[i];
+        int64_t noff = 0, nlen = 0;
+        const int64_t off = envelope_parse(v.src, v.src_len, nullptr, nullptr, &noff, &nlen);
+        const int64_t pay = v.src_len - off;  // ciphertext || tag
+        if (off < 0 || nlen != 12) src_n[i] = JFS_ERR_CORRUPT;
+        else if (pay < 16) src_n[i] = JFS_ERR_AUTH;
+        else if (algo != JFS_ALGO_NONE && pay == 16) src_n[i] = JFS_ERR_EMPTY_INPUT;
+        else if (algo == JFS_ALGO_NONE && v.dst_cap < pay - 16) src_n[i] = JFS_ERR_SHORT_BUFFER;
+        else {
+            // Zstd: the frame header is ciphertext on the host, so dst_cap is staged (see jfs_open_decompress_batch)
+            src_map[i] = (int)ss.size();
+            ss.push_back({i, off, noff, pay, algo == JFS_ALGO_NONE ? pay - 16 : std::min<int64_t>(v.dst_cap, INT32_MAX)});
+        }
+    }
+    // and what jfs_compress_seal_batch answers for the gathered block
+    std::vector<SealedOut> oo;
+    std::vector<int> own;  // outputs with an error of their own: a failed source still wins (below)
+    for (int j = 0; j < nout; j++) {
+        if (crc) crc[j] = 0;
+        const int64_t bound = jfs_envelope_bound(algo, total[j], out_p[j].wrapped_len);
+        const int64_t hdr = 3 + (int64_t)out_p[j].wrapped_len + 12;
+        bool dead = false;  // a source answered on the host feeds it
+        for (int k = seg_first[j]; k < seg_first[j + 1] && !dead; k++) dead = seg[k].src >= 0 && src_map[seg[k].src] < 0;
+        if (dead) {
+            out_n[j] = JFS_ERR_CORRUPT;
+            continue;
+        }
+        if (bound < 0) out_n[j] = JFS_ERR_INVALID;
+        else if (algo == JFS_ALGO_LZ4 && total[j] > LZ4_MAX_INPUT) out_n[j] = JFS_ERR_COMPRESS_FAIL;
+        else if (out[j].dst_cap < bound) out_n[j] = JFS_ERR_SHORT_BUFFER;
+        else {
+            oo.push_back({j, total[j], bound - hdr - 16, hdr});
+            continue;
+        }
+        own.push_back(j);
+    }
+    int64_t rc = JFS_OK;
+    if (!ss.empty() || !oo.empty()) {
+        DevCtx *dev = ds[g_compact_turn.fetch_add(1) % ds.size()];
+        std::unique_lock<std::mutex> lk;
+        Lane &ln = dev->acquire_lane(lk, algo * 2 + COMPRESS);
+        rc = compact_seal_run(dev, ln, algo, cipher, src, src_keys, ss, src_map, out, out_p, oo, seg_first, seg, src_n,
+                              out_n, crc);
+        if (rc == JFS_ERR_HIP) (void)lane_healthy(dev, ln);  // leave nothing in flight into the staging
+    }
+    if (rc != JFS_OK) {  // the chain did not run: every block it held reports why
+        for (const SealedSrc &s : ss) src_n[s.idx] = rc;
+        for (const SealedOut &o : oo) out_n[o.idx] = rc;
+    } else {
+        for (int j : own)  // a source that failed on the device, or is too short, wins over the block's own error
+            for (int k = seg_first[j]; k < seg_first[j + 1]; k++)
+                if (seg[k].src >= 0 && (int64_t)seg[k].src_off + seg[k].len > src_n[seg[k].src]) out_n[j] = JFS_ERR_CORRUPT;
     }
     const uint64_t ns = (uint64_t)(steady_ns() - t0);
     if (OpStats *st = op_stats(algo, DECOMPRESS)) {

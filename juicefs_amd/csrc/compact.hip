@@ -158,8 +158,31 @@ __global__ __launch_bounds__(LANES) void gather_copy_kernel(const jfs_dev_block 
     }
 }
 
+// The sealed chain (capi.hip, compact_seal_run) opens every source before it
+// decodes it.  A failed open zeroes its output (aead.hip), and zeros can be a
+// valid block -- for the "none" codec they always are -- so the open's verdict
+// has to reach the gather: one lane per source writes a negative open result
+// over src_n[i], which the plan kernel then reads as "that source failed".
+// Runs after the decoders (they write every src_n[i], and take the zeroed
+// payload like any other untrusted input) and before the gather.
+__global__ __launch_bounds__(LANES) void chain_merge_kernel(const int32_t *__restrict__ open_ret, int nsrc,
+                                                            int32_t *__restrict__ src_n) {
+    const int i = blockIdx.x * LANES + threadIdx.x;
+    if (i >= nsrc) return;
+    const int32_t r = ((gc_i32 *)open_ret)[i];
+    if (r < 0) ((JFS_GLOBAL int32_t *)src_n)[i] = r;
+}
+
 }  // namespace compact
 }  // namespace jfs
+
+extern "C" int jfs_launch_chain_merge(const int32_t *d_open_ret, int nsrc, int32_t *d_src_n, hipStream_t stream) {
+    using namespace jfs::compact;
+    if (nsrc <= 0) return 0;
+    hipLaunchKernelGGL(chain_merge_kernel, dim3((unsigned)((nsrc + LANES - 1) / LANES)), dim3(LANES), 0, stream,
+                       d_open_ret, nsrc, d_src_n);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 
 // plan (verdicts into d_ret; merge: see gather_plan_kernel) and, unless merge,
 // the copy.  max_dst_cap: host value >= every d_out[j].dst_cap.

@@ -83,6 +83,9 @@ int jfs_launch_lz4_split(const jfs_dev_block *d_desc, int nb, int32_t *d_ret, vo
 int jfs_launch_gather(const jfs_dev_block *d_src, const int32_t *d_src_n, int nsrc, const jfs_compact_out *d_out,
                       int nout, const jfs_compact_seg *d_seg, int32_t max_dst_cap, int32_t *d_ret, int merge,
                       hipStream_t stream);
+// sealed compaction: d_src_n[i] = d_open_ret[i] where the AEAD open of source i
+// failed (d_open_ret[i] < 0), so the gather counts it as a failed source
+int jfs_launch_chain_merge(const int32_t *d_open_ret, int nsrc, int32_t *d_src_n, hipStream_t stream);
 int jfs_launch_gen(uint8_t *d_dst, int nblk, int64_t block_bytes, char cls, uint64_t seed_base,
                    const uint8_t *d_vocab, hipStream_t stream);
 }

@@ -133,3 +133,72 @@ def open_decompress_batch(codec: int, algo: str, pairs, keys, device_mask: int =
         else:
             res.append((r, None))
     return res
+
+
+def compact_seal_batch(codec: int, algo: str, sources, keys, outputs, params, plan, device_mask: int = 0,
+                       with_crc: bool = False):
+    """Slice compaction of an encrypted volume on one GPU (jfs_compact_seal_batch):
+    open and decode the stored envelopes, gather the planned byte ranges into
+    new blocks, compress and seal those -- Compressor.CompactBatch with
+    open_decompress_batch in front and compress_seal_batch behind, without a
+    decoded or a decrypted byte leaving HBM.
+
+    sources: [(envelope, block_size)], keys: [data key] (one per source);
+    outputs: [writable dst], params: [(key, nonce, wrapped_key)] (one per
+    output; a fresh key / nonce pair for every output is the caller's duty);
+    plan: (seg_first, seg) as compress.compact_plan returns them.  Returns
+    (src_results, out_results[, crcs]): [(n, err)] as open_decompress_batch
+    gives for the sources and as compress_seal_batch gives for the gathered
+    blocks (JFS_ERR_CORRUPT for a block fed by a failed or short source), plus
+    each envelope's CRC-32C with with_crc."""
+    lib = L.load()
+    seg_first, seg = plan
+    ns, no = len(sources), len(outputs)
+    if len(seg_first) != no + 1:
+        raise ValueError("seg_first must have one entry per output plus one")
+    if len(keys) != ns or len(params) != no:
+        raise ValueError("one key per source and one (key, nonce, wrapped_key) per output")
+    _check_keys(algo, list(keys) + [p[0] for p in params], [p[1] for p in params])
+    siov, oiov = (L.JfsIov * max(ns, 1))(), (L.JfsIov * max(no, 1))()
+    kp = (ctypes.c_void_p * max(ns, 1))()
+    sp = (L.JfsSealParam * max(no, 1))()
+    keep = []
+    for i, ((obj, block_size), key) in enumerate(zip(sources, keys)):
+        s, sn, ks = _addr(obj, False)
+        kk, _, k1 = _addr(key, False)
+        keep.append((ks, k1))
+        siov[i].src, siov[i].src_len, siov[i].dst, siov[i].dst_cap = s, sn, None, int(block_size)
+        kp[i] = kk.value if isinstance(kk, ctypes.c_void_p) else kk
+    for j, (dst, (key, nonce, wrapped)) in enumerate(zip(outputs, params)):
+        d, dn, kd = _addr(dst, True)
+        kk, _, k1 = _addr(key, False)
+        nn, _, k2 = _addr(nonce, False)
+        ww, wn, k3 = _addr(wrapped, False)
+        keep.append((kd, k1, k2, k3))
+        oiov[j].src, oiov[j].src_len, oiov[j].dst, oiov[j].dst_cap = None, 0, d, dn
+        sp[j].key, sp[j].nonce, sp[j].wrapped, sp[j].wrapped_len = kk, nn, ww, wn
+    first = (ctypes.c_int32 * (no + 1))(*[int(x) for x in seg_first])
+    segs = (L.JfsCompactSeg * max(len(seg), 1))()
+    for k, (src, src_off, dst_off, n) in enumerate(seg):
+        segs[k].src, segs[k].src_off, segs[k].dst_off, segs[k].len = int(src), int(src_off), int(dst_off), int(n)
+    src_n, out_n = (ctypes.c_int64 * max(ns, 1))(), (ctypes.c_int64 * max(no, 1))()
+    crc = (ctypes.c_uint32 * max(no, 1))()
+    rc = lib.jfs_compact_seal_batch(codec, cipher_id(algo), ns, siov, kp, no, oiov, sp, first, segs, src_n, out_n,
+                                    crc if with_crc else None, device_mask)
+    if rc != 0:
+        raise _err_of(rc, 0, 0, "compact+seal")
+    src_res, out_res = [], []
+    for i in range(ns):
+        r = int(src_n[i])
+        if r < 0:
+            n = r if (codec == L.ALGO_LZ4 and r > L.JFS_ERR_BASE) else 0
+            src_res.append((n, _err_of(r, siov[i].dst_cap, siov[i].src_len, "open+decompress")))
+        else:
+            src_res.append((r, None))
+    for j in range(no):
+        r = int(out_n[j])
+        total = sum(s[3] for s in seg[seg_first[j]:seg_first[j + 1]])
+        out_res.append((0, _err_of(r, oiov[j].dst_cap, total, "compress+seal")) if r < 0 else (r, None))
+    if with_crc:
+        return src_res, out_res, [int(crc[j]) for j in range(no)]
+    return src_res, out_res
