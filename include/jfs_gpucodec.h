@@ -46,6 +46,7 @@ extern "C" {
 #define JFS_ERR_HIP (JFS_ERR_BASE - 8)           /* HIP runtime failure */
 #define JFS_ERR_NO_MEMORY (JFS_ERR_BASE - 9)     /* pinned/HBM staging for this block could not be allocated */
 #define JFS_ERR_AUTH (JFS_ERR_BASE - 10)         /* "cipher: message authentication failed" (aead.Open, encrypt.go:283) */
+#define JFS_ERR_CHECKSUM (JFS_ERR_BASE - 11)     /* "verify checksum failed: %d != %d" (checksum.go:68) */
 
 /* ---- Compressor surface (one synchronous call per block) ---------------- */
 
@@ -449,6 +450,65 @@ int64_t jfs_compact_seal_batch(int algo, int cipher, int nsrc, const jfs_iov *sr
                                int nout, const jfs_iov *out, const jfs_seal_param *out_p,
                                const int32_t *seg_first /* nout+1 */, const jfs_compact_seg *seg, int64_t *src_n,
                                int64_t *out_n, uint32_t *crc /* may be NULL */, uint32_t device_mask);
+
+/* ---- Read assembly (pkg/vfs/reader.go:813-879, pkg/object/checksum.go:55-85) --
+ * dataReader.Read fills a page from byte ranges of stored slices (zeros for
+ * s.Id == 0 and for the tail); on a compressed volume every range costs a whole
+ * decoded block (cached_store.go:162-178).  These calls are the GET-side mirror
+ * of the compaction calls: stored objects go up, are checked against their
+ * CRC-32C, opened, decoded and gathered on the device, and only the requested
+ * bytes come down.  The plan is compaction's (jfs_compact_seg, seg_first):
+ * read j is the run of segments seg[seg_first[j] .. seg_first[j+1]), a hole is
+ * src = -1 (the zero tail of a page is a hole segment), seg_count == 0 is an
+ * empty read. */
+
+/* The gather alone, device-resident: jfs_gather_device's contract (verdicts in
+ * d_ret, nothing written outside dst[0, total) or for a read that is not
+ * gathered) on a one-dimensional grid over the outputs' own tile counts, for
+ * batches whose outputs differ widely in size.  dst_cap: a HOST copy of every
+ * d_out[j].dst_cap (nout entries; it sizes the launch, a smaller value than the
+ * device's leaves that output's tail unwritten).  Asynchronous on `stream`. */
+int64_t jfs_read_gather_device(const jfs_dev_block *d_src, const int32_t *d_src_n, int nsrc, const jfs_compact_out *d_out,
+                               const int32_t *dst_cap, int nout, const jfs_compact_seg *d_seg, int32_t *d_ret,
+                               void *stream);
+
+/* Host buffers (what a Go dataReader.Read adapter calls).  Sources as for
+ * jfs_compact_batch: src[i].src/src_len the stored object, src[i].dst_cap its
+ * block size, src[i].dst ignored.  out[j].dst/dst_cap receives the raw
+ * gathered bytes of read j; out_n[j] = their count, or JFS_ERR_CORRUPT when a
+ * source feeding read j failed or is shorter than a segment needs.  Nothing is
+ * written to out[j].dst for a failed read; errors are per read (the
+ * all-or-nothing choice of reader.go:875-877 stays with the caller).
+ * src_n[i] = exactly what jfs_decompress_batch returns for that object, unless
+ * its checksum fails: src_crc[i] (src_crc may be NULL) is -1 for "no checksum"
+ * (verifyChecksum with ""), else the expected CRC-32C of the whole stored
+ * object in its low 32 bits.  It is computed on the device in front of
+ * everything else; on a mismatch src_n[i] = JFS_ERR_CHECKSUM, which wins over
+ * every other error of that source, and the source counts as failed.
+ * crc_got[i] (crc_got may be NULL) = the computed CRC of every source that had
+ * an expected value, 0 otherwise.
+ * Checked on the host first (JFS_ERR_INVALID): everything jfs_compact_batch
+ * rejects, a read whose total exceeds out[j].dst_cap, a src_crc[i] outside
+ * -1 .. 0xFFFFFFFF; then JFS_ERR_NO_DEVICE.  One device per call, the scratch
+ * failure policy (every src_n[i] / out_n[j] of the call JFS_ERR_NO_MEMORY or
+ * JFS_ERR_HIP, return JFS_OK) and "current device unchanged on return" are
+ * jfs_compact_batch's.  jfs_stats counts the sources under (algo, decompress),
+ * bytes_out being the decoded size; nothing is counted under compress. */
+int64_t jfs_read_batch(int algo, int nsrc, const jfs_iov *src, const int64_t *src_crc /* may be NULL */, int nout,
+                       const jfs_iov *out, const int32_t *seg_first /* nout+1 */, const jfs_compact_seg *seg,
+                       int64_t *src_n, int64_t *out_n, uint32_t *crc_got /* nsrc, may be NULL */,
+                       uint32_t device_mask);
+
+/* jfs_read_batch for a volume with object encryption: src[i] is the whole
+ * envelope and src_keys[i] its unwrapped data key, as for
+ * jfs_compact_seal_batch.  src_n[i] = exactly what jfs_open_decompress_batch
+ * returns, unless the checksum fails; the checksum covers the whole envelope
+ * and wins over JFS_ERR_CORRUPT and JFS_ERR_AUTH too.  Also JFS_ERR_INVALID: an
+ * unknown cipher, a NULL src_keys with nsrc > 0, a NULL src_keys[i]. */
+int64_t jfs_read_open_batch(int algo, int cipher, int nsrc, const jfs_iov *src, const uint8_t *const *src_keys,
+                            const int64_t *src_crc /* may be NULL */, int nout, const jfs_iov *out,
+                            const int32_t *seg_first /* nout+1 */, const jfs_compact_seg *seg, int64_t *src_n,
+                            int64_t *out_n, uint32_t *crc_got /* nsrc, may be NULL */, uint32_t device_mask);
 
 /* ---- Runtime / utilities ------------------------------------------------- */
 

@@ -25,6 +25,7 @@ JFS_ERR_INVALID = JFS_ERR_BASE - 7
 JFS_ERR_HIP = JFS_ERR_BASE - 8
 JFS_ERR_NO_MEMORY = JFS_ERR_BASE - 9
 JFS_ERR_AUTH = JFS_ERR_BASE - 10
+JFS_ERR_CHECKSUM = JFS_ERR_BASE - 11
 
 # every symbol include/jfs_gpucodec.h declares
 EXPORTS = [
@@ -41,6 +42,7 @@ EXPORTS = [
     "jfs_gather_device", "jfs_lz4_compact_device", "jfs_compact_batch", "jfs_compact_seal_batch",
     "jfs_lz4_compress_fast_device", "jfs_lz4_parse_mode", "jfs_set_lz4_parse_mode",
     "jfs_zstd_compress_fast_device", "jfs_zstd_parse_mode", "jfs_set_zstd_parse_mode",
+    "jfs_read_gather_device", "jfs_read_batch", "jfs_read_open_batch",
 ]
 # the hook include/jfs_gpucodec_lz4_fast_test.h declares (the fast LZ4 encoder's host twin)
 LZ4_FAST_TEST_EXPORTS = ["jfs_test_lz4_fast_host"]
@@ -195,6 +197,17 @@ def load() -> ctypes.CDLL:
                                            ctypes.POINTER(JfsCompactSeg), ctypes.POINTER(i64), ctypes.POINTER(i64),
                                            vp, u32]
     lib.jfs_compact_seal_batch.restype = i64
+    lib.jfs_read_gather_device.argtypes = [vp, vp, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, vp]
+    lib.jfs_read_gather_device.restype = i64
+    lib.jfs_read_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(JfsIov), ctypes.POINTER(i64), ctypes.c_int,
+                                   ctypes.POINTER(JfsIov), ctypes.POINTER(i32), ctypes.POINTER(JfsCompactSeg),
+                                   ctypes.POINTER(i64), ctypes.POINTER(i64), vp, u32]
+    lib.jfs_read_batch.restype = i64
+    lib.jfs_read_open_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(JfsIov),
+                                        ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(i64), ctypes.c_int,
+                                        ctypes.POINTER(JfsIov), ctypes.POINTER(i32), ctypes.POINTER(JfsCompactSeg),
+                                        ctypes.POINTER(i64), ctypes.POINTER(i64), vp, u32]
+    lib.jfs_read_open_batch.restype = i64
     lib.jfs_release_staging.argtypes = []
     lib.jfs_release_staging.restype = None
     lib.jfs_device_count.argtypes = []

@@ -182,6 +182,22 @@ class Compressor:
             return src_res, out_res, [int(crc[j]) for j in range(no)]
         return src_res, out_res
 
+    def ReadBatch(self, sources, reads, plan, crcs=None, device_mask: int = 0):
+        """Read assembly on one GPU (jfs_read_batch): check the stored source
+        objects against their CRC-32C, decode them and gather the planned byte
+        ranges, so that only the requested bytes come back over the host link.
+
+        sources: list of (stored_object, block_size); reads: list of writable
+        dst buffers, one per read; plan: (seg_first, seg) as read_plan returns
+        them; crcs: None, or one expected CRC-32C per source (None or -1: no
+        checksum, verifyChecksum with "").  Returns (src_results, read_results,
+        crc_got): [(n, err)] as DecompressBatch would give for the sources
+        ("verify checksum failed" where the CRC differs), [(n, err)] per read
+        (JFS_ERR_CORRUPT for a read fed by a failed or short source; its dst is
+        untouched) and the computed CRC of every source that had an expected
+        one.  read_expect gives the bytes a good read holds."""
+        return _read_call(self.algo, None, sources, None, reads, plan, crcs, device_mask)
+
 
 class noOp(Compressor):  # noqa: N801  (reference name, compress.go:51)
     algo = L.ALGO_NONE
@@ -343,6 +359,140 @@ def compact_plan(slices, block_size: int, src_block_size: int | None = None):
             p += take
     seg_first.append(len(seg))
     return sources, seg_first, seg
+
+
+def read_plan(reads, src_block_size: int):
+    """The gather plan of a batch of dataReader.Read calls (pkg/vfs/reader.go:
+    840-879 + readSlice :813-838).
+
+    reads: [(page_len, offset, slices)] -- one page of page_len bytes filled
+    from position `offset` of a chunk whose slice list is slices =
+    [(id, size, off, len)] (as compact_plan takes them; id == 0 reads as
+    zeros); what the slices do not cover is the page's zero tail.  Stored
+    blocks are cut at src_block_size.
+
+    Returns (sources, seg_first, seg): sources = [(read_index, slice_index,
+    block_index, block_len)], every stored block the batch touches, once, in
+    first-use order (shared between reads); seg / seg_first as for
+    jfs_read_batch, one run of segments per read, the zero tail a hole."""
+    S = int(src_block_size)
+    if S <= 0:
+        raise ValueError("block size must be positive")
+    sources, index, seg, seg_first = [], {}, [], []
+    for ri, (page_len, offset, slices) in enumerate(reads):
+        seg_first.append(len(seg))
+        read, pos = 0, 0
+        if page_len < 0 or offset < 0:
+            raise ValueError(f"read {ri}: negative page length or offset")
+        for si, (sid, size, off, ln) in enumerate(slices):
+            if ln < 0 or (sid != 0 and (off < 0 or off + ln > size)):
+                raise ValueError(f"read {ri} slice {si}: [{off}, {off + ln}) outside its {size} bytes")
+            if read < page_len and offset < pos + ln:  # reader.go:851-852
+                toread = min(page_len - read, pos + ln - offset)
+                p, end = off + (offset - pos), off + (offset - pos) + toread
+                if sid == 0:
+                    if toread > 0:
+                        seg.append((-1, 0, read, toread))
+                    p = end
+                while p < end:  # cut at the stored blocks' boundaries
+                    b = p // S
+                    take = min(end, (b + 1) * S) - p
+                    key = (sid, size, b)
+                    if key not in index:
+                        index[key] = len(sources)
+                        sources.append((ri, si, b, min(S, size - b * S)))
+                    seg.append((index[key], p - b * S, read + (p - (end - toread)), take))
+                    p += take
+                read += toread
+                offset += toread
+            pos += ln
+        if read < page_len:  # reader.go:862-865
+            seg.append((-1, 0, read, page_len - read))
+    seg_first.append(len(seg))
+    return sources, seg_first, seg
+
+
+def read_expect(decoded_sources, plan):
+    """What jfs_read_batch delivers for good reads: the stitch of the decoded
+    sources a plan names, one bytes object per read."""
+    seg_first, seg = plan
+    outs = []
+    for j in range(len(seg_first) - 1):
+        out = bytearray()
+        for src, src_off, dst_off, n in seg[seg_first[j]:seg_first[j + 1]]:
+            if dst_off != len(out) or n <= 0:
+                raise ValueError(f"read {j}: segments must tile the read in order")
+            if src < 0:
+                out += bytes(n)
+            else:
+                piece = bytes(decoded_sources[src][src_off:src_off + n])
+                if src_off < 0 or len(piece) != n:
+                    raise ValueError(f"read {j}: source {src} is shorter than [{src_off}, {src_off + n})")
+                out += piece
+        outs.append(bytes(out))
+    return outs
+
+
+def _read_call(algo: int, cipher, sources, keys, reads, plan, crcs, device_mask: int):
+    """jfs_read_batch (cipher None) / jfs_read_open_batch over host buffers"""
+    lib = L.load()
+    seg_first, seg = plan
+    ns, no = len(sources), len(reads)
+    if len(seg_first) != no + 1:
+        raise ValueError("seg_first must have one entry per read plus one")
+    if crcs is not None and len(crcs) != ns:
+        raise ValueError("one expected checksum (or None) per source")
+    siov, oiov = (L.JfsIov * max(ns, 1))(), (L.JfsIov * max(no, 1))()
+    kp = (ctypes.c_void_p * max(ns, 1))()
+    keep = []
+    for i, (obj, block_size) in enumerate(sources):
+        s, sn, ks = _addr(obj, False)
+        keep.append(ks)
+        siov[i].src, siov[i].src_len, siov[i].dst, siov[i].dst_cap = s, sn, None, int(block_size)
+        if cipher is not None:
+            kk, _, k1 = _addr(keys[i], False)
+            keep.append(k1)
+            kp[i] = kk.value if isinstance(kk, ctypes.c_void_p) else kk
+    for j, dst in enumerate(reads):
+        d, dn, kd = _addr(dst, True)
+        keep.append(kd)
+        oiov[j].src, oiov[j].src_len, oiov[j].dst, oiov[j].dst_cap = None, 0, d, dn
+    first = (ctypes.c_int32 * (no + 1))(*[int(x) for x in seg_first])
+    segs = (L.JfsCompactSeg * max(len(seg), 1))()
+    for k, (src, src_off, dst_off, n) in enumerate(seg):
+        segs[k].src, segs[k].src_off, segs[k].dst_off, segs[k].len = int(src), int(src_off), int(dst_off), int(n)
+    want = None
+    if crcs is not None:
+        want = (ctypes.c_int64 * max(ns, 1))(*[-1 if c is None else int(c) for c in crcs])
+    src_n, out_n = (ctypes.c_int64 * max(ns, 1))(), (ctypes.c_int64 * max(no, 1))()
+    got = (ctypes.c_uint32 * max(ns, 1))()
+    if cipher is None:
+        rc = lib.jfs_read_batch(algo, ns, siov, want, no, oiov, first, segs, src_n, out_n, got, device_mask)
+    else:
+        rc = lib.jfs_read_open_batch(algo, cipher, ns, siov, kp, want, no, oiov, first, segs, src_n, out_n, got,
+                                     device_mask)
+    if rc != 0:
+        raise _err(rc, 0, 0, "read")
+
+    def err_of(code, dst_len, src_len, op):
+        if code == L.JFS_ERR_AUTH:
+            return CompressError("cipher: message authentication failed", code)
+        return _err(code, dst_len, src_len, op)
+
+    src_res, out_res = [], []
+    for i in range(ns):
+        r = int(src_n[i])
+        if r == L.JFS_ERR_CHECKSUM:  # checksum.go:68
+            src_res.append((0, CompressError(f"verify checksum failed: {int(got[i])} != {int(want[i])}", r)))
+        elif r < 0:
+            n = r if (algo == L.ALGO_LZ4 and r > L.JFS_ERR_BASE) else 0
+            src_res.append((n, err_of(r, siov[i].dst_cap, siov[i].src_len, "decompress")))
+        else:
+            src_res.append((r, None))
+    for j in range(no):
+        r = int(out_n[j])
+        out_res.append((0, err_of(r, oiov[j].dst_cap, 0, "read")) if r < 0 else (r, None))
+    return src_res, out_res, [int(got[i]) for i in range(ns)]
 
 
 CSUM_BLOCK = 32 << 10  # disk_cache_file.go csBlock

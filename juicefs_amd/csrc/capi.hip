@@ -2186,6 +2186,200 @@ int64_t compact_seal_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_
     return JFS_OK;
 }
 
+// ---------------------------------------------------------------------------
+// read assembly: verify -> (open) -> decode -> gather on one device
+// (jfs_read_batch, jfs_read_open_batch)
+// ---------------------------------------------------------------------------
+// One stored object the device works on.  The first `ns` entries of the list
+// are the sources the chain decodes (bytes [off, off + pay) of the object are
+// staged: the whole object, or the sealed payload of an envelope); the rest are
+// objects the host already answered, staged whole only for their checksum.
+struct ReadSrc {
+    int idx;
+    int64_t off, noff, pay;  // SealedSrc's; off = noff = 0 without a cipher
+    int64_t cap;             // staged decode capacity
+    bool check;              // an expected CRC-32C came with it
+    uint32_t expect;
+};
+struct ReadOut {
+    int idx;
+    int64_t total;
+};
+
+// The GET-side mirror of compact_run / compact_seal_run (cipher < 0: no
+// envelopes), their staging and decoder choice, one pass on the lane's kernel
+// stream: stored bytes and the plan H2D, CRC-32C of every object that has an
+// expected value (for an envelope the payload's, seeded on the host with the
+// header's), open in place, decode, the opens' verdicts and then the
+// checksums' verdicts merged into the source lengths, plan and flat gather
+// into one packed area (16-byte aligned offsets), one D2H of the results and
+// that area; the host copies the good reads out.  st[0, ns) are the decoded
+// sources; src_map as in compact_run.  Returns JFS_OK with src_n / out_n /
+// crc_got of these objects filled, or JFS_ERR_NO_MEMORY / JFS_ERR_HIP.
+int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src, const uint8_t *const *src_keys,
+                 const std::vector<ReadSrc> &st, int ns, const std::vector<int> &src_map, const jfs_iov *out,
+                 const std::vector<ReadOut> &oo, const int32_t *seg_first, const jfs_compact_seg *seg, int64_t *src_n,
+                 int64_t *out_n, uint32_t *crc_got) {
+    LaneRun scope(dev, ln, algo * 2 + DECOMPRESS, (uint64_t)st.size());
+    const bool codec = algo != JFS_ALGO_NONE, sealed = cipher >= 0;
+    const int n = (int)st.size(), no = (int)oo.size();
+    const int klen = sealed ? jfs_cipher_key_size(cipher) : 0;
+    bool any_check = false;
+    std::vector<int64_t> in_off(n), out_off(no), dec_off(ns);
+    std::vector<int32_t> tile_first(no + 1);
+    int64_t tin = 0, tout = 0, scratch = 0, nseg = 0, ntiles = 0;
+    for (int k = 0; k < n; k++) {
+        in_off[k] = tin;
+        tin += align16(st[k].pay);
+        any_check = any_check || st[k].check;
+        if (codec && k < ns) {
+            dec_off[k] = scratch;
+            scratch += align16(st[k].cap);
+        }
+    }
+    for (int k = 0; k < no; k++) {
+        out_off[k] = tout;
+        tout += align16(oo[k].total);
+        nseg += seg_first[oo[k].idx + 1] - seg_first[oo[k].idx];
+        tile_first[k] = (int32_t)ntiles;
+        ntiles += jfs_gather_tiles(oo[k].total);
+        if (ntiles > INT32_MAX) return JFS_ERR_NO_MEMORY;
+    }
+    tile_first[no] = (int32_t)ntiles;
+    // staged area, mirrored pinned / HBM: [stored bytes | meta | results | packed reads]
+    // meta: source descriptors (ns + 1: the last one is "a failed source"), the
+    // plan, segments, tile prefix, the opens' descriptors and key | nonce cells,
+    // the checksum descriptors with their seeds, lengths (-1: no expected value)
+    // and expected values, the preset source lengths; results, which only the
+    // device writes: opens, reads, raw checksums, checked checksums
+    const int64_t blk_b = (int64_t)sizeof(jfs_dev_block), aead_b = (int64_t)sizeof(jfs_aead_block);
+    const int64_t o_sdesc = tin;
+    const int64_t o_plan = o_sdesc + align16((ns + 1) * blk_b);
+    const int64_t o_seg = o_plan + align16((int64_t)no * (int64_t)sizeof(jfs_compact_out));
+    const int64_t o_tf = o_seg + align16(nseg * (int64_t)sizeof(jfs_compact_seg));
+    const int64_t o_sad = o_tf + align16((int64_t)(no + 1) * 4);
+    const int64_t o_kn = o_sad + align16(ns * aead_b);
+    const int64_t o_cd = o_kn + 64 * (int64_t)ns;
+    const int64_t o_seed = o_cd + align16(n * blk_b);
+    const int64_t o_len = o_seed + align16((int64_t)n * 4);
+    const int64_t o_exp = o_len + align16((int64_t)n * 4);
+    const int64_t o_srcn = o_exp + align16((int64_t)n * 4);
+    const int64_t o_open = o_srcn + align16((int64_t)(ns + 1) * 4);
+    const int64_t o_ret = o_open + align16((int64_t)ns * 4);
+    const int64_t o_crc = o_ret + align16((int64_t)no * 4);
+    const int64_t o_got = o_crc + align16((int64_t)n * 4);
+    const int64_t o_out = o_got + align16((int64_t)n * 4);
+    Slot &sl = ln.slot[0];
+    if (!sl.ensure(o_out + tout)) return JFS_ERR_NO_MEMORY;
+    if (codec && !sl.ensure_split(std::max<int64_t>(scratch, 16))) return JFS_ERR_NO_MEMORY;
+    uint8_t *h = sl.h, *d = sl.d;
+    jfs_dev_block *h_sdesc = (jfs_dev_block *)(h + o_sdesc), *h_cd = (jfs_dev_block *)(h + o_cd);
+    jfs_aead_block *h_sad = (jfs_aead_block *)(h + o_sad);
+    jfs_compact_out *h_plan = (jfs_compact_out *)(h + o_plan);
+    jfs_compact_seg *h_seg = (jfs_compact_seg *)(h + o_seg);
+    uint32_t *h_seed = (uint32_t *)(h + o_seed), *h_exp = (uint32_t *)(h + o_exp);
+    int32_t *h_len = (int32_t *)(h + o_len), *h_srcn = (int32_t *)(h + o_srcn);
+    const int32_t *h_open = (const int32_t *)(h + o_open), *h_ret = (const int32_t *)(h + o_ret);
+    const uint32_t *h_got = (const uint32_t *)(h + o_got);
+    const jfs_dev_block *d_sdesc = (const jfs_dev_block *)(d + o_sdesc), *d_cd = (const jfs_dev_block *)(d + o_cd);
+    const jfs_aead_block *d_sad = (const jfs_aead_block *)(d + o_sad);
+    int32_t *d_srcn = (int32_t *)(d + o_srcn), *d_open = (int32_t *)(d + o_open), *d_ret = (int32_t *)(d + o_ret);
+    memcpy(h + o_tf, tile_first.data(), (size_t)(no + 1) * 4);
+    std::vector<CopyJob> jobs;
+    for (int k = 0; k < n; k++) {
+        const ReadSrc &s = st[k];
+        const jfs_iov &v = src[s.idx];
+        if (s.pay > 0) jobs.push_back({h + in_off[k], v.src + s.off, s.pay});
+        // the checksum covers the object as fetched: the staged bytes, behind the envelope header's on the host
+        h_cd[k] = jfs_dev_block{d + in_off[k], nullptr, (int32_t)s.pay, 0};
+        h_seed[k] = s.check && s.off > 0 ? host_crc32c(0, v.src, s.off) : 0u;
+        h_len[k] = s.check && s.pay > 0 ? (int32_t)s.pay : -1;
+        h_exp[k] = s.expect;
+        if (k >= ns) continue;
+        const int64_t plain = sealed ? s.pay - 16 : s.pay;  // sealed: pay >= 16, the host answered shorter ones
+        if (sealed) {
+            uint8_t *cell = h + o_kn + 64 * (int64_t)k, *d_cell = d + o_kn + 64 * (int64_t)k;
+            memcpy(cell, src_keys[s.idx], (size_t)klen);
+            memcpy(cell + 32, v.src + s.noff, 12);
+            // open in place over the staged payload; the codec reads the plaintext
+            h_sad[k] = jfs_aead_block{d + in_off[k], d + in_off[k], (int32_t)s.pay, (int32_t)s.pay, d_cell, d_cell + 32};
+        }
+        // "none": the stored (opened) object is the decoded block
+        uint8_t *dec = codec ? sl.sp + dec_off[k] : d + in_off[k];
+        h_sdesc[k] = jfs_dev_block{d + in_off[k], dec, (int32_t)plain, (int32_t)(codec ? s.cap : plain)};
+        h_srcn[k] = codec ? -1 : (int32_t)plain;  // a decoder overwrites it
+    }
+    h_sdesc[ns] = jfs_dev_block{nullptr, nullptr, 0, 0};
+    h_srcn[ns] = -1;
+    par_copy(jobs);
+    int64_t sg = 0;
+    for (int k = 0; k < no; k++) {
+        const int j = oo[k].idx;
+        const int cnt = seg_first[j + 1] - seg_first[j];
+        h_plan[k] = jfs_compact_out{d + o_out + out_off[k], (int32_t)oo[k].total, (int32_t)sg, cnt, 0};
+        for (int q = 0; q < cnt; q++) {
+            jfs_compact_seg s = seg[seg_first[j] + q];
+            if (s.src >= 0) s.src = src_map[s.src] >= 0 ? src_map[s.src] : ns;
+            h_seg[sg + q] = s;
+        }
+        sg += cnt;
+    }
+    // the small-batch LZ4 decoder's scratch (slot 1's) is sized before anything is queued (see compact_run)
+    Slot &s1 = ln.slot[1];
+    const bool lz4 = algo == JFS_ALGO_LZ4;
+    if (lz4 && ns > 0) {
+        const int64_t need = lz4_decode_scratch(ns, desc_lens(h_sdesc, ns).data(), desc_caps(h_sdesc, ns).data());
+        if (need > 0 && !s1.ensure_split(need)) return JFS_ERR_NO_MEMORY;
+    }
+    hipStream_t ks = ln.s_k;
+    // one H2D: stored bytes, the plan, keys, checksum inputs and the preset source lengths
+    if (hipMemcpyAsync(d, h, (size_t)o_open, hipMemcpyHostToDevice, ks) != hipSuccess) return JFS_ERR_HIP;
+    int lk = 0;
+    // verifyChecksum sits in front of Decrypt and Decompress: before the open rewrites the staged bytes
+    if (any_check)
+        lk = jfs_launch_crc32c_lens(d_cd, n, (const int32_t *)(d + o_len), (const uint32_t *)(d + o_seed),
+                                    (uint32_t *)(d + o_crc), ks);
+    if (lk == 0 && sealed && ns > 0) lk = jfs_launch_aead(cipher, d_sad, ns, 1, d_open, nullptr, ks);
+    if (lk == 0 && lz4 && ns > 0) {
+        lk = launch_lz4_decode(s1, h_sdesc, d_sdesc, ns, d_srcn, ks) == JFS_OK ? 0 : -1;
+    } else if (lk == 0 && algo == JFS_ALGO_ZSTD && ns > 0) {
+        lk = jfs_launch_zstd_decode(d_sdesc, ns, d_srcn, nullptr, ks);  // plans its own scratch
+    }
+    // a failed open left zeros, which may decode: its verdict replaces the length (see compact_seal_run)
+    if (lk == 0 && sealed) lk = jfs_launch_chain_merge(d_open, ns, d_srcn, ks);
+    if (lk == 0 && any_check)
+        lk = jfs_launch_verify_gate((const uint32_t *)(d + o_crc), (const int32_t *)(d + o_len),
+                                    (const uint32_t *)(d + o_exp), n, ns, d_srcn, (uint32_t *)(d + o_got), ks);
+    if (lk == 0)
+        lk = jfs_launch_gather_flat(d_sdesc, d_srcn, ns + 1, (const jfs_compact_out *)(d + o_plan), no,
+                                    (const jfs_compact_seg *)(d + o_seg), d_ret, (const int32_t *)(d + o_tf), ntiles, ks);
+    // one D2H: the results and every read, packed
+    if (lk != 0 || hipMemcpyAsync(h + o_srcn, d + o_srcn, (size_t)(o_out + tout - o_srcn), hipMemcpyDeviceToHost, ks) !=
+                       hipSuccess ||
+        hipStreamSynchronize(ks) != hipSuccess) {
+        (void)hipStreamSynchronize(ks);
+        return JFS_ERR_HIP;
+    }
+    for (int k = 0; k < n; k++) {
+        const ReadSrc &s = st[k];
+        const uint32_t got = s.check && s.pay > 0 ? h_got[k] : 0u;  // an empty object's CRC is 0
+        if (crc_got) crc_got[s.idx] = got;
+        if (s.check && got != s.expect) src_n[s.idx] = JFS_ERR_CHECKSUM;  // before aead.Open and the codec
+        else if (k >= ns) continue;                                             // the host's answer stands
+        else if (sealed && h_open[k] < 0) src_n[s.idx] = JFS_ERR_AUTH;
+        else src_n[s.idx] = codec ? finish_result(algo, DECOMPRESS, h_srcn[k]) : (int64_t)h_srcn[k];
+    }
+    jobs.clear();
+    for (int k = 0; k < no; k++) {
+        const int j = oo[k].idx;
+        const int32_t raw = h_ret[k];
+        out_n[j] = raw == JFS_CHAIN_FAILED ? JFS_ERR_CORRUPT : raw >= 0 ? (int64_t)raw : JFS_ERR_INVALID;
+        if (raw > 0) jobs.push_back({out[j].dst, h + o_out + out_off[k], raw});
+    }
+    par_copy(jobs);
+    return JFS_OK;
+}
+
 // The plan checks jfs_compact_batch and jfs_compact_seal_batch share (before
 // any device is touched); total[j] = output j's gathered bytes.
 bool compact_plan_ok(int algo, int nsrc, const jfs_iov *src, int nout, const jfs_iov *out, const int32_t *seg_first,
@@ -2226,7 +2420,7 @@ struct SplitScratch {
     int64_t cap = 0;
     hipEvent_t ev_done = nullptr;
 };
-SplitScratch g_split[64], g_eseg_scr[64], g_fast_scr[64];
+SplitScratch g_split[64], g_eseg_scr[64], g_fast_scr[64], g_read_scr[64];
 
 // One LZ4 small-batch launch (nblk > 0) on the caller's stream with `need`
 // bytes of the current device's scratch in `tab`: launch(scratch, cap, stream)
@@ -2925,6 +3119,150 @@ int64_t jfs_compact_seal_batch(int algo, int cipher, int nsrc, const jfs_iov *sr
         st->nanos.fetch_add(ns, std::memory_order_relaxed);
     }
     return JFS_OK;
+}
+
+int64_t jfs_read_gather_device(const jfs_dev_block *d_src, const int32_t *d_src_n, int nsrc, const jfs_compact_out *d_out,
+                               const int32_t *dst_cap, int nout, const jfs_compact_seg *d_seg, int32_t *d_ret,
+                               void *stream) {
+    if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
+    if (nsrc < 0 || nout < 0 || (nout > 0 && (!d_out || !d_ret || !dst_cap))) return JFS_ERR_INVALID;
+    if (nout == 0) return JFS_OK;
+    int64_t ntiles = 0;
+    for (int j = 0; j < nout; j++) ntiles += jfs_gather_tiles(dst_cap[j]);
+    if (ntiles > INT32_MAX) return JFS_ERR_INVALID;
+    // the tile prefix is built on the device from d_out, in the current device's shared scratch
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return JFS_ERR_HIP;
+    SplitScratch &z = g_read_scr[dev];
+    std::lock_guard<std::mutex> lk(z.mu);
+    if (!z.ev_done && hipEventCreateWithFlags(&z.ev_done, hipEventDisableTiming) != hipSuccess) return JFS_ERR_HIP;
+    const int64_t need = ((int64_t)nout + 1) * 4;
+    if (need > z.cap) {
+        if (hipEventSynchronize(z.ev_done) != hipSuccess) return JFS_ERR_HIP;  // earlier launches may still use it
+        if (z.p) (void)hipFree(z.p);
+        z.p = nullptr;
+        z.cap = 0;
+        int64_t want = 1ll << 20;
+        while (want < need) want <<= 1;
+        if (hipMalloc((void **)&z.p, (size_t)want) != hipSuccess) return JFS_ERR_NO_MEMORY;
+        z.cap = want;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (hipStreamWaitEvent(st, z.ev_done, 0) != hipSuccess) return JFS_ERR_HIP;
+    int32_t *d_tf = (int32_t *)z.p;
+    if (jfs_launch_gather_prefix(d_out, nout, d_tf, st) != 0 ||
+        jfs_launch_gather_flat(d_src, d_src_n, nsrc, d_out, nout, d_seg, d_ret, d_tf, ntiles, st) != 0)
+        return JFS_ERR_HIP;
+    return hipEventRecord(z.ev_done, st) == hipSuccess ? JFS_OK : JFS_ERR_HIP;
+}
+
+// jfs_read_batch (cipher < 0) and jfs_read_open_batch
+static int64_t read_call(int algo, int cipher, int nsrc, const jfs_iov *src, const uint8_t *const *src_keys,
+                         const int64_t *src_crc, int nout, const jfs_iov *out, const int32_t *seg_first,
+                         const jfs_compact_seg *seg, int64_t *src_n, int64_t *out_n, uint32_t *crc_got,
+                         uint32_t device_mask) {
+    const bool sealed = cipher >= 0;
+    // the plan, the keys and the checksums are checked before any device is touched
+    std::vector<int64_t> total;
+    if (!compact_plan_ok(algo, nsrc, src, nout, out, seg_first, seg, src_n, out_n, total)) return JFS_ERR_INVALID;
+    for (int j = 0; j < nout; j++)
+        if (total[j] > out[j].dst_cap) return JFS_ERR_INVALID;
+    for (int i = 0; src_crc && i < nsrc; i++)
+        if (src_crc[i] < -1 || src_crc[i] > 0xFFFFFFFFll) return JFS_ERR_INVALID;
+    if (sealed) {
+        if (jfs_cipher_key_size(cipher) < 0 || (nsrc > 0 && !src_keys)) return JFS_ERR_INVALID;
+        for (int i = 0; i < nsrc; i++)
+            if (!src_keys[i]) return JFS_ERR_INVALID;
+    }
+    std::vector<DevCtx *> ds;
+    for (DevCtx *d : devices())
+        if (device_mask == 0 || (d->id < 32 && (device_mask >> d->id) & 1u)) ds.push_back(d);
+    if (ds.empty()) return JFS_ERR_NO_DEVICE;
+    const int64_t t0 = steady_ns();
+    // what jfs_decompress_batch / jfs_open_decompress_batch answer before the device runs
+    std::vector<ReadSrc> st, only_crc;
+    std::vector<int> src_map(nsrc, -1);
+    for (int i = 0; i < nsrc; i++) {
+        const jfs_iov &v = src[i];
+        const bool check = src_crc && src_crc[i] >= 0;
+        const uint32_t expect = check ? (uint32_t)src_crc[i] : 0u;
+        if (crc_got) crc_got[i] = 0;
+        ReadSrc r{i, 0, 0, v.src_len, 0, check, expect};
+        bool run = false;
+        if (sealed) {
+            int64_t nlen = 0;
+            r.off = envelope_parse(v.src, v.src_len, nullptr, nullptr, &r.noff, &nlen);
+            r.pay = v.src_len - r.off;  // ciphertext || tag
+            if (r.off < 0 || nlen != 12) src_n[i] = JFS_ERR_CORRUPT;
+            else if (r.pay < 16) src_n[i] = JFS_ERR_AUTH;
+            else if (algo != JFS_ALGO_NONE && r.pay == 16) src_n[i] = JFS_ERR_EMPTY_INPUT;
+            else if (algo == JFS_ALGO_NONE && v.dst_cap < r.pay - 16) src_n[i] = JFS_ERR_SHORT_BUFFER;
+            else {
+                // Zstd: the frame header is ciphertext on the host, so dst_cap is staged (see jfs_open_decompress_batch)
+                r.cap = algo == JFS_ALGO_NONE ? r.pay - 16 : std::min<int64_t>(v.dst_cap, INT32_MAX);
+                run = true;
+            }
+        } else if (algo == JFS_ALGO_NONE ? v.dst_cap < v.src_len : v.src_len == 0) {
+            src_n[i] = algo == JFS_ALGO_NONE ? JFS_ERR_SHORT_BUFFER : JFS_ERR_EMPTY_INPUT;
+        } else {
+            r.cap = algo == JFS_ALGO_NONE ? v.src_len : staged_cap(algo, DECOMPRESS, v);
+            run = true;
+        }
+        if (run) {
+            src_map[i] = (int)st.size();
+            st.push_back(r);
+        } else if (check && v.src_len == 0) {  // an empty object: CRC 0, no device needed
+            if (expect != 0) src_n[i] = JFS_ERR_CHECKSUM;
+        } else if (check) {  // answered above, but verifyChecksum reads the whole object first
+            only_crc.push_back(ReadSrc{i, 0, 0, v.src_len, 0, true, expect});
+        }
+    }
+    const int ns = (int)st.size();
+    st.insert(st.end(), only_crc.begin(), only_crc.end());
+    std::vector<ReadOut> oo;
+    for (int j = 0; j < nout; j++) {
+        bool dead = false;  // a source answered on the host feeds it
+        for (int k = seg_first[j]; k < seg_first[j + 1] && !dead; k++) dead = seg[k].src >= 0 && src_map[seg[k].src] < 0;
+        if (dead) out_n[j] = JFS_ERR_CORRUPT;
+        else if (total[j] == 0) out_n[j] = 0;
+        else oo.push_back({j, total[j]});
+    }
+    int64_t rc = JFS_OK;
+    if (!st.empty() || !oo.empty()) {
+        DevCtx *dev = ds[g_compact_turn.fetch_add(1) % ds.size()];
+        std::unique_lock<std::mutex> lk;
+        Lane &ln = dev->acquire_lane(lk, algo * 2 + DECOMPRESS);
+        rc = read_run(dev, ln, algo, cipher, src, src_keys, st, ns, src_map, out, oo, seg_first, seg, src_n, out_n,
+                      crc_got);
+        if (rc == JFS_ERR_HIP) (void)lane_healthy(dev, ln);  // leave nothing in flight into the staging
+    }
+    if (rc != JFS_OK) {  // the chain did not run: every object it held reports why
+        for (const ReadSrc &s : st) src_n[s.idx] = rc;
+        for (const ReadOut &o : oo) out_n[o.idx] = rc;
+    }
+    if (OpStats *os = op_stats(algo, DECOMPRESS)) {
+        os->calls.fetch_add(1, std::memory_order_relaxed);
+        if (ns > 0) os->batches.fetch_add(1, std::memory_order_relaxed);
+        for (int i = 0; i < nsrc; i++) stat_block(os, src[i].src_len, src_n[i]);
+        os->nanos.fetch_add((uint64_t)(steady_ns() - t0), std::memory_order_relaxed);
+    }
+    return JFS_OK;
+}
+
+int64_t jfs_read_batch(int algo, int nsrc, const jfs_iov *src, const int64_t *src_crc, int nout, const jfs_iov *out,
+                       const int32_t *seg_first, const jfs_compact_seg *seg, int64_t *src_n, int64_t *out_n,
+                       uint32_t *crc_got, uint32_t device_mask) {
+    return read_call(algo, -1, nsrc, src, nullptr, src_crc, nout, out, seg_first, seg, src_n, out_n, crc_got,
+                     device_mask);
+}
+
+int64_t jfs_read_open_batch(int algo, int cipher, int nsrc, const jfs_iov *src, const uint8_t *const *src_keys,
+                            const int64_t *src_crc, int nout, const jfs_iov *out, const int32_t *seg_first,
+                            const jfs_compact_seg *seg, int64_t *src_n, int64_t *out_n, uint32_t *crc_got,
+                            uint32_t device_mask) {
+    if (cipher < 0) return JFS_ERR_INVALID;
+    return read_call(algo, cipher, nsrc, src, src_keys, src_crc, nout, out, seg_first, seg, src_n, out_n, crc_got,
+                     device_mask);
 }
 
 int jfs_device_count(void) { return (int)devices().size(); }

@@ -9,7 +9,10 @@
 //                       decoder wrote them) and writes the verdict to ret[j]:
 //                       the block's total, -1 (bad plan) or JFS_CHAIN_FAILED;
 //   gather_copy_kernel  grid (output tiles, blocks): moves the bytes of the
-//                       blocks whose verdict is a total.
+//                       blocks whose verdict is a total;
+//   gather_copy_flat_kernel  the same tile body on a one-dimensional grid over
+//                       a per-output tile prefix, for the read path's batches
+//                       of very different output sizes.
 // Work is split by OUTPUT position: a tile is TILE bytes of one block,
 // whatever segments it is made of, so one 4 MiB single-segment block spreads
 // over 256 workgroups and a block of thousands of one-byte segments does not
@@ -108,21 +111,18 @@ __device__ inline uint4 shift_bytes(const uint4 x, const uint4 y, int sm) {
     return make_uint4(o[0], o[1], o[2], o[3]);
 }
 
-__global__ __launch_bounds__(LANES) void gather_copy_kernel(const jfs_dev_block *__restrict__ src,
-                                                            const jfs_compact_out *__restrict__ out,
-                                                            const jfs_compact_seg *__restrict__ seg,
-                                                            const int32_t *__restrict__ ret) {
+// One TILE of output block o (its segments sg, its verdict total > 0): the body
+// both copy kernels run, so the 2-D and the flat grid move the same words the
+// same way.  Every lane of the workgroup calls it (it synchronises).
+__device__ __forceinline__ void gather_tile(const jfs_dev_block *__restrict__ src, const jfs_compact_out o,
+                                            const gc_seg *sg, const int32_t total, const int64_t tile) {
     __shared__ int krange[2];
-    const int j = blockIdx.y, t = threadIdx.x;
-    const int32_t total = ((gc_i32 *)ret)[j];  // the plan kernel's verdict
-    if (total <= 0) return;
-    const jfs_compact_out o = ((gc_out *)out)[j];
+    const int t = threadIdx.x;
     g_u8 *dst = (g_u8 *)o.dst;
-    const gc_seg *sg = (gc_seg *)seg + o.seg_first;
     // word w of the block holds output positions [16 w - m, 16 w - m + 16): aligned in memory
     const int m = (int)((uintptr_t)o.dst & 15u);
     const int64_t nwords = ((int64_t)m + total + 15) >> 4;
-    const int64_t w0 = (int64_t)blockIdx.x * WORDS;
+    const int64_t w0 = tile * WORDS;
     if (w0 >= nwords) return;
     const int64_t w1 = w0 + WORDS < nwords ? w0 + WORDS : nwords;
     if (t < 2) {  // the segments this tile touches
@@ -158,6 +158,79 @@ __global__ __launch_bounds__(LANES) void gather_copy_kernel(const jfs_dev_block 
     }
 }
 
+__global__ __launch_bounds__(LANES) void gather_copy_kernel(const jfs_dev_block *__restrict__ src,
+                                                            const jfs_compact_out *__restrict__ out,
+                                                            const jfs_compact_seg *__restrict__ seg,
+                                                            const int32_t *__restrict__ ret) {
+    const int j = blockIdx.y;
+    const int32_t total = ((gc_i32 *)ret)[j];  // the plan kernel's verdict
+    if (total <= 0) return;
+    const jfs_compact_out o = ((gc_out *)out)[j];
+    gather_tile(src, o, (gc_seg *)seg + o.seg_first, total, (int64_t)blockIdx.x);
+}
+
+// Tiles a block of `cap` bytes may need: it has at most (15 + cap + 15) / 16
+// destination-aligned words.  The host sizes both grids with it, and the flat
+// grid's prefix (below) is its running sum.
+__host__ __device__ inline int64_t tiles_of(int64_t cap) { return cap > 0 ? (cap + 30 + TILE - 1) / TILE : 0; }
+
+// The read path's grid (capi.hip, read_run): a batch mixes 4 KiB and 4 MiB
+// outputs, so a (largest output's tiles) x nout grid would be almost all empty
+// workgroups.  Here the grid is one-dimensional over tile_first, the running
+// sum of every output's own tile count (nout + 1 entries, tile_first[0] = 0):
+// a workgroup finds its output by binary search and runs the same tile body.
+__global__ __launch_bounds__(LANES) void gather_copy_flat_kernel(const jfs_dev_block *__restrict__ src,
+                                                                 const jfs_compact_out *__restrict__ out, int nout,
+                                                                 const jfs_compact_seg *__restrict__ seg,
+                                                                 const int32_t *__restrict__ ret,
+                                                                 const int32_t *__restrict__ tile_first) {
+    const gc_i32 *tf = (gc_i32 *)tile_first;
+    const int32_t b = (int32_t)blockIdx.x;
+    if (b >= tf[nout]) return;
+    int lo = 0, hi = nout - 1;  // the last output whose first tile is at or before b (empty outputs share a start)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tf[mid] <= b) lo = mid;
+        else hi = mid - 1;
+    }
+    const int j = lo;
+    const int32_t total = ((gc_i32 *)ret)[j];  // the plan kernel's verdict
+    if (total <= 0) return;
+    const jfs_compact_out o = ((gc_out *)out)[j];
+    gather_tile(src, o, (gc_seg *)seg + o.seg_first, total, (int64_t)(b - tf[j]));
+}
+
+// tile_first from the outputs' dst_cap on the device (jfs_read_gather_device:
+// its caller has no staged prefix).  One workgroup: lane t sums a run of
+// outputs, lane 0 scans the 256 sums, every lane writes its run's prefix.
+__global__ __launch_bounds__(LANES) void gather_prefix_kernel(const jfs_compact_out *__restrict__ out, int nout,
+                                                              int32_t *__restrict__ tile_first) {
+    __shared__ int64_t part[LANES];
+    const int t = threadIdx.x;
+    const int per = (nout + LANES - 1) / LANES;
+    const int j0 = t * per < nout ? t * per : nout, j1 = j0 + per < nout ? j0 + per : nout;
+    int64_t sum = 0;
+    for (int j = j0; j < j1; j++) sum += tiles_of(((gc_out *)out)[j].dst_cap);
+    part[t] = sum;
+    __syncthreads();
+    if (t == 0) {
+        int64_t run = 0;
+        for (int i = 0; i < LANES; i++) {
+            const int64_t v = part[i];
+            part[i] = run;
+            run += v;
+        }
+    }
+    __syncthreads();
+    int64_t run = part[t];
+    JFS_GLOBAL int32_t *tf = (JFS_GLOBAL int32_t *)tile_first;
+    for (int j = j0; j < j1; j++) {
+        tf[j] = (int32_t)(run < INT32_MAX ? run : INT32_MAX);
+        run += tiles_of(((gc_out *)out)[j].dst_cap);
+    }
+    if (t == LANES - 1) tf[nout] = (int32_t)(run < INT32_MAX ? run : INT32_MAX);  // the last lane's run ends at nout
+}
+
 // The sealed chain (capi.hip, compact_seal_run) opens every source before it
 // decodes it.  A failed open zeroes its output (aead.hip), and zeros can be a
 // valid block -- for the "none" codec they always are -- so the open's verdict
@@ -171,6 +244,27 @@ __global__ __launch_bounds__(LANES) void chain_merge_kernel(const int32_t *__res
     if (i >= nsrc) return;
     const int32_t r = ((gc_i32 *)open_ret)[i];
     if (r < 0) ((JFS_GLOBAL int32_t *)src_n)[i] = r;
+}
+
+// The read chain (capi.hip, read_run) checks every stored object's CRC-32C
+// before anything else sees a byte of it (pkg/object/checksum.go:55-85).  The
+// decoders still run on a mismatching object; like a failed open, only its
+// verdict is replaced.  One lane per staged object i: lens[i] > 0 means "has an
+// expected value" and crc[i] is what crc32c.hip computed; crc_got[i] receives
+// it (0 without an expected value), and a mismatch on one of the first ndec
+// objects (the decoded sources) writes JFS_CHECKSUM_FAILED over src_n[i].
+// Runs after the decoders and the open's merge, before the gather's plan.
+__global__ __launch_bounds__(LANES) void verify_gate_kernel(const uint32_t *__restrict__ crc,
+                                                            const int32_t *__restrict__ lens,
+                                                            const uint32_t *__restrict__ expect, int n, int ndec,
+                                                            int32_t *__restrict__ src_n,
+                                                            uint32_t *__restrict__ crc_got) {
+    const int i = blockIdx.x * LANES + threadIdx.x;
+    if (i >= n) return;
+    const bool has = ((gc_i32 *)lens)[i] > 0;
+    const uint32_t got = has ? ((gc_u32 *)crc)[i] : 0u;
+    ((g_u32 *)crc_got)[i] = got;
+    if (has && got != ((gc_u32 *)expect)[i] && i < ndec) ((JFS_GLOBAL int32_t *)src_n)[i] = JFS_CHECKSUM_FAILED;
 }
 
 }  // namespace compact
@@ -205,4 +299,43 @@ extern "C" int jfs_launch_gather(const jfs_dev_block *d_src, const int32_t *d_sr
         if (hipGetLastError() != hipSuccess) return -1;
     }
     return 0;
+}
+
+extern "C" int64_t jfs_gather_tiles(int64_t cap) { return jfs::compact::tiles_of(cap); }
+
+// d_tile_first[j] = running sum of jfs_gather_tiles(d_out[j].dst_cap), nout + 1 entries
+extern "C" int jfs_launch_gather_prefix(const jfs_compact_out *d_out, int nout, int32_t *d_tile_first,
+                                        hipStream_t stream) {
+    using namespace jfs::compact;
+    if (nout < 0) return -1;
+    hipLaunchKernelGGL(gather_prefix_kernel, dim3(1), dim3(LANES), 0, stream, d_out, nout, d_tile_first);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// plan (verdicts into d_ret) and the copy on the flat grid.  d_tile_first: the
+// device copy of the tile prefix (nout + 1 entries); ntiles: its last entry, a
+// host value (it sizes the launch).
+extern "C" int jfs_launch_gather_flat(const jfs_dev_block *d_src, const int32_t *d_src_n, int nsrc,
+                                      const jfs_compact_out *d_out, int nout, const jfs_compact_seg *d_seg,
+                                      int32_t *d_ret, const int32_t *d_tile_first, int64_t ntiles,
+                                      hipStream_t stream) {
+    using namespace jfs::compact;
+    if (nout <= 0) return 0;
+    if (ntiles < 0 || ntiles > INT32_MAX) return -1;
+    hipLaunchKernelGGL(gather_plan_kernel, dim3(nout), dim3(LANES), 0, stream, d_src, d_src_n, nsrc, d_out, d_seg, d_ret,
+                       0);
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (ntiles == 0) return 0;
+    hipLaunchKernelGGL(gather_copy_flat_kernel, dim3((unsigned)ntiles), dim3(LANES), 0, stream, d_src, d_out, nout, d_seg,
+                       d_ret, d_tile_first);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+extern "C" int jfs_launch_verify_gate(const uint32_t *d_crc, const int32_t *d_lens, const uint32_t *d_expect, int n,
+                                      int ndec, int32_t *d_src_n, uint32_t *d_crc_got, hipStream_t stream) {
+    using namespace jfs::compact;
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(verify_gate_kernel, dim3((unsigned)((n + LANES - 1) / LANES)), dim3(LANES), 0, stream, d_crc,
+                       d_lens, d_expect, n, ndec, d_src_n, d_crc_got);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }

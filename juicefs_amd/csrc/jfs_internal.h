@@ -86,6 +86,21 @@ int jfs_launch_gather(const jfs_dev_block *d_src, const int32_t *d_src_n, int ns
 // sealed compaction: d_src_n[i] = d_open_ret[i] where the AEAD open of source i
 // failed (d_open_ret[i] < 0), so the gather counts it as a failed source
 int jfs_launch_chain_merge(const int32_t *d_open_ret, int nsrc, int32_t *d_src_n, hipStream_t stream);
+// src_n value of a read source whose CRC-32C did not match (compact.hip, verify_gate_kernel)
+#define JFS_CHECKSUM_FAILED (-2147483647)
+// the read path's gather (compact.hip): verdicts and the copy on a one-dimensional
+// grid over d_tile_first, the running sum of jfs_gather_tiles(dst_cap) (nout + 1
+// entries; ntiles = its last entry on the host).  jfs_launch_gather_prefix
+// builds it on the device from d_out.
+int64_t jfs_gather_tiles(int64_t cap);
+int jfs_launch_gather_prefix(const jfs_compact_out *d_out, int nout, int32_t *d_tile_first, hipStream_t stream);
+int jfs_launch_gather_flat(const jfs_dev_block *d_src, const int32_t *d_src_n, int nsrc, const jfs_compact_out *d_out,
+                           int nout, const jfs_compact_seg *d_seg, int32_t *d_ret, const int32_t *d_tile_first,
+                           int64_t ntiles, hipStream_t stream);
+// read path: d_crc_got[i] = d_crc[i] where d_lens[i] > 0 (an expected CRC exists) else 0;
+// a mismatch with d_expect[i] writes JFS_CHECKSUM_FAILED over d_src_n[i] (i < ndec)
+int jfs_launch_verify_gate(const uint32_t *d_crc, const int32_t *d_lens, const uint32_t *d_expect, int n, int ndec,
+                           int32_t *d_src_n, uint32_t *d_crc_got, hipStream_t stream);
 int jfs_launch_gen(uint8_t *d_dst, int nblk, int64_t block_bytes, char cls, uint64_t seed_base,
                    const uint8_t *d_vocab, hipStream_t stream);
 }

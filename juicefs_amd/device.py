@@ -238,6 +238,20 @@ def gather(src_desc: torch.Tensor, src_n: torch.Tensor, out_desc: torch.Tensor, 
            "jfs_gather_device")
 
 
+def read_gather(src_desc: torch.Tensor, src_n: torch.Tensor, out_desc: torch.Tensor, seg: torch.Tensor, dst_caps,
+                ret: torch.Tensor, stream=None):
+    """jfs_read_gather_device: gather()'s contract on the flat grid, for
+    outputs of very different sizes; dst_caps = the outputs' dst_cap on the host."""
+    ns = src_desc.numel() // DESC_DTYPE.itemsize
+    no = out_desc.numel() // COMPACT_OUT_DTYPE.itemsize
+    caps = np.ascontiguousarray(dst_caps, dtype=np.int32)
+    if caps.size != no:
+        raise ValueError("one dst_cap per output")
+    _check(L.load().jfs_read_gather_device(src_desc.data_ptr(), src_n.data_ptr(), ns, out_desc.data_ptr(),
+                                           caps.ctypes.data, no, seg.data_ptr(), ret.data_ptr(),
+                                           _stream_ptr(stream)), "jfs_read_gather_device")
+
+
 def lz4_compact(src_desc: torch.Tensor, src_ret: torch.Tensor, gather_desc: torch.Tensor, seg: torch.Tensor,
                 enc_desc: torch.Tensor, max_dst_cap: int, ret: torch.Tensor, stream=None):
     """Fused LZ4 decode -> gather -> LZ4 encode (jfs_lz4_compact_device)."""

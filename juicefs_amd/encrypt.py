@@ -19,7 +19,7 @@ from __future__ import annotations
 import ctypes
 
 from . import _lib as L
-from .compress import CompressError, _addr, _err
+from .compress import CompressError, _addr, _err, _read_call
 
 AES256GCM_RSA = "aes256gcm-rsa"
 CHACHA20_RSA = "chacha20-rsa"
@@ -202,3 +202,16 @@ def compact_seal_batch(codec: int, algo: str, sources, keys, outputs, params, pl
     if with_crc:
         return src_res, out_res, [int(crc[j]) for j in range(no)]
     return src_res, out_res
+
+
+def read_open_batch(codec: int, algo: str, sources, keys, reads, plan, crcs=None, device_mask: int = 0):
+    """Read assembly of an encrypted volume on one GPU (jfs_read_open_batch):
+    Compressor.ReadBatch with open_decompress_batch in front.  sources:
+    [(envelope, block_size)], keys: [data key] (one per source); reads, plan,
+    crcs and the result as for ReadBatch -- the expected CRC-32C covers the
+    whole envelope, and a source that does not authenticate is a failed
+    source."""
+    if len(keys) != len(sources):
+        raise ValueError("one key per source")
+    _check_keys(algo, keys, None)
+    return _read_call(codec, cipher_id(algo), sources, keys, reads, plan, crcs, device_mask)
