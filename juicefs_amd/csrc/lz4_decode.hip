@@ -30,6 +30,7 @@
 
 #include "jfs_internal.h"
 #include "lz4_put16.h"
+#include "lz4_tailpack.h"
 #include "wave.cuh"
 
 namespace jfs {
@@ -71,6 +72,7 @@ constexpr int LMAX = 64;               // longer literal runs / matches are copi
 constexpr int BSPAN = 2048;            // max output span of one lane-parallel batch
 static_assert(BSPAN + FLUSH_T + 128 <= R, "ring must hold the unflushed tail plus one batch");
 static_assert(R - BSPAN >= LMAX + 16, "far sources must lie below the flushed prefix");
+static_assert(R == (int)TP_RING && LMAX <= (int)TP_LEN_MAX, "tail_pack field widths (lz4_tailpack.h)");
 
 #ifdef JFS_PROF
 // diagnostic build only: per-phase cycle sums (s_memtime), never in the product .so
@@ -379,7 +381,9 @@ __device__ __forceinline__ void direct_lit(Smem &s, Ctx &c, int32_t srcpos, int3
 }
 
 __device__ __forceinline__ void coop_lit(Smem &s, Ctx &c, int32_t srcpos, int32_t op, int32_t len) {
-    const int l = lane_id();
+    // opaque: l + dmis is not hoisted out of the copier's loops (a VGPR live through batch())
+    int l = lane_id();
+    asm volatile("" : "+v"(l));
     if (len >= LIT_DIRECT) {
         const int32_t body = op + len - R;
         direct_lit(s, c, srcpos, op, body);
@@ -434,7 +438,9 @@ __device__ __forceinline__ int32_t direct_fill(Smem &s, Ctx &c, int32_t op, int3
 }
 
 __device__ __forceinline__ void coop_match(Smem &s, Ctx &c, int32_t op, int32_t off, int32_t len) {
-    const int l = lane_id();
+    // opaque: l + dmis is not hoisted out of the copier's loops (a VGPR live through batch())
+    int l = lane_id();
+    asm volatile("" : "+v"(l));
     if (len >= LIT_DIRECT && off > 0 && off <= 16 && (16 % off) == 0) {
         const int32_t b = direct_fill(s, c, op, off, len);
         len -= b - op;
@@ -677,27 +683,27 @@ __device__ __forceinline__ void copy16(Smem &s, uint32_t sa, uint32_t da, int32_
 }
 
 
-// Whole-wave copy of len bytes to output op from output op - D (all inside the
-// ring), in chunks of at most D bytes so that self-overlapping matches repeat
-// their period; plain byte stores (the bytes are not written by anyone else).
-// WRAP = false: the destination does not cross the ring's end; when the source
-// does not either (a scalar test per match) both slots are computed once and
+// Whole-wave copy of len bytes to ring slot ds from ring slot ss, D = ds - ss
+// (mod R, 1 <= D < R) bytes before it, in chunks of at most D bytes so that
+// self-overlapping matches repeat their period; plain byte stores (the bytes are not written by
+// anyone else).  WRAP = false: the destination does not cross the ring's end;
+// when the source does not either (a scalar test per match) the slots are
 // stepped by an add.
 template <bool WRAP>
-__device__ __forceinline__ void wave_near(Smem &s, const Ctx &c, int32_t op, int32_t D, int32_t len) {
+__device__ __forceinline__ void wave_near(Smem &s, uint32_t ds, uint32_t ss, int32_t len) {
     const int l = lane_id();
+    const int32_t D = (int32_t)((ds - ss) & RMASK);
     const int32_t step = D < 64 ? D : 64;
-    const uint32_t ss = slot(c, op - D);
     if (!WRAP && ss + (uint32_t)len <= (uint32_t)R) {
-        const int32_t back = (int32_t)ss - (int32_t)slot(c, op);
-        uint8_t *d = s.ring + slot(c, op) + l;
+        const int32_t back = (int32_t)ss - (int32_t)ds;
+        uint8_t *d = s.ring + ds + l;
         for (int32_t left = len; left > 0; left -= step, d += step)
             if (l < (left < step ? left : step)) d[0] = d[back];
         return;
     }
     for (int32_t k = 0; k < len; k += step) {
         const int32_t i = k + l;
-        if (l < step && i < len) s.ring[slot(c, op + i)] = s.ring[slot(c, op + i - D)];
+        if (l < step && i < len) s.ring[(ds + (uint32_t)i) & RMASK] = s.ring[(ds + (uint32_t)(i - D)) & RMASK];
     }
 }
 // Whole-wave copy of literal bytes [from, len) of a run staged at cw + litr.
@@ -837,11 +843,21 @@ __device__ __forceinline__ void batch(Smem &s, Ctx &c, bool act, int32_t o, uint
                 if (rem <= 0) pend = false;
             }
         }
-        for (uint64_t pmk = __ballot(pend); pmk; pmk &= pmk - 1) {
+        // one lane read per match: slots, length and whether the match is a
+        // single chunk that crosses the ring's end on neither side, all
+        // computed by the lanes once per batch (every source is >= hz, so
+        // D < R and wave_near recovers it from the two slots)
+        const uint32_t tw = tail_pack(dslot(pos), slot(c, pos - D), (uint32_t)rem, (uint32_t)D);
+        for (uint64_t pmk = __ballot(pend); pmk;) {
             const int j = (int)__builtin_ctzll(pmk);
+            pmk &= ~(1ull << j);
             PCOUNT(19, 1);
-            wave_near<WRAP>(s, c, (int32_t)readlane((uint32_t)pos, j), (int32_t)readlane((uint32_t)D, j),
-                      (int32_t)readlane((uint32_t)rem, j));
+            const uint32_t w = readlane(tw, j);
+            if (tail_direct(w)) {
+                if ((uint32_t)lane_id() < tail_rem(w)) s.ring[tail_ds(w) + lane_id()] = s.ring[tail_ss(w) + lane_id()];
+            } else {
+                wave_near<WRAP>(s, tail_ds(w), tail_ss(w), (int32_t)tail_rem(w));
+            }
         }
     }
     PSTAMP(6);
