@@ -202,6 +202,33 @@ int64_t jfs_lz4_decompress_device(const jfs_dev_block *d_blocks, int nblk, int32
  * ~128-192 blocks of 4 MiB; jfs_lz4_decompress_device is faster for large batches. */
 int64_t jfs_lz4_decompress_device_small(const jfs_dev_block *d_blocks, const int32_t *src_len, const int32_t *dst_cap,
                                         int nblk, int32_t *d_ret, void *stream);
+/* Prefix decode: block i is decoded only as far as its first d_want[i] bytes
+ * (an LZ4_decompress_safe_partial-style stop; a 128 KiB read out of a 4 MiB
+ * block need not pay for 4 MiB of decode).  d_want is a device array of nblk
+ * int32.  For a stream let `size` be what jfs_lz4_decompress_device returns
+ * for it and q the output position at which the first sequence it rejects
+ * begins (q = infinity for a stream it accepts).
+ *   Well-formed stream (size >= 0): ret = min(size, want), and dst[0, ret)
+ *     equals the first ret bytes of the full decode.
+ *   Rejected stream, want > q: ret = size, the same negative value; everything
+ *     up to the faulty sequence was decoded identically with the same dst_cap.
+ *   Rejected stream, want <= q: ret is either that negative value or want; if
+ *     it is want, dst[0, want) holds the bytes the sequences in front of the
+ *     fault define.  Which of the two is unspecified (the two paths cut at
+ *     different granularity); a caller that needs the whole object validated
+ *     uses the CRC-32C check or the full decoders.
+ * Bytes of dst[ret, dst_cap) are unspecified; nothing outside dst[0, dst_cap)
+ * is ever written; the small-batch call, for a block it decodes itself, writes
+ * nothing at or above ret.  want <= 0 gives 0, after the early answers of the
+ * full decoders (NULL src, src_len == 0, dst_cap == 0 keep their results);
+ * want > dst_cap acts as dst_cap.  Asynchronous on `stream`.  The _small form
+ * is jfs_lz4_decompress_device_small's (host copies of the sizes, the same
+ * per-device scratch and its rules); jfs_lz4_split_counts counts its blocks. */
+int64_t jfs_lz4_decompress_prefix_device(const jfs_dev_block *d_blocks, const int32_t *d_want, int nblk,
+                                         int32_t *d_ret, void *stream);
+int64_t jfs_lz4_decompress_prefix_device_small(const jfs_dev_block *d_blocks, const int32_t *src_len,
+                                               const int32_t *dst_cap, const int32_t *d_want, int nblk,
+                                               int32_t *d_ret, void *stream);
 /* Diagnostics for the small-batch path (used by it, by jfs_decompress and by
  * small jfs_decompress_batch calls), six counters: out[0] = blocks it decoded
  * itself, out[1] = blocks it handed to the one-workgroup kernel (inputs outside
@@ -509,6 +536,31 @@ int64_t jfs_read_open_batch(int algo, int cipher, int nsrc, const jfs_iov *src, 
                             const int64_t *src_crc /* may be NULL */, int nout, const jfs_iov *out,
                             const int32_t *seg_first /* nout+1 */, const jfs_compact_seg *seg, int64_t *src_n,
                             int64_t *out_n, uint32_t *crc_got /* nsrc, may be NULL */, uint32_t device_mask);
+
+/* Decode mode of jfs_read_batch and jfs_read_open_batch.  JFS_READ_DECODE_FULL
+ * (default) decodes every source whole: the calls are what they were before
+ * the mode existed, byte for byte and result for result.
+ * JFS_READ_DECODE_PREFIX stops each LZ4 decode at the last byte a read needs:
+ * per source, need = max(src_off + len) over the segments that reference it
+ * (0 for a source nothing references), clamped to its dst_cap, is passed to
+ * the prefix decoders above as `want`.  Then, for LZ4, src_n[i] = min(size,
+ * need), or the error as the prefix decoders define it (a fault behind `need`
+ * may go unseen); the checksum, open and host-answered verdicts keep their
+ * precedence, out_n and the output bytes are those of full mode for every read
+ * whose sources are well-formed, and a source too short for a segment still
+ * fails that read (JFS_ERR_CORRUPT).  A call in which every source is needed to
+ * its dst_cap takes the full decoders.  Zstd and "none" decode whole in either
+ * mode, with full mode's src_n.  jfs_stats' bytes_out counts src_n.  The
+ * compaction calls do not consult the mode.
+ * The initial value is read once from JFS_READ_DECODE = "full" | "prefix"
+ * (case-insensitive; anything else, or unset: full).
+ * jfs_set_read_decode_mode returns the previous mode, or -1 for an unknown
+ * value (which changes nothing); it is atomic and applies to calls that start
+ * afterwards. */
+#define JFS_READ_DECODE_FULL 0
+#define JFS_READ_DECODE_PREFIX 1
+int jfs_read_decode_mode(void);
+int jfs_set_read_decode_mode(int mode);
 
 /* ---- Runtime / utilities ------------------------------------------------- */
 

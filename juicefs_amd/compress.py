@@ -279,6 +279,25 @@ def zstd_parse_mode(mode: str):
         lib.jfs_set_zstd_parse_mode(prev)
 
 
+_READ_DECODE = {"full": L.READ_DECODE_FULL, "prefix": L.READ_DECODE_PREFIX}
+
+
+def read_decode_mode() -> str:
+    """The decode mode of the read calls (jfs_read_decode_mode): "full", or
+    "prefix" -- every LZ4 decode stops at the last byte a read needs."""
+    m = L.load().jfs_read_decode_mode()
+    return next(k for k, v in _READ_DECODE.items() if v == m)
+
+
+def set_read_decode_mode(mode: str) -> str:
+    """Set it (process-wide, for calls that start afterwards) and return the
+    previous mode's name."""
+    if mode not in _READ_DECODE:
+        raise ValueError(f"read decode mode {mode!r}: expected 'full' or 'prefix'")
+    prev = L.load().jfs_set_read_decode_mode(_READ_DECODE[mode])
+    return next(k for k, v in _READ_DECODE.items() if v == prev)
+
+
 def zstd_fast_seqs(src, device_ptr: int | None = None):
     """The fast Zstd parse's sequence records (test infrastructure): per 128 KiB
     block of src a (records, nl) pair, records = [(ll, ml, Offset_Value)] and

@@ -300,6 +300,18 @@ std::atomic<int> &lz4_parse() {
 }
 inline bool lz4_fast_mode() { return lz4_parse().load(std::memory_order_relaxed) == JFS_LZ4_PARSE_FAST; }
 
+// JFS_READ_DECODE (include/jfs_gpucodec.h): full (default) | prefix
+std::atomic<int> &read_decode() {
+    static std::atomic<int> m{[] {
+        const char *e = getenv("JFS_READ_DECODE");
+        if (!e) return JFS_READ_DECODE_FULL;
+        std::string v(e);
+        for (auto &ch : v) ch = (char)tolower((unsigned char)ch);
+        return v == "prefix" ? JFS_READ_DECODE_PREFIX : JFS_READ_DECODE_FULL;
+    }()};
+    return m;
+}
+
 // JFS_ZSTD_PARSE (include/jfs_gpucodec.h): exact (default) | fast
 std::atomic<int> &zstd_parse() {
     static std::atomic<int> m{[] {
@@ -830,6 +842,18 @@ int64_t launch_lz4_decode(Slot &sl, const jfs_dev_block *h_desc, const jfs_dev_b
     if (!sl.ensure_split(lz4_decode_scratch(n, lens.data(), caps.data()))) return JFS_ERR_NO_MEMORY;
     const jfs_plan::Lz4SplitGeom g = jfs_plan::lz4_split_geom(n, lens.data(), caps.data());
     return launch_rc(jfs_launch_lz4_split(d_desc, n, d_ret, sl.sp, g.nseg, g.max_cap, g.norg, st));
+}
+// The same choice for a prefix decode: block k stops at d_want[k] output bytes
+// (max_want: the largest of them, known on the host).  The scratch is
+// lz4_decode_scratch's.
+int64_t launch_lz4_decode_prefix(Slot &sl, const jfs_dev_block *h_desc, const jfs_dev_block *d_desc, int n,
+                                 int32_t *d_ret, const int32_t *d_want, int64_t max_want, hipStream_t st) {
+    if (n > split_max()) return launch_rc(jfs_launch_lz4_decode_prefix(d_desc, n, d_ret, d_want, nullptr, st));
+    const std::vector<int32_t> lens = desc_lens(h_desc, n), caps = desc_caps(h_desc, n);
+    if (!sl.ensure_split(lz4_decode_scratch(n, lens.data(), caps.data()))) return JFS_ERR_NO_MEMORY;
+    const jfs_plan::Lz4SplitGeom g = jfs_plan::lz4_split_geom(n, lens.data(), caps.data());
+    return launch_rc(
+        jfs_launch_lz4_split_prefix(d_desc, n, d_ret, d_want, sl.sp, g.nseg, g.max_cap, g.norg, max_want, st));
 }
 
 // One run_batch call: the chunk plan (batch_plan.h), every chunk's staging
@@ -2216,10 +2240,15 @@ struct ReadOut {
 // that area; the host copies the good reads out.  st[0, ns) are the decoded
 // sources; src_map as in compact_run.  Returns JFS_OK with src_n / out_n /
 // crc_got of these objects filled, or JFS_ERR_NO_MEMORY / JFS_ERR_HIP.
+// need (JFS_READ_DECODE_PREFIX with LZ4, else null): per object of the call,
+// the last byte a segment asks of it; the decode of source k stops there
+// (clamped to its capacity, staged behind the expected checksums in the same
+// H2D copy) unless every source is needed whole, which takes the full
+// launchers.
 int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src, const uint8_t *const *src_keys,
                  const std::vector<ReadSrc> &st, int ns, const std::vector<int> &src_map, const jfs_iov *out,
                  const std::vector<ReadOut> &oo, const int32_t *seg_first, const jfs_compact_seg *seg, int64_t *src_n,
-                 int64_t *out_n, uint32_t *crc_got) {
+                 int64_t *out_n, uint32_t *crc_got, const int64_t *need) {
     LaneRun scope(dev, ln, algo * 2 + DECOMPRESS, (uint64_t)st.size());
     const bool codec = algo != JFS_ALGO_NONE, sealed = cipher >= 0;
     const int n = (int)st.size(), no = (int)oo.size();
@@ -2246,6 +2275,19 @@ int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src
         if (ntiles > INT32_MAX) return JFS_ERR_NO_MEMORY;
     }
     tile_first[no] = (int32_t)ntiles;
+    std::vector<int32_t> want;
+    int64_t max_want = 0;
+    if (need && algo == JFS_ALGO_LZ4) {
+        bool whole = true;
+        want.resize(ns);
+        for (int k = 0; k < ns; k++) {
+            want[k] = (int32_t)std::min<int64_t>(need[st[k].idx], st[k].cap);
+            max_want = std::max<int64_t>(max_want, want[k]);
+            whole = whole && want[k] >= st[k].cap;
+        }
+        if (whole) want.clear();
+    }
+    const bool prefix = !want.empty();
     // staged area, mirrored pinned / HBM: [stored bytes | meta | results | packed reads]
     // meta: source descriptors (ns + 1: the last one is "a failed source"), the
     // plan, segments, tile prefix, the opens' descriptors and key | nonce cells,
@@ -2263,7 +2305,8 @@ int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src
     const int64_t o_seed = o_cd + align16(n * blk_b);
     const int64_t o_len = o_seed + align16((int64_t)n * 4);
     const int64_t o_exp = o_len + align16((int64_t)n * 4);
-    const int64_t o_srcn = o_exp + align16((int64_t)n * 4);
+    const int64_t o_want = o_exp + align16((int64_t)n * 4);
+    const int64_t o_srcn = o_want + (prefix ? align16((int64_t)ns * 4) : 0);
     const int64_t o_open = o_srcn + align16((int64_t)(ns + 1) * 4);
     const int64_t o_ret = o_open + align16((int64_t)ns * 4);
     const int64_t o_crc = o_ret + align16((int64_t)no * 4);
@@ -2285,6 +2328,7 @@ int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src
     const jfs_aead_block *d_sad = (const jfs_aead_block *)(d + o_sad);
     int32_t *d_srcn = (int32_t *)(d + o_srcn), *d_open = (int32_t *)(d + o_open), *d_ret = (int32_t *)(d + o_ret);
     memcpy(h + o_tf, tile_first.data(), (size_t)(no + 1) * 4);
+    if (prefix) memcpy(h + o_want, want.data(), (size_t)ns * 4);
     std::vector<CopyJob> jobs;
     for (int k = 0; k < n; k++) {
         const ReadSrc &s = st[k];
@@ -2341,7 +2385,10 @@ int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src
                                     (uint32_t *)(d + o_crc), ks);
     if (lk == 0 && sealed && ns > 0) lk = jfs_launch_aead(cipher, d_sad, ns, 1, d_open, nullptr, ks);
     if (lk == 0 && lz4 && ns > 0) {
-        lk = launch_lz4_decode(s1, h_sdesc, d_sdesc, ns, d_srcn, ks) == JFS_OK ? 0 : -1;
+        const int64_t r = prefix ? launch_lz4_decode_prefix(s1, h_sdesc, d_sdesc, ns, d_srcn,
+                                                            (const int32_t *)(d + o_want), max_want, ks)
+                                 : launch_lz4_decode(s1, h_sdesc, d_sdesc, ns, d_srcn, ks);
+        lk = r == JFS_OK ? 0 : -1;
     } else if (lk == 0 && algo == JFS_ALGO_ZSTD && ns > 0) {
         lk = jfs_launch_zstd_decode(d_sdesc, ns, d_srcn, nullptr, ks);  // plans its own scratch
     }
@@ -2804,6 +2851,30 @@ int64_t jfs_lz4_decompress_device_small(const jfs_dev_block *d_blocks, const int
                           });
 }
 
+int64_t jfs_lz4_decompress_prefix_device(const jfs_dev_block *d_blocks, const int32_t *d_want, int nblk,
+                                         int32_t *d_ret, void *stream) {
+    if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
+    if (nblk > 0 && !d_want) return JFS_ERR_INVALID;
+    stat_launch(JFS_ALGO_LZ4, DECOMPRESS, nblk);
+    return jfs_launch_lz4_decode_prefix(d_blocks, nblk, d_ret, d_want, nullptr, (hipStream_t)stream) == 0 ? JFS_OK
+                                                                                                          : JFS_ERR_HIP;
+}
+
+int64_t jfs_lz4_decompress_prefix_device_small(const jfs_dev_block *d_blocks, const int32_t *src_len,
+                                               const int32_t *dst_cap, const int32_t *d_want, int nblk,
+                                               int32_t *d_ret, void *stream) {
+    if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
+    if (nblk < 0 || (nblk > 0 && (!src_len || !dst_cap || !d_want))) return JFS_ERR_INVALID;
+    if (nblk == 0) return JFS_OK;
+    const jfs_plan::Lz4SplitGeom g = jfs_plan::lz4_split_geom(nblk, src_len, dst_cap);
+    // (want lives on the device only: the grids stay sized by the largest dst_cap)
+    return scratch_launch(g_split, DECOMPRESS, nblk, jfs_lz4_split_scratch_bytes(nblk, src_len, dst_cap), stream,
+                          [&](uint8_t *p, int64_t, hipStream_t st) {
+                              return jfs_launch_lz4_split_prefix(d_blocks, nblk, d_ret, d_want, p, g.nseg, g.max_cap,
+                                                                 g.norg, g.max_cap, st);
+                          });
+}
+
 int64_t jfs_lz4_compress_device_small(const jfs_dev_block *d_blocks, const int32_t *src_len, int nblk, int32_t *d_ret,
                                       void *stream) {
     if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
@@ -2851,6 +2922,13 @@ int64_t jfs_zstd_compress_fast_device(const jfs_dev_block *d_blocks, int nblk, i
     stat_launch(JFS_ALGO_ZSTD, COMPRESS, nblk);
     return jfs_launch_zstd_encode(d_blocks, nblk, d_ret, (hipStream_t)stream, JFS_ZSTD_PARSE_FAST) == 0 ? JFS_OK
                                                                                                         : JFS_ERR_HIP;
+}
+
+int jfs_read_decode_mode(void) { return read_decode().load(std::memory_order_relaxed); }
+
+int jfs_set_read_decode_mode(int mode) {
+    if (mode != JFS_READ_DECODE_FULL && mode != JFS_READ_DECODE_PREFIX) return -1;
+    return read_decode().exchange(mode);
 }
 
 int jfs_zstd_parse_mode(void) { return zstd_parse_now(); }
@@ -3227,13 +3305,21 @@ static int64_t read_call(int algo, int cipher, int nsrc, const jfs_iov *src, con
         else if (total[j] == 0) out_n[j] = 0;
         else oo.push_back({j, total[j]});
     }
+    // prefix mode (LZ4): the last byte the plan asks of every object
+    std::vector<int64_t> need;
+    if (algo == JFS_ALGO_LZ4 && read_decode().load(std::memory_order_relaxed) == JFS_READ_DECODE_PREFIX) {
+        need.assign(nsrc, 0);
+        for (int j = 0; j < nout; j++)
+            for (int k = seg_first[j]; k < seg_first[j + 1]; k++)
+                if (seg[k].src >= 0) need[seg[k].src] = std::max(need[seg[k].src], (int64_t)seg[k].src_off + seg[k].len);
+    }
     int64_t rc = JFS_OK;
     if (!st.empty() || !oo.empty()) {
         DevCtx *dev = ds[g_compact_turn.fetch_add(1) % ds.size()];
         std::unique_lock<std::mutex> lk;
         Lane &ln = dev->acquire_lane(lk, algo * 2 + DECOMPRESS);
         rc = read_run(dev, ln, algo, cipher, src, src_keys, st, ns, src_map, out, oo, seg_first, seg, src_n, out_n,
-                      crc_got);
+                      crc_got, need.empty() ? nullptr : need.data());
         if (rc == JFS_ERR_HIP) (void)lane_healthy(dev, ln);  // leave nothing in flight into the staging
     }
     if (rc != JFS_OK) {  // the chain did not run: every object it held reports why

@@ -68,6 +68,10 @@ int jfs_launch_lz4_decode_lens(const jfs_dev_block *d_blocks, int nblk, int32_t 
                                hipStream_t stream);
 int jfs_launch_lz4_decode_todo(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, const int32_t *d_todo,
                                hipStream_t stream);
+// the decode of block b stops at d_want[b] output bytes (lz4_decode_prefix.hip;
+// <= 0: the result is 0, above dst_cap: dst_cap); d_todo may be null
+int jfs_launch_lz4_decode_prefix(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, const int32_t *d_want,
+                                 const int32_t *d_todo, hipStream_t stream);
 // small-batch LZ4 decode (lz4_split.hip): compressed bytes per segment (one
 // lane each), scratch bytes for these blocks, and
 // the launch (nseg_all = sum of ceil(src_len / 256), max_cap = largest dst_cap,
@@ -76,6 +80,11 @@ int jfs_launch_lz4_decode_todo(const jfs_dev_block *d_blocks, int nblk, int32_t 
 int64_t jfs_lz4_split_scratch_bytes(int nb, const int32_t *src_len, const int32_t *cap);
 int jfs_launch_lz4_split(const jfs_dev_block *d_desc, int nb, int32_t *d_ret, void *d_scratch, int64_t nseg_all,
                          int64_t max_cap, int64_t norg_all, hipStream_t st);
+// the same with per-block d_want (as above); max_want: a host-side upper bound
+// of them, at most max_cap (max_cap where the host does not know them)
+int jfs_launch_lz4_split_prefix(const jfs_dev_block *d_desc, int nb, int32_t *d_ret, const int32_t *d_want,
+                                void *d_scratch, int64_t nseg_all, int64_t max_cap, int64_t norg_all, int64_t max_want,
+                                hipStream_t st);
 // ret value of a fused chain's second step when its first step failed
 #define JFS_CHAIN_FAILED (-2147483647 - 1)
 // compaction gather (compact.hip): verdicts into d_ret and the copy; merge != 0:

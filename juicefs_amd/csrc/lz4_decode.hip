@@ -1318,7 +1318,13 @@ __device__ __forceinline__ void parser_wave(Smem &s, Ctx &c PROF_ARG) {
     }
 }
 
-__device__ __forceinline__ void copier_wave(Smem &s, Ctx &c, int32_t *retp PROF_ARG) {
+// PREFIX: the decode stops once the output position reaches `want` (1 <= want
+// <= cap): the ring is flushed up to it and the result is `want`.  The stop is
+// tested where the copier knows its position anyway -- after a window's
+// copy_tokens and after every exact step -- so up to a window's output (or one
+// whole long token) beyond `want` may be written, never past cap.
+template <bool PREFIX>
+__device__ __forceinline__ void copier_wave(Smem &s, Ctx &c, int32_t *retp, int32_t want PROF_ARG) {
     __builtin_amdgcn_s_setprio(1);  // the copier is the critical wave of the pair (2 / 3: no better)
     Ser st;
     st.ip = 0;
@@ -1355,6 +1361,14 @@ __device__ __forceinline__ void copier_wave(Smem &s, Ctx &c, int32_t *retp PROF_
                     st.ip = (int32_t)(m.efin & ~STOP);
                     ser = (m.efin & STOP) != 0;
                 }
+                if constexpr (PREFIX) {
+                    if (st.op >= want) {  // enough output: no exact steps, the parser leaves on done
+                        ser = false;
+                        flush(s, c, st.op);
+                        result = want;
+                        done = 1;
+                    }
+                }
             } else {
                 ser = true;  // W_SER, or the window's start is not fast-path eligible
             }
@@ -1366,8 +1380,17 @@ __device__ __forceinline__ void copier_wave(Smem &s, Ctx &c, int32_t *retp PROF_
                     if (status != SER_CONT) {
                         if (status == SER_DONE) flush(s, c, st.op);
                         result = st.ret;
+                        if constexpr (PREFIX) result = st.ret > want ? want : st.ret;
                         done = 1;
                         break;
+                    }
+                    if constexpr (PREFIX) {
+                        if (st.op >= want) {
+                            flush(s, c, st.op);
+                            result = want;
+                            done = 1;
+                            break;
+                        }
                     }
                     if (++nser > (int64_t)c.n + 64) { c.bug |= 16; break; }
                     if (st.fast && st.ip < c.n - 64 && st.op < c.cap - 128) {
@@ -1412,10 +1435,17 @@ __device__ __forceinline__ void copier_wave(Smem &s, Ctx &c, int32_t *retp PROF_
 // previous kernel of a fused chain (AES-GCM open); < 0 = that step failed.
 // todo (optional): only the blocks with todo[b] != 0 are decoded (the others
 // were decoded by lz4_split.hip and keep its results).
+// PREFIX: one more array, wantp: wantp[b] output bytes are enough (copier_wave);
+// <= 0 answers 0 behind the early answers, above dst_cap means dst_cap.  The
+// array is a parameter of that instantiation alone (WANT = const int32_t *):
+// lz4_decode_kernel<false> keeps the five parameters and the code it had
+// before the switch existed.
+template <bool PREFIX, class... WANT>
 __global__ __launch_bounds__(128) JFS_LZ4_ATTR void lz4_decode_kernel(const jfs_dev_block *__restrict__ blocks, int nblk,
                                                         int32_t *__restrict__ ret,
                                                         const int32_t *__restrict__ lens,
-                                                        const int32_t *__restrict__ todo) {
+                                                        const int32_t *__restrict__ todo, WANT... wantp) {
+    static_assert(sizeof...(WANT) == (PREFIX ? 1 : 0), "the prefix instantiation takes want, the full one does not");
     __shared__ Smem s;
     const int b = blockIdx.x;
     if (b >= nblk) return;
@@ -1451,8 +1481,17 @@ __global__ __launch_bounds__(128) JFS_LZ4_ATTR void lz4_decode_kernel(const jfs_
         if (wave == 1 && lane_id() == 0) ret[b] = result;
         return;
     }
+    int32_t want = 0;
+    if constexpr (PREFIX) {
+        want = (int32_t)uniform((uint32_t)(wantp, ...)[b]);
+        if (want <= 0) {
+            if (wave == 1 && lane_id() == 0) ret[b] = 0;
+            return;
+        }
+        if (want > c.cap) want = c.cap;
+    }
     if (wave == 0) parser_wave(s, c PROF_PASS);
-    else copier_wave(s, c, ret + b PROF_PASS);
+    else copier_wave<PREFIX>(s, c, ret + b, want PROF_PASS);
 #ifdef JFS_PROF
     pr.flush_out();
 #endif
@@ -1461,6 +1500,13 @@ __global__ __launch_bounds__(128) JFS_LZ4_ATTR void lz4_decode_kernel(const jfs_
 }  // namespace lz4d
 }  // namespace jfs
 
+// The two instantiations are compiled in separate translation units: with
+// both in one module the compiler orders its inlining differently and emits
+// other code for lz4_decode_kernel<false> (four more instructions in the
+// copier; measured by diffing the assembly against the kernel before the
+// switch existed).  lz4_decode_prefix.hip includes this file with
+// JFS_LZ4_DECODE_PREFIX_TU set and gets the prefix launcher alone.
+#ifndef JFS_LZ4_DECODE_PREFIX_TU
 #ifdef JFS_PROF
 extern "C" int jfs_prof_read(uint64_t *out) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(jfs::lz4d::g_prof), sizeof(uint64_t) * NPROF) == hipSuccess ? 0 : -1;
@@ -1478,15 +1524,27 @@ extern "C" int jfs_launch_lz4_decode(const jfs_dev_block *d_blocks, int nblk, in
 extern "C" int jfs_launch_lz4_decode_lens(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, const int32_t *d_lens,
                                           hipStream_t stream) {
     if (nblk <= 0) return 0;
-    hipLaunchKernelGGL(jfs::lz4d::lz4_decode_kernel, dim3(nblk), dim3(128), 0, stream, d_blocks, nblk, d_ret, d_lens,
-                       (const int32_t *)nullptr);
+    hipLaunchKernelGGL(jfs::lz4d::lz4_decode_kernel<false>, dim3(nblk), dim3(128), 0, stream, d_blocks, nblk, d_ret,
+                       d_lens, (const int32_t *)nullptr);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 extern "C" int jfs_launch_lz4_decode_todo(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, const int32_t *d_todo,
                                           hipStream_t stream) {
     if (nblk <= 0) return 0;
-    hipLaunchKernelGGL(jfs::lz4d::lz4_decode_kernel, dim3(nblk), dim3(128), 0, stream, d_blocks, nblk, d_ret,
+    hipLaunchKernelGGL(jfs::lz4d::lz4_decode_kernel<false>, dim3(nblk), dim3(128), 0, stream, d_blocks, nblk, d_ret,
                        (const int32_t *)nullptr, d_todo);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+#else  // JFS_LZ4_DECODE_PREFIX_TU
+// The decode stops at d_want[b] output bytes (the PREFIX instantiation);
+// d_todo as above, or null for every block.
+extern "C" int jfs_launch_lz4_decode_prefix(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret,
+                                            const int32_t *d_want, const int32_t *d_todo, hipStream_t stream) {
+    if (nblk <= 0) return 0;
+    hipLaunchKernelGGL((jfs::lz4d::lz4_decode_kernel<true, const int32_t *>), dim3(nblk), dim3(128), 0, stream,
+                       d_blocks, nblk, d_ret, (const int32_t *)nullptr, d_todo, d_want);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+#endif  // JFS_LZ4_DECODE_PREFIX_TU

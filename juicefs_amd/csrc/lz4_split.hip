@@ -40,6 +40,15 @@
 // oend-5; the last sequence is literals only, ends exactly at iend and within
 // oend (literal-length bytes before iend-14).  Encoder output always meets
 // them; anything else takes the exact path.
+//
+// Prefix decode (jfs_launch_lz4_split_prefix): a block also carries `want`, the
+// output bytes its caller needs.  Origin pointers only point backwards, so the
+// entries of [0, want) never depend on one at or above want: spec, fix, count
+// and scan (which walk compressed bytes) run whole, emit writes only the
+// entries below want (a token that starts below want is still checked in
+// full, one that starts at or above it is not looked at), jump and gather run
+// over min(total, want) entries, and the result is that minimum.  The full
+// launcher is the same kernels with want = cap.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -59,6 +68,7 @@ struct SBlock {
     const uint8_t *src;
     uint8_t *dst;
     int32_t n, cap;
+    int32_t want;  // output bytes asked for, in [0, cap] (the full decode: cap)
     int32_t seg0, nseg;
     int64_t bits_off;  // dwords into the bitmap area
     int64_t org_off;   // entries into the origin area (multiple of 4)
@@ -176,8 +186,10 @@ __device__ __forceinline__ int block_of(const SBlock *blk, int nb, int g) {
 // descriptor asks for more than that budget leaves -- it would overrun the
 // segment or origin-map scratch -- is planned empty and marked bad, so the
 // exact one-workgroup kernel decodes it from its descriptor instead.
-__global__ void plan_kernel(const jfs_dev_block *__restrict__ desc, int nb, Scratch sc, int64_t nseg_all,
-                            int64_t max_cap, int64_t norg_all) {
+// want (null: the full decode) is clamped to [0, cap] and to max_want, the
+// bound the host sized the jump and gather grids with.
+__global__ void plan_kernel(const jfs_dev_block *__restrict__ desc, const int32_t *__restrict__ want, int nb,
+                            Scratch sc, int64_t nseg_all, int64_t max_cap, int64_t norg_all, int64_t max_want) {
     for (int i = threadIdx.x; i < nb * (int)(sizeof(BStat) / 4); i += blockDim.x) ((int32_t *)sc.st)[i] = 0;
     __syncthreads();
     if (threadIdx.x == 0 && blockIdx.x == 0) {
@@ -196,6 +208,8 @@ __global__ void plan_kernel(const jfs_dev_block *__restrict__ desc, int nb, Scra
                 s.cap = 0;
                 sc.st[b].bad = 1;
             }
+            const int64_t hi = s.cap < max_want ? (int64_t)s.cap : max_want, w = want ? (int64_t)want[b] : hi;
+            s.want = (int32_t)(w < 0 ? 0 : w < hi ? w : hi);
             s.seg0 = seg;
             s.nseg = (s.n + SEG - 1) / SEG;
             s.bits_off = bits;
@@ -373,6 +387,11 @@ __device__ __forceinline__ bool tok_ok(uint32_t tok, const Tok &t, int32_t n, in
 constexpr int EWV = T / 64;  // segments per workgroup
 constexpr int ESTG = 1024;   // compressed bytes staged per segment (its tokens' fields, mostly)
 constexpr int64_t EMIT_WAVE_MAX = 65536;  // segments (about 4 blocks of 4 MiB text)
+// PREFIX: only the origin entries below the block's `want` are written, and a
+// segment (or the rest of one) whose output starts at or above it is skipped
+// when the block is longer than want (cut).  A block that ends within want is
+// emitted whole, final token included: its last_ok is still required.
+template <bool PREFIX>
 __global__ __launch_bounds__(T) void emit_kernel(int nb, int nseg_all, Scratch sc) {
     __shared__ alignas(16) uint8_t stg[EWV][ESTG];
     const int l = lane_id();
@@ -389,6 +408,9 @@ __global__ __launch_bounds__(T) void emit_kernel(int nb, int nseg_all, Scratch s
                   k = g - (int32_t)uniform((uint32_t)B.seg0);
     const int32_t s0 = k * SEG, s1 = s0 + SEG < n ? s0 + SEG : n;
     int32_t x = (int32_t)uniform((uint32_t)sc.entry[g]), op = (int32_t)uniform((uint32_t)sc.cnt[g]);
+    const int32_t want = PREFIX ? (int32_t)uniform((uint32_t)B.want) : cap;
+    const bool cut = PREFIX && want < (int32_t)uniform((uint32_t)st.total);
+    if (cut && op >= want) return;
     // the parse reads the segment's bytes from LDS (one wave-uniform LDS round
     // trip per field instead of an L2 one); bytes past the staging from HBM
     uint8_t *buf = stg[threadIdx.x >> 6];
@@ -420,17 +442,19 @@ __global__ __launch_bounds__(T) void emit_kernel(int nb, int nseg_all, Scratch s
             return;
         }
         const uint32_t v0 = (uint32_t)(-(t.lenip) - 1);  // literal entry i = v0 - i
-        const int32_t ll = t.ll, ml = t.ml;
+        // (PREFIX: the entries below want; want - op <= 0 leaves none)
+        const int32_t ll = PREFIX ? min(t.ll, want - op) : t.ll;
         for (int32_t i = l; i < ll; i += 64) org[op + i] = v0 - (uint32_t)i;
         op += t.ll;
         if (t.last) {
             if (l == 0) st.last_ok = 1;
             return;
         }
+        const int32_t ml = PREFIX ? min(t.ml, want - op) : t.ml;
         // match entry i = op - off + (i mod off): overlapped matches point before the match
         const int32_t base = op - t.off;
         const uint32_t off = (uint32_t)t.off;
-        if (off >= (uint32_t)ml) {  // no overlap (most matches): no modulo
+        if (off >= (uint32_t)t.ml) {  // no overlap (most matches): no modulo
             for (int32_t i = l; i < ml; i += 64) org[op + i] = (uint32_t)(base + i);
         } else {
             for (int32_t i = l; i < ml; i += 64) {
@@ -440,12 +464,14 @@ __global__ __launch_bounds__(T) void emit_kernel(int nb, int nseg_all, Scratch s
         }
         op += t.ml;
         x = t.next;
+        if (cut && op >= want) return;
     }
 }
 
 // One THREAD per segment (large batches: 64 segments per wave do the most
 // work per instruction; the wave form above wins only while the segments are
 // too few to fill the GPU -- a 16-block chunk ran 20 % slower in it).
+template <bool PREFIX>
 __global__ __launch_bounds__(T) void emit_thread_kernel(int nb, int nseg_all, Scratch sc) {
     const int g = blockIdx.x * T + threadIdx.x;
     if (g >= nseg_all) return;
@@ -458,6 +484,9 @@ __global__ __launch_bounds__(T) void emit_thread_kernel(int nb, int nseg_all, Sc
     const int32_t n = B.n, cap = B.cap, k = g - B.seg0;
     const int32_t s0 = k * SEG, s1 = s0 + SEG < n ? s0 + SEG : n;
     int32_t x = sc.entry[g], op = sc.cnt[g];
+    const int32_t want = PREFIX ? B.want : cap;
+    const bool cut = PREFIX && want < st.total;
+    if (cut && op >= want) return;
     while (x < s1) {
         const Tok t = parse(s, n, x, true);
         const bool ok = tok_ok(t.tok, t, n, op, cap);
@@ -469,13 +498,14 @@ __global__ __launch_bounds__(T) void emit_thread_kernel(int nb, int nseg_all, Sc
         // area starts 16-byte aligned: org_off is a multiple of 4 entries)
         {
             const uint32_t v0 = (uint32_t)(-(t.lenip) - 1);  // entry i = v0 - i
+            const int32_t ll = PREFIX ? min(t.ll, want - op) : t.ll;  // (the entries below want)
             int32_t i = 0;
-            for (; i < t.ll && ((op + i) & 3); i++) org[op + i] = v0 - (uint32_t)i;
-            for (; i + 4 <= t.ll; i += 4) {
+            for (; i < ll && ((op + i) & 3); i++) org[op + i] = v0 - (uint32_t)i;
+            for (; i + 4 <= ll; i += 4) {
                 const uint32_t v = v0 - (uint32_t)i;
                 *(g_u4 *)(org + op + i) = make_uint4(v, v - 1u, v - 2u, v - 3u);
             }
-            for (; i < t.ll; i++) org[op + i] = v0 - (uint32_t)i;
+            for (; i < ll; i++) org[op + i] = v0 - (uint32_t)i;
         }
         op += t.ll;
         if (t.last) {
@@ -485,13 +515,14 @@ __global__ __launch_bounds__(T) void emit_thread_kernel(int nb, int nseg_all, Sc
         {
             const int32_t base = op - t.off;
             const uint32_t off = (uint32_t)t.off;
+            const int32_t ml = PREFIX ? min(t.ml, want - op) : t.ml;
             uint32_t j = 0;  // entry i = base + (i mod off)
             int32_t i = 0;
-            for (; i < t.ml && ((op + i) & 3); i++) {
+            for (; i < ml && ((op + i) & 3); i++) {
                 org[op + i] = (uint32_t)(base + j);
                 j = j + 1 == off ? 0u : j + 1;
             }
-            for (; i + 4 <= t.ml; i += 4) {
+            for (; i + 4 <= ml; i += 4) {
                 uint32_t e[4];
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
@@ -500,13 +531,14 @@ __global__ __launch_bounds__(T) void emit_thread_kernel(int nb, int nseg_all, Sc
                 }
                 *(g_u4 *)(org + op + i) = make_uint4(e[0], e[1], e[2], e[3]);
             }
-            for (; i < t.ml; i++) {
+            for (; i < ml; i++) {
                 org[op + i] = (uint32_t)(base + j);
                 j = j + 1 == off ? 0u : j + 1;
             }
         }
         op += t.ml;
         x = t.next;
+        if (cut && op >= want) return;
     }
 }
 
@@ -519,8 +551,8 @@ __global__ __launch_bounds__(T) void jump_kernel(Scratch sc, int round) {
     BStat &st = sc.st[b];
     if (st.fix[FIX_ROUNDS - 1] || st.bad) return;
     if (round > 0 && !st.jmp[round - 1]) return;
-    const int64_t total = st.total;
     const SBlock B = sc.blk[b];
+    const int64_t total = min(st.total, B.want);  // (the entries the emit wrote; the full decode: st.total)
     g_u32 *org = (g_u32 *)(sc.org + B.org_off);
     bool any = false;
     for (int64_t p = ((int64_t)blockIdx.x * T + threadIdx.x) * 4; p < total; p += (int64_t)gridDim.x * T * 4) {
@@ -562,16 +594,18 @@ __global__ void verdict_kernel(int nb, Scratch sc, int32_t *__restrict__ ret, in
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nb) return;
     BStat &st = sc.st[b];
-    const bool bad = st.bad || !st.last_ok || st.fix[FIX_ROUNDS - 1] || st.unsettled;
+    // (a block cut at want never reaches its final token: no last_ok to ask for)
+    const int32_t want = sc.blk[b].want;
+    const bool bad = st.bad || (!st.last_ok && st.total <= want) || st.fix[FIX_ROUNDS - 1] || st.unsettled;
     st.todo = bad;
     todo[b] = bad;
-    if (!bad) ret[b] = st.total;
+    if (!bad) ret[b] = min(st.total, want);
     atomicAdd(&g_split_counts[bad ? 1 : 0], 1ull);
     // why a block was handed over: fix-up / jumping did not converge, a token
     // outside the proven cases, no final literal run
     if (st.fix[FIX_ROUNDS - 1]) atomicAdd(&g_split_counts[2], 1ull);
     else if (st.bad) atomicAdd(&g_split_counts[4], 1ull);
-    else if (!st.last_ok) atomicAdd(&g_split_counts[5], 1ull);
+    else if (!st.last_ok && st.total <= want) atomicAdd(&g_split_counts[5], 1ull);
     else if (st.unsettled) atomicAdd(&g_split_counts[3], 1ull);
 }
 
@@ -580,11 +614,11 @@ __global__ void verdict_kernel(int nb, Scratch sc, int32_t *__restrict__ ret, in
 __global__ __launch_bounds__(T) void gather_kernel(Scratch sc) {
     const int b = blockIdx.y;
     BStat &st = sc.st[b];
-    if (st.bad || !st.last_ok || st.fix[FIX_ROUNDS - 1]) return;  // (entries not all written: never read)
-    const int64_t p = ((int64_t)blockIdx.x * T + threadIdx.x) * 4;
-    const int64_t total = st.total;
-    if (p >= total) return;
     const SBlock B = sc.blk[b];
+    if (st.bad || (!st.last_ok && st.total <= B.want) || st.fix[FIX_ROUNDS - 1]) return;  // (entries not all written: never read)
+    const int64_t p = ((int64_t)blockIdx.x * T + threadIdx.x) * 4;
+    const int64_t total = min(st.total, B.want);  // no byte at or above it is written
+    if (p >= total) return;
     const gc_u32 *org = (const gc_u32 *)(sc.org + B.org_off);
     const gc_u8 *s = (const gc_u8 *)B.src;
     g_u8 *d = (g_u8 *)B.dst;
@@ -628,10 +662,14 @@ extern "C" int64_t jfs_lz4_split_scratch_bytes(int nb, const int32_t *src_len, c
 
 // nseg_all / max_cap: Σ segments and the largest dst_cap (grid sizes); the
 // host computes both from the same (src_len, cap) it sized the scratch with.
-// d_todo (nb int32, optional): 1 for the blocks the exact kernel must redo.
-extern "C" int jfs_launch_lz4_split(const jfs_dev_block *d_desc, int nb, int32_t *d_ret, void *d_scratch,
-                                    int64_t nseg_all, int64_t max_cap, int64_t norg_all, hipStream_t st) {
+// d_want (null: the full decode): the output bytes asked for per block;
+// max_want: an upper bound of them on the host (at most max_cap), which sizes
+// the jump and gather grids -- the device values are clamped to it.
+template <bool PREFIX>
+static int launch_split(const jfs_dev_block *d_desc, int nb, int32_t *d_ret, const int32_t *d_want, void *d_scratch,
+                        int64_t nseg_all, int64_t max_cap, int64_t norg_all, int64_t max_want, hipStream_t st) {
     if (nb <= 0) return 0;
+    max_want = std::max<int64_t>(0, std::min(max_want, max_cap));
     uint8_t *p = (uint8_t *)(((uintptr_t)d_scratch + 255) & ~(uintptr_t)255);
     Scratch sc;
     sc.blk = (SBlock *)p;
@@ -650,8 +688,8 @@ extern "C" int jfs_launch_lz4_split(const jfs_dev_block *d_desc, int nb, int32_t
     p += a256(nb * 4);
     sc.org = (int32_t *)p;
     const int gs = (int)((nseg_all + T - 1) / T);
-    const dim3 gp((unsigned)((max_cap / 4 + T) / T), (unsigned)nb);
-    hipLaunchKernelGGL(plan_kernel, dim3(1), dim3(T), 0, st, d_desc, nb, sc, nseg_all, max_cap, norg_all);
+    const dim3 gp((unsigned)((max_want / 4 + T) / T), (unsigned)nb);
+    hipLaunchKernelGGL(plan_kernel, dim3(1), dim3(T), 0, st, d_desc, d_want, nb, sc, nseg_all, max_cap, norg_all, max_want);
     if (nseg_all > 0) {
         hipLaunchKernelGGL(spec_kernel, dim3(gs), dim3(T), 0, st, nb, (int)nseg_all, sc);
         for (int r = 0; r < FIX_ROUNDS; r++) hipLaunchKernelGGL(fix_kernel, dim3(gs), dim3(T), 0, st, nb, (int)nseg_all, sc, r);
@@ -662,27 +700,40 @@ extern "C" int jfs_launch_lz4_split(const jfs_dev_block *d_desc, int nb, int32_t
         // a wave per segment while that leaves the GPU short of waves (a lone
         // block: ~16 k segments), a thread per segment beyond
         if (nseg_all <= EMIT_WAVE_MAX)
-            hipLaunchKernelGGL(emit_kernel, dim3((unsigned)((nseg_all + EWV - 1) / EWV)), dim3(T), 0, st, nb, (int)nseg_all, sc);
+            hipLaunchKernelGGL(emit_kernel<PREFIX>, dim3((unsigned)((nseg_all + EWV - 1) / EWV)), dim3(T), 0, st, nb, (int)nseg_all, sc);
         else
-            hipLaunchKernelGGL(emit_thread_kernel, dim3((unsigned)gs), dim3(T), 0, st, nb, (int)nseg_all, sc);
+            hipLaunchKernelGGL(emit_thread_kernel<PREFIX>, dim3((unsigned)gs), dim3(T), 0, st, nb, (int)nseg_all, sc);
     }
     // jump grid: about 2,048 workgroups in all (every entry of a 4 MiB block
     // is covered after a few strides), at most one per 1,024 entries
-    const unsigned jx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((max_cap / 4 + T) / T, (2048 + nb - 1) / nb));
+    const unsigned jx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((max_want / 4 + T) / T, (2048 + nb - 1) / nb));
     // Rounds: after round r every entry points >= HOPS^r steps up its chain (or
     // to a literal), and a chain is at most one step per token (a step from a
     // token's match lands in an earlier token's output or in its own
-    // literals), i.e. <= max_cap / 4 + 1 steps: HOPS^jr above that settles
+    // literals), i.e. <= max_want / 4 + 1 steps: HOPS^jr above that settles
     // every well-formed block (8 rounds for 4 MiB; each idle launch cost ~6 us
     // of a lone decode).  The gather checks every entry regardless.
     int jr = 1;
-    for (double reach = HOPS; reach <= (double)max_cap / 4 + 1 && jr < JUMP_ROUNDS; reach *= HOPS) jr++;
+    for (double reach = HOPS; reach <= (double)max_want / 4 + 1 && jr < JUMP_ROUNDS; reach *= HOPS) jr++;
     for (int r = 0; r < jr; r++) hipLaunchKernelGGL(jump_kernel, dim3(jx, (unsigned)nb), dim3(T), 0, st, sc, r);
     hipLaunchKernelGGL(gather_kernel, gp, dim3(T), 0, st, sc);
     hipLaunchKernelGGL(verdict_kernel, dim3((nb + 63) / 64), dim3(64), 0, st, nb, sc, d_ret, todo);
     if (hipGetLastError() != hipSuccess) return -1;
     // the exact one-workgroup kernel for the flagged blocks (the others exit at once)
+    if (PREFIX) return jfs_launch_lz4_decode_prefix(d_desc, nb, d_ret, d_want, todo, st);
     return jfs_launch_lz4_decode_todo(d_desc, nb, d_ret, todo, st);
+}
+
+extern "C" int jfs_launch_lz4_split(const jfs_dev_block *d_desc, int nb, int32_t *d_ret, void *d_scratch,
+                                    int64_t nseg_all, int64_t max_cap, int64_t norg_all, hipStream_t st) {
+    return launch_split<false>(d_desc, nb, d_ret, nullptr, d_scratch, nseg_all, max_cap, norg_all, max_cap, st);
+}
+
+extern "C" int jfs_launch_lz4_split_prefix(const jfs_dev_block *d_desc, int nb, int32_t *d_ret, const int32_t *d_want,
+                                           void *d_scratch, int64_t nseg_all, int64_t max_cap, int64_t norg_all,
+                                           int64_t max_want, hipStream_t st) {
+    if (!d_want) return -1;
+    return launch_split<true>(d_desc, nb, d_ret, d_want, d_scratch, nseg_all, max_cap, norg_all, max_want, st);
 }
 
 // Diagnostics: blocks the small-batch path decoded itself (out[0]) and blocks

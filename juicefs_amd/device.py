@@ -63,6 +63,28 @@ def lz4_decompress_small(desc: torch.Tensor, ret: torch.Tensor, src_lens, dst_ca
            "jfs_lz4_decompress_device_small")
 
 
+def lz4_decompress_prefix(desc: torch.Tensor, want: torch.Tensor, ret: torch.Tensor, stream=None):
+    """jfs_lz4_decompress_prefix_device: block i is decoded as far as its first
+    want[i] bytes (want: an int32 device tensor, one entry per descriptor)."""
+    n = desc.numel() // DESC_DTYPE.itemsize
+    assert want.dtype == torch.int32 and want.numel() >= n
+    _check(L.load().jfs_lz4_decompress_prefix_device(desc.data_ptr(), want.data_ptr(), n, ret.data_ptr(),
+                                                     _stream_ptr(stream)), "jfs_lz4_decompress_prefix_device")
+
+
+def lz4_decompress_prefix_small(desc: torch.Tensor, want: torch.Tensor, ret: torch.Tensor, src_lens, dst_caps,
+                                stream=None):
+    """jfs_lz4_decompress_prefix_device_small: the same through the small-batch
+    path; src_lens / dst_caps are host copies of the descriptors' sizes."""
+    n = desc.numel() // DESC_DTYPE.itemsize
+    assert want.dtype == torch.int32 and want.numel() >= n
+    sl = (ctypes.c_int32 * max(n, 1))(*[int(x) for x in src_lens])
+    dc = (ctypes.c_int32 * max(n, 1))(*[int(x) for x in dst_caps])
+    _check(L.load().jfs_lz4_decompress_prefix_device_small(desc.data_ptr(), sl, dc, want.data_ptr(), n,
+                                                           ret.data_ptr(), _stream_ptr(stream)),
+           "jfs_lz4_decompress_prefix_device_small")
+
+
 def lz4_split_counts(reset: bool = False):
     """(blocks the small-batch path decoded itself, blocks it handed to the
     one-workgroup kernel, ... the reasons: fix-up, jumping, token, no last run)

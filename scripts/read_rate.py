@@ -9,7 +9,14 @@ out of 64 text-class source blocks x 4 MiB, on one GPU.
       blocks, then numpy slicing on the host -- with the two stage times;
   (c) the flat-grid gather kernel alone (jfs_read_gather_device) against the
       2-D grid (jfs_gather_device) on the same plan, sources already decoded
-      in HBM, under device events.
+      in HBM, under device events;
+  (d) --decode full|prefix [...]: jfs_read_batch (LZ4, no checksums) in each
+      listed decode mode (JFS_READ_DECODE), in the order given, on three
+      workloads: (a)'s 64 sources (the small-batch decoder), the same reads out
+      of 256 sources (more than JFS_LZ4_SPLIT_MAX: the one-workgroup kernel),
+      and 64 sources with every segment ending at its block's last byte
+      (need == dst_cap everywhere: prefix mode takes the full launchers).
+      --only-decode skips (a)-(c).
 
 Medians of --reps calls after --warmup calls, one process.  Needs a GPU;
 writes one JSON file."""
@@ -29,7 +36,8 @@ U = 4 << 20
 NSRC, NREAD, READ = 64, 256, 128 << 10
 
 
-def plan(seed=2025):
+def plan(seed=2025, nsrc=NSRC, tail=False):
+    """tail: every segment ends at its block's last byte, and the sources take turns"""
     rng = np.random.default_rng(seed)
     seg_first, seg = [0], []
     for _ in range(NREAD):
@@ -38,10 +46,63 @@ def plan(seed=2025):
         at = 0
         for end in cuts + [READ]:
             n = end - at
-            seg.append((int(rng.integers(0, NSRC)), int(rng.integers(0, U - n + 1)), at, n))
+            if tail:
+                seg.append((len(seg) % nsrc, U - n, at, n))
+            else:
+                seg.append((int(rng.integers(0, nsrc)), int(rng.integers(0, U - n + 1)), at, n))
             at = end
         seg_first.append(len(seg))
     return seg_first, seg
+
+
+def decode_modes(a, res):
+    """(d): ReadBatch (LZ4) per workload and decode mode"""
+    import torch
+    from juicefs_amd import compress as C
+    from juicefs_amd import device as D
+    dev = torch.device("cuda:0")
+    c = C.NewCompressor("lz4")
+    out = {}
+    for wname, nsrc, tail in (("sources_64", 64, False), ("sources_256", 256, False), ("tail_64", 64, True)):
+        raw_t = torch.empty(nsrc * U, dtype=torch.uint8, device=dev)
+        D.gen_blocks(raw_t, nsrc, U, "T", 7000)
+        torch.cuda.synchronize()
+        raw = raw_t.cpu().numpy()
+        del raw_t
+        seg_first, seg = plan(nsrc=nsrc, tail=tail)
+        want = [np.empty(READ, dtype=np.uint8) for _ in range(NREAD)]
+        slice_reads([raw[i * U:(i + 1) * U] for i in range(nsrc)], seg_first, seg, want)
+        sd = [bytearray(c.CompressBound(U)) for _ in range(nsrc)]
+        r = c.CompressBatch([(sd[i], raw[i * U:(i + 1) * U]) for i in range(nsrc)])
+        assert all(e is None for _, e in r)
+        srcs = [(bytes(sd[i][:r[i][0]]), U) for i in range(nsrc)]
+        need = [0] * nsrc
+        for src, so, _, n in seg:
+            need[src] = max(need[src], so + n)
+        dst = [np.empty(READ, dtype=np.uint8) for _ in range(NREAD)]
+        w = {"sources": nsrc, "segments": len(seg), "decoded_bytes_full": nsrc * U, "decoded_bytes_needed": sum(need)}
+        for mode in a.decode:
+            prev = C.set_read_decode_mode(mode)
+            try:
+                ms = []
+                for it in range(a.warmup + a.reps):
+                    t0 = time.perf_counter()
+                    sres, rres, _ = c.ReadBatch(srcs, dst, (seg_first, seg))
+                    t1 = time.perf_counter()
+                    assert all(e is None for _, e in sres + rres)
+                    if it == 0:
+                        assert [n for n, _ in sres] == (need if mode == "prefix" else [U] * nsrc)
+                        for j in range(NREAD):
+                            assert np.array_equal(dst[j], want[j]), (wname, mode, j)
+                    if it >= a.warmup:
+                        ms.append((t1 - t0) * 1e3)
+            finally:
+                C.set_read_decode_mode(prev)
+            w[mode] = {"read_batch_ms": med(ms), "min_ms": min(ms), "max_ms": max(ms)}
+        if "full" in w and "prefix" in w:
+            w["prefix_over_full"] = w["prefix"]["read_batch_ms"] / w["full"]["read_batch_ms"]
+        out[wname] = w
+    res["decode_modes"] = out
 
 
 def slice_reads(dec, seg_first, seg, outs):
@@ -59,6 +120,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--decode", nargs="+", choices=["full", "prefix"], default=["full"],
+                    help="decode modes of the read calls to measure in (d), in this order")
+    ap.add_argument("--only-decode", action="store_true", help="measure (d) alone")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "read_assembly", "read_rate.json"))
     a = ap.parse_args()
     import torch
@@ -67,6 +131,11 @@ def main():
     from juicefs_amd import _lib as L
     assert torch.cuda.is_available(), "read_rate.py measures on a GPU"
     dev = torch.device("cuda:0")
+    if a.only_decode:
+        res = {"shape": {"block_bytes": U, "reads": NREAD, "read_bytes": READ, "gathered_bytes": NREAD * READ},
+               "reps": a.reps, "warmup": a.warmup}
+        decode_modes(a, res)
+        return write(a, res)
     raw_t = torch.empty(NSRC * U, dtype=torch.uint8, device=dev)
     D.gen_blocks(raw_t, NSRC, U, "T", 7000)
     torch.cuda.synchronize()
@@ -171,6 +240,11 @@ def main():
         "mixed_grid2d_ms": med(grid2), "mixed_grid2d_min_ms": min(grid2), "mixed_grid2d_max_ms": max(grid2),
         "mixed_flat_over_grid2d": med(flat2) / med(grid2),
     }
+    decode_modes(a, res)
+    write(a, res)
+
+
+def write(a, res):
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
