@@ -34,6 +34,7 @@
 #include "../../include/jfs_gpucodec_test.h"
 #include "batch_plan.h"
 #include "blockgen.h"
+#include "chain_plan.h"
 #include "jfs_internal.h"
 
 #define JFS_VERSION "jfs-gpucodec 0.1.0 (gfx950)"
@@ -43,6 +44,7 @@ namespace {
 constexpr int64_t LZ4_MAX_INPUT = 0x7E000000;
 
 using jfs_plan::align16;
+using jfs_plan::envelope_parse;
 
 // JFS_HOST_TRACE=1: per-chunk host timings on stderr (diagnostics)
 bool host_trace() {
@@ -1713,14 +1715,19 @@ bool pre_answer(int algo, int dir, const jfs_iov &v, int64_t *res) {
     return false;
 }
 
+// the devices a call may use: those of device_mask (0: all)
+std::vector<DevCtx *> devices_in(uint32_t device_mask) {
+    std::vector<DevCtx *> ds;
+    for (DevCtx *d : devices())
+        if (device_mask == 0 || (d->id < 32 && (device_mask >> d->id) & 1u)) ds.push_back(d);
+    return ds;
+}
+
 // Deal the todo blocks over the selected devices, size-balanced
 // (plan_deal) and run them; ae_all (optional) is parallel to iov2.
 int64_t deal(int algo, int dir, const std::vector<int> &todo, const std::vector<jfs_iov> &iov2, int64_t *out_n,
              uint32_t mask, const Aead *ae_all, uint32_t *crc = nullptr, uint8_t *const *csum = nullptr) {
-    std::vector<DevCtx *> &all = devices();
-    std::vector<DevCtx *> ds;
-    for (DevCtx *d : all)
-        if (mask == 0 || (d->id < 32 && (mask >> d->id) & 1u)) ds.push_back(d);
+    const std::vector<DevCtx *> ds = devices_in(mask);
     if (ds.empty()) return JFS_ERR_NO_DEVICE;
     const size_t G = std::min(ds.size(), todo.size());
     struct Part {
@@ -1780,17 +1787,6 @@ int64_t deal(int algo, int dir, const std::vector<int> &todo, const std::vector<
     return JFS_OK;
 }
 
-int64_t envelope_parse(const uint8_t *src, int64_t n, int64_t *woff, int64_t *wlen, int64_t *noff, int64_t *nlen) {
-    if (!src || n < 3) return JFS_ERR_CORRUPT;  // "received encrypted text length is less than 3"
-    const int64_t kl = ((int64_t)src[0] << 8) + src[1], nl = src[2];
-    if (3 + kl + nl >= n) return JFS_ERR_CORRUPT;  // "malformed ciphertext"
-    if (woff) *woff = 3;
-    if (wlen) *wlen = kl;
-    if (noff) *noff = 3 + kl;
-    if (nlen) *nlen = nl;
-    return 3 + kl + nl;
-}
-
 // disk_cache_file.go checksum() of n bytes on the host (blocks answered
 // without the GPU: the "none" codec)
 void host_csum(const uint8_t *p, int64_t n, uint8_t *out) {
@@ -1825,603 +1821,357 @@ int64_t batch_common(int algo, int dir, int nblk, const jfs_iov *iov, int64_t *o
 }
 
 // ---------------------------------------------------------------------------
-// compaction: decode -> gather -> encode on one device (jfs_compact_batch)
+// the on-device chains, one device and one lane per call:
+//   compaction     (open ->) decode -> gather -> encode (-> seal)
+//                  jfs_compact_batch, jfs_compact_seal_batch
+//   read assembly  verify -> (open ->) decode -> gather
+//                  jfs_read_batch, jfs_read_open_batch
+// cipher < 0: no envelopes.  The planning arithmetic is chain_plan.h's.
 // ---------------------------------------------------------------------------
-// One source / output the device works on (the others were answered on the
-// host); idx = its position in the caller's arrays.
-struct CompactSrc {
-    int idx;
-    int64_t cap;  // staged decode capacity (staged_cap)
-};
-struct CompactOut {
-    int idx;
-    int64_t total;  // gathered bytes
-    int64_t cap;    // staged encode capacity
+using jfs_plan::ChainFlags;
+using jfs_plan::ChainLayout;
+using jfs_plan::ChainOut;
+using jfs_plan::ChainSrc;
+
+// One call's staging on its lane (the caller holds ln.mu).  Staging comes from
+// the lane's slots: slot 0's pinned/HBM pair (h / d, laid out by ChainLayout)
+// for what crosses the link, slot 0's device scratch for the decoded sources
+// and the gathered blocks, slots 1 and 2's for the small-batch encoder and
+// decoder.  The whole chain is a single pass on the lane's kernel stream.
+struct Chain {
+    int algo, cipher, ns, n, no;  // ns decoded sources of n staged objects, no outputs
+    bool codec, sealed, lz4;
+    jfs_plan::ChainOffsets off;
+    ChainLayout L;
+    Slot *sl, *s1;
+    uint8_t *h, *d;
+    hipStream_t ks;
+
+    template <class T>
+    T *host(int64_t o) const { return (T *)(h + o); }
+    template <class T>
+    T *dev(int64_t o) const { return (T *)(d + o); }
+    uint8_t *d_in(int k) const { return d + off.in[k]; }
+    uint8_t *d_out(int k) const { return d + L.out + off.out[k]; }
+    uint8_t *h_out(int k) const { return h + L.out + off.out[k]; }
+    // where output k is gathered: in front of an encoder in the scratch, else in place
+    uint8_t *gat(int k) const { return off.gat.empty() ? d_out(k) : sl->sp + off.gat[k]; }
 };
 
-// Runs the whole chain on one lane (the caller holds ln.mu) in a single pass
-// on the lane's kernel stream: compressed sources and the plan H2D, decode,
-// gather, encode, checksums, results D2H, then exactly the compressed bytes
-// D2H.  Staging comes from the lane's slots: slot 0's pinned/HBM pair for what
-// crosses the link, slot 0's device scratch for the decoded sources and the
-// gathered blocks, slots 1 and 2's for the small-batch encoder and decoder.
-// src_map[i]: source i's position in `ss`, or -1 (answered on the host: it
-// counts as failed).  Returns JFS_OK with src_n / out_n / crc of these blocks
-// filled, or JFS_ERR_NO_MEMORY / JFS_ERR_HIP with nothing filled.
-int64_t compact_run(DevCtx *dev, Lane &ln, int algo, const jfs_iov *src, const std::vector<CompactSrc> &ss,
-                    const std::vector<int> &src_map, const jfs_iov *out, const std::vector<CompactOut> &oo,
-                    const int32_t *seg_first, const jfs_compact_seg *seg, int64_t *src_n, int64_t *out_n,
-                    uint32_t *crc) {
-    LaneRun scope(dev, ln, algo * 2 + COMPRESS, (uint64_t)(ss.size() + oo.size()));
-    const bool codec = algo != JFS_ALGO_NONE;
-    const int ns = (int)ss.size(), no = (int)oo.size();
-    // staged area, mirrored pinned / HBM: [compressed sources | meta | compressed outputs]
-    // meta: source descriptors (ns + 1: the last one is "a failed source"),
-    // output plan, segments, encoder and checksum descriptors, then the three
-    // result arrays (source lengths, output results, checksums) back to back
-    std::vector<int64_t> in_off(ns), out_off(no), dec_off(ns), gat_off(no);
-    int64_t tin = 0, tout = 0, scratch = 0, nseg = 0;
-    int32_t max_total = 0;
-    for (int k = 0; k < ns; k++) {
-        in_off[k] = tin;
-        tin += align16(src[ss[k].idx].src_len);
-        if (codec) {
-            dec_off[k] = scratch;
-            scratch += align16(ss[k].cap);
-        }
-    }
-    for (int k = 0; k < no; k++) {
-        out_off[k] = tout;
-        tout += align16(oo[k].cap);
-        if (codec) {
-            gat_off[k] = scratch;
-            scratch += align16(oo[k].total);
-        }
-        nseg += seg_first[oo[k].idx + 1] - seg_first[oo[k].idx];
-        max_total = (int32_t)std::max<int64_t>(max_total, oo[k].total);
-    }
-    const int64_t o_sdesc = tin;
-    const int64_t o_plan = o_sdesc + align16((int64_t)(ns + 1) * (int64_t)sizeof(jfs_dev_block));
-    const int64_t o_seg = o_plan + align16((int64_t)no * (int64_t)sizeof(jfs_compact_out));
-    const int64_t o_enc = o_seg + align16(nseg * (int64_t)sizeof(jfs_compact_seg));
-    const int64_t o_cd = o_enc + align16((int64_t)no * (int64_t)sizeof(jfs_dev_block));
-    const int64_t o_srcn = o_cd + align16((int64_t)no * (int64_t)sizeof(jfs_dev_block));
-    const int64_t o_ret = o_srcn + align16((int64_t)(ns + 1) * 4);
-    const int64_t o_crc = o_ret + align16((int64_t)no * 4);
-    const int64_t o_out = o_crc + align16((int64_t)no * 4);
-    Slot &sl = ln.slot[0];
-    if (!sl.ensure(o_out + tout)) return JFS_ERR_NO_MEMORY;
-    if (codec && !sl.ensure_split(std::max<int64_t>(scratch, 16))) return JFS_ERR_NO_MEMORY;
-    uint8_t *h = sl.h, *d = sl.d;
-    jfs_dev_block *h_sdesc = (jfs_dev_block *)(h + o_sdesc), *h_enc = (jfs_dev_block *)(h + o_enc),
-                  *h_cd = (jfs_dev_block *)(h + o_cd);
-    jfs_compact_out *h_plan = (jfs_compact_out *)(h + o_plan);
-    jfs_compact_seg *h_seg = (jfs_compact_seg *)(h + o_seg);
-    int32_t *h_srcn = (int32_t *)(h + o_srcn), *h_ret = (int32_t *)(h + o_ret);
-    uint32_t *h_crc = (uint32_t *)(h + o_crc);
-    const jfs_dev_block *d_sdesc = (const jfs_dev_block *)(d + o_sdesc), *d_enc = (const jfs_dev_block *)(d + o_enc),
-                        *d_cd = (const jfs_dev_block *)(d + o_cd);
-    int32_t *d_srcn = (int32_t *)(d + o_srcn), *d_ret = (int32_t *)(d + o_ret);
-    std::vector<CopyJob> jobs;
-    for (int k = 0; k < ns; k++) {
-        const jfs_iov &v = src[ss[k].idx];
-        if (v.src_len > 0) jobs.push_back({h + in_off[k], v.src, v.src_len});
-        // "none": the stored object is the decoded block
-        uint8_t *dec = codec ? sl.sp + dec_off[k] : d + in_off[k];
-        h_sdesc[k] = jfs_dev_block{d + in_off[k], dec, (int32_t)v.src_len, (int32_t)(codec ? ss[k].cap : v.src_len)};
-        h_srcn[k] = codec ? -1 : (int32_t)v.src_len;  // a decoder overwrites it
-    }
-    h_sdesc[ns] = jfs_dev_block{nullptr, nullptr, 0, 0};
-    h_srcn[ns] = -1;
-    par_copy(jobs);
-    int64_t sg = 0;
-    for (int k = 0; k < no; k++) {
-        const int j = oo[k].idx;
-        const int cnt = seg_first[j + 1] - seg_first[j];
-        uint8_t *gat = codec ? sl.sp + gat_off[k] : d + o_out + out_off[k];
-        h_plan[k] = jfs_compact_out{gat, (int32_t)oo[k].total, (int32_t)sg, cnt, 0};
-        for (int q = 0; q < cnt; q++) {
-            jfs_compact_seg s = seg[seg_first[j] + q];
-            if (s.src >= 0) s.src = src_map[s.src] >= 0 ? src_map[s.src] : ns;
-            h_seg[sg + q] = s;
-        }
-        sg += cnt;
-        h_enc[k] = jfs_dev_block{gat, d + o_out + out_off[k], (int32_t)oo[k].total, (int32_t)oo[k].cap};
-        h_cd[k] = jfs_dev_block{d + o_out + out_off[k], nullptr, 0, 0};
-    }
-    // the small-batch LZ4 decoder and encoder run one after the other on the
-    // stream: they share slot 1's scratch, sized for both before anything is queued
-    Slot &s1 = ln.slot[1];
-    const bool lz4 = algo == JFS_ALGO_LZ4, fast = lz4_fast_mode();
-    {
-        int64_t need = 0;
-        if (lz4 && ns > 0) need = lz4_decode_scratch(ns, desc_lens(h_sdesc, ns).data(), desc_caps(h_sdesc, ns).data());
-        if (lz4 && no > 0) need = std::max(need, lz4_encode_scratch(no, desc_lens(h_enc, no).data(), fast));
-        if (need > 0 && !s1.ensure_split(need)) return JFS_ERR_NO_MEMORY;
-    }
-    hipStream_t ks = ln.s_k;
-    // one H2D: compressed sources, the plan and the preset result arrays
-    if (hipMemcpyAsync(d, h, (size_t)o_ret, hipMemcpyHostToDevice, ks) != hipSuccess) return JFS_ERR_HIP;
-    int lk = 0;
-    if (lz4 && ns > 0) {
-        lk = launch_lz4_decode(s1, h_sdesc, d_sdesc, ns, d_srcn, ks) == JFS_OK ? 0 : -1;
-    } else if (algo == JFS_ALGO_ZSTD && ns > 0) {
-        lk = jfs_launch_zstd_decode(d_sdesc, ns, d_srcn, nullptr, ks);  // plans its own scratch
-    }
-    const jfs_compact_out *d_plan = (const jfs_compact_out *)(d + o_plan);
-    const jfs_compact_seg *d_seg = (const jfs_compact_seg *)(d + o_seg);
-    if (lk == 0) lk = jfs_launch_gather(d_sdesc, d_srcn, ns + 1, d_plan, no, d_seg, max_total, d_ret, 0, ks);
-    if (lk == 0 && codec && no > 0) {
-        lk = lz4 ? (launch_lz4_encode(s1, h_enc, d_enc, no, d_ret, ks, fast) == JFS_OK ? 0 : -1)
-                 : launch_kernel(algo, COMPRESS, d_enc, no, d_ret, ks, zstd_parse_now());
-        // the encoder ran on every block: a failed gather's verdict replaces its result
-        if (lk == 0) lk = jfs_launch_gather(d_sdesc, d_srcn, ns + 1, d_plan, no, d_seg, max_total, d_ret, 1, ks);
-    }
-    if (lk == 0 && crc && no > 0)
-        lk = jfs_launch_crc32c_lens(d_cd, no, d_ret, nullptr, (uint32_t *)(d + o_crc), ks);
-    if (lk != 0 || hipMemcpyAsync(h + o_srcn, d + o_srcn, (size_t)(o_out - o_srcn), hipMemcpyDeviceToHost, ks) !=
-                       hipSuccess ||
-        hipStreamSynchronize(ks) != hipSuccess) {
-        (void)hipStreamSynchronize(ks);
-        return JFS_ERR_HIP;
-    }
-    // exactly the compressed bytes come back
-    for (int k = 0; k < no; k++) {
-        const int64_t n = h_ret[k];
-        if (n > 0 && hipMemcpyAsync(h + o_out + out_off[k], d + o_out + out_off[k], (size_t)n, hipMemcpyDeviceToHost,
-                                    ks) != hipSuccess) {
-            (void)hipStreamSynchronize(ks);
-            return JFS_ERR_HIP;
-        }
-    }
-    if (hipStreamSynchronize(ks) != hipSuccess) return JFS_ERR_HIP;
-    jobs.clear();
-    for (int k = 0; k < ns; k++)
-        src_n[ss[k].idx] = codec ? finish_result(algo, DECOMPRESS, h_srcn[k]) : (int64_t)h_srcn[k];
-    for (int k = 0; k < no; k++) {
-        const int j = oo[k].idx;
-        const int32_t raw = h_ret[k];
-        int64_t r;
-        if (raw == JFS_CHAIN_FAILED) r = JFS_ERR_CORRUPT;
-        else if (codec) r = finish_result(algo, COMPRESS, raw);
-        else r = raw >= 0 ? (int64_t)raw : JFS_ERR_INVALID;
-        out_n[j] = r;
-        if (crc) crc[j] = r >= 0 ? h_crc[k] : 0u;
-        if (r > 0) jobs.push_back({out[j].dst, h + o_out + out_off[k], r});
-    }
-    par_copy(jobs);
+// Lays the call out and sizes slot 0 for it: JFS_OK or JFS_ERR_NO_MEMORY.
+int64_t chain_open(Chain &c, Lane &ln, int algo, int cipher, const std::vector<ChainSrc> &st, int ns,
+                   const std::vector<ChainOut> &oo, const int32_t *seg_first, bool encode, bool out_crc, bool src_crc,
+                   bool prefix) {
+    c.algo = algo;
+    c.cipher = cipher;
+    c.ns = ns;
+    c.n = (int)st.size();
+    c.no = (int)oo.size();
+    c.codec = algo != JFS_ALGO_NONE;
+    c.sealed = cipher >= 0;
+    c.lz4 = algo == JFS_ALGO_LZ4;
+    c.off = jfs_plan::chain_offsets(st, ns, oo, c.codec, encode);
+    int64_t nseg = 0;
+    for (const ChainOut &o : oo) nseg += seg_first[o.idx + 1] - seg_first[o.idx];
+    c.L = ChainLayout(c.off.tin, ns, c.n, c.no, nseg, ChainFlags{c.sealed, encode, out_crc, src_crc, prefix});
+    c.sl = &ln.slot[0];
+    c.s1 = &ln.slot[1];
+    c.ks = ln.s_k;
+    if (!c.sl->ensure(c.L.out + c.off.tout)) return JFS_ERR_NO_MEMORY;
+    if (c.codec && !c.sl->ensure_split(std::max<int64_t>(c.off.scratch, 16))) return JFS_ERR_NO_MEMORY;
+    c.h = c.sl->h;
+    c.d = c.sl->d;
     return JFS_OK;
 }
 
-// ---------------------------------------------------------------------------
-// compaction of an encrypted volume: open -> decode -> gather -> encode -> seal
-// on one device (jfs_compact_seal_batch)
-// ---------------------------------------------------------------------------
-// One source / output the device works on, as CompactSrc / CompactOut.
-struct SealedSrc {
-    int idx;
-    int64_t off;   // sealed payload (ciphertext || tag) = src[off, off + pay)
-    int64_t noff;  // its 12-byte nonce inside the envelope header
-    int64_t pay;
-    int64_t cap;   // staged decode capacity
-};
-struct SealedOut {
-    int idx;
-    int64_t total;  // gathered bytes
-    int64_t bound;  // encoder capacity (the codec's bound of total); the payload area holds bound + 16
-    int64_t hdr;    // envelope header bytes
-};
+// fills 64-byte key | nonce cell `slot`; returns its device address
+uint8_t *chain_cell(const Chain &c, int slot, const uint8_t *key, const uint8_t *nonce) {
+    uint8_t *cell = c.h + c.L.kn + 64 * (int64_t)slot;
+    memcpy(cell, key, (size_t)jfs_cipher_key_size(c.cipher));
+    memcpy(cell + 32, nonce, 12);
+    return c.d + c.L.kn + 64 * (int64_t)slot;
+}
 
-// compact_run's chain with an AEAD open in front of the decoders and a seal
-// behind the encoders, still one pass on the lane's kernel stream: payloads,
-// keys and the plan H2D, open in place, decode, the opens' verdicts merged into
-// the source lengths, gather, encode into the envelope's payload area, seal in
-// place (lengths from the encoder on the device), checksums seeded with the
-// header's, results D2H, then exactly the sealed bytes D2H; the host writes
-// the headers.  Staging as compact_run.  Per-block results follow
-// BatchRun::finish's rules for sealed batches, so they equal
-// jfs_open_decompress_batch's and jfs_compress_seal_batch's.
-int64_t compact_seal_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src,
-                         const uint8_t *const *src_keys, const std::vector<SealedSrc> &ss,
-                         const std::vector<int> &src_map, const jfs_iov *out, const jfs_seal_param *out_p,
-                         const std::vector<SealedOut> &oo, const int32_t *seg_first, const jfs_compact_seg *seg,
-                         int64_t *src_n, int64_t *out_n, uint32_t *crc) {
-    LaneRun scope(dev, ln, algo * 2 + COMPRESS, (uint64_t)(ss.size() + oo.size()));
-    const bool codec = algo != JFS_ALGO_NONE;
-    const int ns = (int)ss.size(), no = (int)oo.size();
-    const int klen = jfs_cipher_key_size(cipher);
-    // staged area, mirrored pinned / HBM: [sealed source payloads | meta | sealed output payloads]
-    // meta: compact_run's descriptors, the AEAD descriptors of both sides, one
-    // 64-byte key | nonce cell per block, the checksum seeds and the preset
-    // source lengths; then what only the device writes: the opens' results,
-    // the outputs' results (encoder / gather, seal) and the checksums
-    std::vector<int64_t> in_off(ns), out_off(no), dec_off(ns), gat_off(no);
-    int64_t tin = 0, tout = 0, scratch = 0, nseg = 0;
-    int32_t max_total = 0;
-    for (int k = 0; k < ns; k++) {
-        in_off[k] = tin;
-        tin += align16(ss[k].pay);
-        if (codec) {
-            dec_off[k] = scratch;
-            scratch += align16(ss[k].cap);
+// The source side's staging: the stored bytes of every staged object (copy
+// jobs for the caller's par_copy), and for the ns decoded sources the open and
+// decode descriptors, key cells and preset lengths.
+void chain_stage_sources(const Chain &c, const jfs_iov *src, const uint8_t *const *src_keys,
+                         const std::vector<ChainSrc> &st, std::vector<CopyJob> &jobs) {
+    jfs_dev_block *h_sdesc = c.host<jfs_dev_block>(c.L.sdesc);
+    int32_t *h_srcn = c.host<int32_t>(c.L.srcn);
+    for (int k = 0; k < c.n; k++) {
+        const ChainSrc &s = st[k];
+        const jfs_iov &v = src[s.idx];
+        if (s.pay > 0) jobs.push_back({c.h + c.off.in[k], v.src + s.off, s.pay});
+        if (k >= c.ns) continue;  // staged for its checksum only
+        const int64_t plain = c.sealed ? s.pay - 16 : s.pay;  // sealed: pay >= 16, the host answered shorter ones
+        if (c.sealed) {
+            uint8_t *d_cell = chain_cell(c, k, src_keys[s.idx], v.src + s.noff);
+            // open in place over the staged payload; the codec reads the plaintext
+            c.host<jfs_aead_block>(c.L.sad)[k] =
+                jfs_aead_block{c.d_in(k), c.d_in(k), (int32_t)s.pay, (int32_t)s.pay, d_cell, d_cell + 32};
         }
+        // "none": the stored (opened) object is the decoded block
+        uint8_t *dec = c.codec ? c.sl->sp + c.off.dec[k] : c.d_in(k);
+        h_sdesc[k] = jfs_dev_block{c.d_in(k), dec, (int32_t)plain, (int32_t)(c.codec ? s.cap : plain)};
+        h_srcn[k] = c.codec ? -1 : (int32_t)plain;  // a decoder overwrites it
     }
-    for (int k = 0; k < no; k++) {
-        out_off[k] = tout;
-        tout += align16(oo[k].bound + 16);
-        if (codec) {
-            gat_off[k] = scratch;
-            scratch += align16(oo[k].total);
-        }
-        nseg += seg_first[oo[k].idx + 1] - seg_first[oo[k].idx];
-        max_total = (int32_t)std::max<int64_t>(max_total, oo[k].total);
-    }
-    const int64_t blk_b = (int64_t)sizeof(jfs_dev_block), aead_b = (int64_t)sizeof(jfs_aead_block);
-    const int64_t o_sdesc = tin;
-    const int64_t o_plan = o_sdesc + align16((ns + 1) * blk_b);
-    const int64_t o_seg = o_plan + align16((int64_t)no * (int64_t)sizeof(jfs_compact_out));
-    const int64_t o_enc = o_seg + align16(nseg * (int64_t)sizeof(jfs_compact_seg));
-    const int64_t o_cd = o_enc + align16(no * blk_b);
-    const int64_t o_sad = o_cd + align16(no * blk_b);
-    const int64_t o_oad = o_sad + align16(ns * aead_b);
-    const int64_t o_kn = o_oad + align16(no * aead_b);
-    const int64_t o_seed = o_kn + 64 * (int64_t)(ns + no);
-    const int64_t o_srcn = o_seed + align16((int64_t)no * 4);
-    const int64_t o_open = o_srcn + align16((int64_t)(ns + 1) * 4);
-    const int64_t o_ret = o_open + align16((int64_t)ns * 4);
-    const int64_t o_r2 = o_ret + align16((int64_t)no * 4);
-    const int64_t o_crc = o_r2 + align16((int64_t)no * 4);
-    const int64_t o_out = o_crc + align16((int64_t)no * 4);
-    Slot &sl = ln.slot[0];
-    if (!sl.ensure(o_out + tout)) return JFS_ERR_NO_MEMORY;
-    if (codec && !sl.ensure_split(std::max<int64_t>(scratch, 16))) return JFS_ERR_NO_MEMORY;
-    uint8_t *h = sl.h, *d = sl.d;
-    jfs_dev_block *h_sdesc = (jfs_dev_block *)(h + o_sdesc), *h_enc = (jfs_dev_block *)(h + o_enc),
-                  *h_cd = (jfs_dev_block *)(h + o_cd);
-    jfs_aead_block *h_sad = (jfs_aead_block *)(h + o_sad), *h_oad = (jfs_aead_block *)(h + o_oad);
-    jfs_compact_out *h_plan = (jfs_compact_out *)(h + o_plan);
-    jfs_compact_seg *h_seg = (jfs_compact_seg *)(h + o_seg);
-    uint32_t *h_seed = (uint32_t *)(h + o_seed);
-    int32_t *h_srcn = (int32_t *)(h + o_srcn);
-    const int32_t *h_open = (const int32_t *)(h + o_open), *h_ret = (const int32_t *)(h + o_ret),
-                  *h_r2 = (const int32_t *)(h + o_r2);
-    const uint32_t *h_crc = (const uint32_t *)(h + o_crc);
-    const jfs_dev_block *d_sdesc = (const jfs_dev_block *)(d + o_sdesc), *d_enc = (const jfs_dev_block *)(d + o_enc),
-                        *d_cd = (const jfs_dev_block *)(d + o_cd);
-    const jfs_aead_block *d_sad = (const jfs_aead_block *)(d + o_sad), *d_oad = (const jfs_aead_block *)(d + o_oad);
-    int32_t *d_srcn = (int32_t *)(d + o_srcn), *d_open = (int32_t *)(d + o_open), *d_ret = (int32_t *)(d + o_ret),
-            *d_r2 = (int32_t *)(d + o_r2);
-    std::vector<CopyJob> jobs;
-    for (int k = 0; k < ns; k++) {
-        const jfs_iov &v = src[ss[k].idx];
-        const int64_t pay = ss[k].pay, plain = pay - 16;  // pay >= 16: the host answered shorter ones
-        jobs.push_back({h + in_off[k], v.src + ss[k].off, pay});
-        uint8_t *cell = h + o_kn + 64 * (int64_t)k, *d_cell = d + o_kn + 64 * (int64_t)k;
-        memcpy(cell, src_keys[ss[k].idx], (size_t)klen);
-        memcpy(cell + 32, v.src + ss[k].noff, 12);
-        // open in place over the staged payload; the codec reads the plaintext
-        // ("none": the opened payload is the decoded block)
-        h_sad[k] = jfs_aead_block{d + in_off[k], d + in_off[k], (int32_t)pay, (int32_t)pay, d_cell, d_cell + 32};
-        uint8_t *dec = codec ? sl.sp + dec_off[k] : d + in_off[k];
-        h_sdesc[k] = jfs_dev_block{d + in_off[k], dec, (int32_t)plain, (int32_t)(codec ? ss[k].cap : plain)};
-        h_srcn[k] = codec ? -1 : (int32_t)plain;  // a decoder overwrites it
-    }
-    h_sdesc[ns] = jfs_dev_block{nullptr, nullptr, 0, 0};
-    h_srcn[ns] = -1;
-    par_copy(jobs);
+    h_sdesc[c.ns] = jfs_dev_block{nullptr, nullptr, 0, 0};  // "a failed source"
+    h_srcn[c.ns] = -1;
+}
+
+// the gather plan of the outputs the device works on, its segments remapped to the staged sources
+void chain_stage_plan(const Chain &c, const std::vector<ChainOut> &oo, const std::vector<int> &src_map,
+                      const int32_t *seg_first, const jfs_compact_seg *seg) {
+    jfs_compact_out *h_plan = c.host<jfs_compact_out>(c.L.plan);
+    jfs_compact_seg *h_seg = c.host<jfs_compact_seg>(c.L.seg);
     int64_t sg = 0;
-    for (int k = 0; k < no; k++) {
+    for (int k = 0; k < c.no; k++) {
         const int j = oo[k].idx;
-        const jfs_seal_param &p = out_p[j];
         const int cnt = seg_first[j + 1] - seg_first[j];
-        uint8_t *pay = d + o_out + out_off[k];  // the envelope's payload area: bound + 16 bytes
-        uint8_t *gat = codec ? sl.sp + gat_off[k] : pay;
-        h_plan[k] = jfs_compact_out{gat, (int32_t)oo[k].total, (int32_t)sg, cnt, 0};
-        for (int q = 0; q < cnt; q++) {
-            jfs_compact_seg s = seg[seg_first[j] + q];
-            if (s.src >= 0) s.src = src_map[s.src] >= 0 ? src_map[s.src] : ns;
-            h_seg[sg + q] = s;
-        }
+        h_plan[k] = jfs_compact_out{c.gat(k), (int32_t)oo[k].total, (int32_t)sg, cnt, 0};
+        for (int q = 0; q < cnt; q++) h_seg[sg + q] = jfs_plan::chain_remap(seg[seg_first[j] + q], src_map, c.ns);
         sg += cnt;
-        h_enc[k] = jfs_dev_block{gat, pay, (int32_t)oo[k].total, (int32_t)oo[k].bound};
-        h_cd[k] = jfs_dev_block{pay, nullptr, 0, 0};
-        uint8_t *cell = h + o_kn + 64 * (int64_t)(ns + k), *d_cell = d + o_kn + 64 * (int64_t)(ns + k);
-        memcpy(cell, p.key, (size_t)klen);
-        memcpy(cell + 32, p.nonce, 12);
-        // seal in place; with a codec the length comes from the encoder on the device
-        h_oad[k] = jfs_aead_block{pay, pay, (int32_t)oo[k].total, (int32_t)(oo[k].bound + 16), d_cell, d_cell + 32};
-        h_seed[k] = seal_header_crc(p);
     }
-    // the small-batch LZ4 decoder and encoder share slot 1's scratch (see compact_run)
-    Slot &s1 = ln.slot[1];
-    const bool lz4 = algo == JFS_ALGO_LZ4, fast = lz4_fast_mode();
-    {
-        int64_t need = 0;
-        if (lz4 && ns > 0) need = lz4_decode_scratch(ns, desc_lens(h_sdesc, ns).data(), desc_caps(h_sdesc, ns).data());
-        if (lz4 && no > 0) need = std::max(need, lz4_encode_scratch(no, desc_lens(h_enc, no).data(), fast));
-        if (need > 0 && !s1.ensure_split(need)) return JFS_ERR_NO_MEMORY;
-    }
-    hipStream_t ks = ln.s_k;
-    // one H2D: sealed payloads, the plan, keys and the preset source lengths
-    if (hipMemcpyAsync(d, h, (size_t)o_open, hipMemcpyHostToDevice, ks) != hipSuccess) return JFS_ERR_HIP;
+}
+
+// The small-batch LZ4 decoder and encoder (h_enc, or null) run one after the
+// other on the stream: they share slot 1's scratch, sized for both before
+// anything is queued.
+bool chain_lz4_scratch(const Chain &c, const jfs_dev_block *h_enc, bool fast) {
+    if (!c.lz4) return true;
+    const jfs_dev_block *h_sdesc = c.host<jfs_dev_block>(c.L.sdesc);
+    int64_t need = 0;
+    if (c.ns > 0) need = lz4_decode_scratch(c.ns, desc_lens(h_sdesc, c.ns).data(), desc_caps(h_sdesc, c.ns).data());
+    if (h_enc && c.no > 0) need = std::max(need, lz4_encode_scratch(c.no, desc_lens(h_enc, c.no).data(), fast));
+    return need <= 0 || c.s1->ensure_split(need);
+}
+
+// Queues open -> decode -> the opens' verdicts merged into the source lengths.
+// d_want (prefix mode, LZ4; else null): where each decode stops.
+int chain_decode(const Chain &c, const int32_t *d_want, int64_t max_want) {
+    const jfs_dev_block *h_sdesc = c.host<jfs_dev_block>(c.L.sdesc), *d_sdesc = c.dev<jfs_dev_block>(c.L.sdesc);
+    int32_t *d_srcn = c.dev<int32_t>(c.L.srcn), *d_open = c.dev<int32_t>(c.L.open);
+    const int ns = c.ns;
     int lk = 0;
-    if (ns > 0) lk = jfs_launch_aead(cipher, d_sad, ns, 1, d_open, nullptr, ks);
-    if (lk == 0 && lz4 && ns > 0) {
-        lk = launch_lz4_decode(s1, h_sdesc, d_sdesc, ns, d_srcn, ks) == JFS_OK ? 0 : -1;
-    } else if (lk == 0 && algo == JFS_ALGO_ZSTD && ns > 0) {
-        lk = jfs_launch_zstd_decode(d_sdesc, ns, d_srcn, nullptr, ks);  // ciphertext on the host: it plans its own scratch
+    if (c.sealed && ns > 0) lk = jfs_launch_aead(c.cipher, c.dev<jfs_aead_block>(c.L.sad), ns, 1, d_open, nullptr, c.ks);
+    if (lk == 0 && c.lz4 && ns > 0) {
+        const int64_t r = d_want ? launch_lz4_decode_prefix(*c.s1, h_sdesc, d_sdesc, ns, d_srcn, d_want, max_want, c.ks)
+                                 : launch_lz4_decode(*c.s1, h_sdesc, d_sdesc, ns, d_srcn, c.ks);
+        lk = r == JFS_OK ? 0 : -1;
+    } else if (lk == 0 && c.algo == JFS_ALGO_ZSTD && ns > 0) {
+        // (with a cipher the frame headers are ciphertext on the host) it plans its own scratch
+        lk = jfs_launch_zstd_decode(d_sdesc, ns, d_srcn, nullptr, c.ks);
     }
     // a failed open left zeros, which may decode (for "none" they are the block): its verdict replaces the length
-    if (lk == 0) lk = jfs_launch_chain_merge(d_open, ns, d_srcn, ks);
-    const jfs_compact_out *d_plan = (const jfs_compact_out *)(d + o_plan);
-    const jfs_compact_seg *d_seg = (const jfs_compact_seg *)(d + o_seg);
-    if (lk == 0) lk = jfs_launch_gather(d_sdesc, d_srcn, ns + 1, d_plan, no, d_seg, max_total, d_ret, 0, ks);
+    if (lk == 0 && c.sealed) lk = jfs_launch_chain_merge(d_open, ns, d_srcn, c.ks);
+    return lk;
+}
+
+// One D2H of [results, end) once the launches (lk) are queued; the stream is
+// drained either way.  false: JFS_ERR_HIP.
+bool chain_results(const Chain &c, int lk, int64_t end) {
+    const int64_t at = c.L.results;
+    if (lk == 0 && hipMemcpyAsync(c.h + at, c.d + at, (size_t)(end - at), hipMemcpyDeviceToHost, c.ks) == hipSuccess &&
+        hipStreamSynchronize(c.ks) == hipSuccess)
+        return true;
+    (void)hipStreamSynchronize(c.ks);
+    return false;
+}
+
+// decoded source k's result: aead.Open first (encrypt.go:283), then the codec
+int64_t chain_src_result(const Chain &c, int k) {
+    if (c.sealed && c.host<int32_t>(c.L.open)[k] < 0) return JFS_ERR_AUTH;
+    const int32_t raw = c.host<int32_t>(c.L.srcn)[k];
+    return c.codec ? finish_result(c.algo, DECOMPRESS, raw) : (int64_t)raw;
+}
+
+// output result `raw` of the gather (encoded: of the encoder behind it)
+int64_t chain_out_result(int algo, bool encoded, int32_t raw) {
+    if (raw == JFS_CHAIN_FAILED) return JFS_ERR_CORRUPT;
+    if (encoded) return finish_result(algo, COMPRESS, raw);
+    return raw >= 0 ? (int64_t)raw : JFS_ERR_INVALID;
+}
+
+// Compaction on one lane: stored sources (sealed payloads), keys and the plan
+// H2D, open in place, decode, the opens' verdicts merged into the source
+// lengths, gather, encode into the output's payload area, seal in place
+// (lengths from the encoder on the device), checksums (seeded with the
+// envelope header's), results D2H, then exactly the compressed / sealed bytes
+// D2H; the host writes the envelope headers.  Returns JFS_OK with src_n /
+// out_n / crc of these blocks filled, or JFS_ERR_NO_MEMORY / JFS_ERR_HIP with
+// nothing filled.  Per-block results of sealed calls follow BatchRun::finish's
+// rules for sealed batches, so they equal jfs_open_decompress_batch's and
+// jfs_compress_seal_batch's.
+int64_t compact_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src, const uint8_t *const *src_keys,
+                    const std::vector<ChainSrc> &ss, const std::vector<int> &src_map, const jfs_iov *out,
+                    const jfs_seal_param *out_p, const std::vector<ChainOut> &oo, const int32_t *seg_first,
+                    const jfs_compact_seg *seg, int64_t *src_n, int64_t *out_n, uint32_t *crc) {
+    LaneRun scope(dev, ln, algo * 2 + COMPRESS, (uint64_t)(ss.size() + oo.size()));
+    Chain c;
+    const int64_t rc = chain_open(c, ln, algo, cipher, ss, (int)ss.size(), oo, seg_first, true, crc != nullptr, false, false);
+    if (rc != JFS_OK) return rc;
+    const ChainLayout &L = c.L;
+    const int ns = c.ns, no = c.no;
+    const bool codec = c.codec, sealed = c.sealed;
+    std::vector<CopyJob> jobs;
+    chain_stage_sources(c, src, src_keys, ss, jobs);
+    par_copy(jobs);
+    chain_stage_plan(c, oo, src_map, seg_first, seg);
+    jfs_dev_block *h_enc = c.host<jfs_dev_block>(L.enc);
+    for (int k = 0; k < no; k++) {
+        uint8_t *pay = c.d_out(k);  // the output's payload area: oo[k].area bytes
+        h_enc[k] = jfs_dev_block{c.gat(k), pay, (int32_t)oo[k].total, (int32_t)oo[k].cap};
+        if (crc) c.host<jfs_dev_block>(L.ocd)[k] = jfs_dev_block{pay, nullptr, 0, 0};
+        if (!sealed) continue;
+        const jfs_seal_param &p = out_p[oo[k].idx];
+        uint8_t *d_cell = chain_cell(c, ns + k, p.key, p.nonce);
+        // seal in place; with a codec the length comes from the encoder on the device
+        c.host<jfs_aead_block>(L.oad)[k] =
+            jfs_aead_block{pay, pay, (int32_t)oo[k].total, (int32_t)(oo[k].cap + 16), d_cell, d_cell + 32};
+        if (crc) c.host<uint32_t>(L.oseed)[k] = seal_header_crc(p);
+    }
+    const bool fast = lz4_fast_mode();
+    if (!chain_lz4_scratch(c, h_enc, fast)) return JFS_ERR_NO_MEMORY;
+    hipStream_t ks = c.ks;
+    // one H2D: stored sources, the plan, keys and the preset source lengths
+    if (hipMemcpyAsync(c.d, c.h, (size_t)L.h2d, hipMemcpyHostToDevice, ks) != hipSuccess) return JFS_ERR_HIP;
+    const jfs_dev_block *d_sdesc = c.dev<jfs_dev_block>(L.sdesc), *d_enc = c.dev<jfs_dev_block>(L.enc);
+    int32_t *d_srcn = c.dev<int32_t>(L.srcn), *d_ret = c.dev<int32_t>(L.ret), *d_r2 = c.dev<int32_t>(L.r2);
+    const int32_t max_total = jfs_plan::chain_max_total(oo);
+    auto gather = [&](int pass) {
+        return jfs_launch_gather(d_sdesc, d_srcn, ns + 1, c.dev<jfs_compact_out>(L.plan), no, c.dev<jfs_compact_seg>(L.seg),
+                                 max_total, d_ret, pass, ks);
+    };
+    int lk = chain_decode(c, nullptr, 0);
+    if (lk == 0) lk = gather(0);
     if (lk == 0 && codec && no > 0) {
-        lk = lz4 ? (launch_lz4_encode(s1, h_enc, d_enc, no, d_ret, ks, fast) == JFS_OK ? 0 : -1)
-                 : launch_kernel(algo, COMPRESS, d_enc, no, d_ret, ks, zstd_parse_now());
+        lk = c.lz4 ? (launch_lz4_encode(*c.s1, h_enc, d_enc, no, d_ret, ks, fast) == JFS_OK ? 0 : -1)
+                   : launch_kernel(algo, COMPRESS, d_enc, no, d_ret, ks, zstd_parse_now());
         // the encoder ran on every block: a failed gather's verdict replaces its result
-        if (lk == 0) lk = jfs_launch_gather(d_sdesc, d_srcn, ns + 1, d_plan, no, d_seg, max_total, d_ret, 1, ks);
+        if (lk == 0) lk = gather(1);
     }
     // "none": the length is the planned total; the seal also runs over a block
     // whose gather failed (its verdict in d_ret decides on the host)
-    if (lk == 0 && no > 0) lk = jfs_launch_aead(cipher, d_oad, no, 0, d_r2, codec ? d_ret : nullptr, ks);
+    if (lk == 0 && sealed && no > 0)
+        lk = jfs_launch_aead(cipher, c.dev<jfs_aead_block>(L.oad), no, 0, d_r2, codec ? d_ret : nullptr, ks);
     if (lk == 0 && crc && no > 0)
-        lk = jfs_launch_crc32c_lens(d_cd, no, d_r2, (const uint32_t *)(d + o_seed), (uint32_t *)(d + o_crc), ks);
-    if (lk != 0 || hipMemcpyAsync(h + o_srcn, d + o_srcn, (size_t)(o_out - o_srcn), hipMemcpyDeviceToHost, ks) !=
-                       hipSuccess ||
-        hipStreamSynchronize(ks) != hipSuccess) {
-        (void)hipStreamSynchronize(ks);
-        return JFS_ERR_HIP;
-    }
-    for (int k = 0; k < ns; k++)  // aead.Open first (encrypt.go:283), then the codec
-        src_n[ss[k].idx] = h_open[k] < 0 ? JFS_ERR_AUTH
-                           : codec       ? finish_result(algo, DECOMPRESS, h_srcn[k])
-                                         : (int64_t)h_srcn[k];
-    std::vector<int64_t> res(no);
+        lk = jfs_launch_crc32c_lens(c.dev<jfs_dev_block>(L.ocd), no, sealed ? d_r2 : d_ret,
+                                    sealed ? c.dev<uint32_t>(L.oseed) : nullptr, c.dev<uint32_t>(L.ocrc), ks);
+    if (!chain_results(c, lk, L.out)) return JFS_ERR_HIP;
+    const int32_t *h_ret = c.host<int32_t>(L.ret), *h_r2 = c.host<int32_t>(L.r2);
+    std::vector<int64_t> res(no), back(no);  // per output: its result, its bytes in the payload area
     for (int k = 0; k < no; k++) {
-        const int32_t raw = h_ret[k];
-        int64_t r;
-        if (raw == JFS_CHAIN_FAILED) r = JFS_ERR_CORRUPT;
-        else if (codec) r = finish_result(algo, COMPRESS, raw);
-        else r = raw >= 0 ? (int64_t)raw : JFS_ERR_INVALID;
-        if (r >= 0 && h_r2[k] != r + 16) r = JFS_ERR_HIP;
-        else if (r >= 0 && oo[k].hdr + r + 16 > out[oo[k].idx].dst_cap) r = JFS_ERR_SHORT_BUFFER;
+        int64_t r = chain_out_result(algo, codec, h_ret[k]);
+        if (sealed && r >= 0 && h_r2[k] != r + 16) r = JFS_ERR_HIP;
+        else if (sealed && r >= 0 && oo[k].hdr + r + 16 > out[oo[k].idx].dst_cap) r = JFS_ERR_SHORT_BUFFER;
         res[k] = r;
-        // exactly the sealed bytes come back
-        if (r >= 0 && hipMemcpyAsync(h + o_out + out_off[k], d + o_out + out_off[k], (size_t)(r + 16),
-                                     hipMemcpyDeviceToHost, ks) != hipSuccess) {
+        back[k] = r < 0 ? 0 : sealed ? r + 16 : r;
+        // exactly the compressed / sealed bytes come back
+        if (back[k] > 0 &&
+            hipMemcpyAsync(c.h_out(k), c.d_out(k), (size_t)back[k], hipMemcpyDeviceToHost, ks) != hipSuccess) {
             (void)hipStreamSynchronize(ks);
             return JFS_ERR_HIP;
         }
     }
     if (hipStreamSynchronize(ks) != hipSuccess) return JFS_ERR_HIP;
+    for (int k = 0; k < ns; k++) src_n[ss[k].idx] = chain_src_result(c, k);
     jobs.clear();
     for (int k = 0; k < no; k++) {
         const int j = oo[k].idx;
-        const int64_t r = res[k];
-        if (r >= 0) {
-            seal_header_write(out[j].dst, out_p[j]);
-            jobs.push_back({out[j].dst + oo[k].hdr, h + o_out + out_off[k], r + 16});
-        }
-        out_n[j] = r >= 0 ? oo[k].hdr + r + 16 : r;
-        if (crc) crc[j] = r >= 0 ? h_crc[k] : 0u;
+        if (sealed && res[k] >= 0) seal_header_write(out[j].dst, out_p[j]);
+        if (back[k] > 0) jobs.push_back({out[j].dst + oo[k].hdr, c.h_out(k), back[k]});
+        out_n[j] = res[k] >= 0 ? oo[k].hdr + back[k] : res[k];
+        if (crc) crc[j] = res[k] >= 0 ? c.host<uint32_t>(L.ocrc)[k] : 0u;
     }
     par_copy(jobs);
     return JFS_OK;
 }
 
-// ---------------------------------------------------------------------------
-// read assembly: verify -> (open) -> decode -> gather on one device
-// (jfs_read_batch, jfs_read_open_batch)
-// ---------------------------------------------------------------------------
-// One stored object the device works on.  The first `ns` entries of the list
-// are the sources the chain decodes (bytes [off, off + pay) of the object are
-// staged: the whole object, or the sealed payload of an envelope); the rest are
+// The GET-side mirror of compact_run, its staging and decoder choice: stored
+// bytes and the plan H2D, CRC-32C of every object that has an expected value
+// (for an envelope the payload's, seeded on the host with the header's), open
+// in place, decode, the opens' verdicts and then the checksums' verdicts
+// merged into the source lengths, plan and flat gather into one packed area
+// (16-byte aligned offsets), one D2H of the results and that area; the host
+// copies the good reads out.  st[0, ns) are the decoded sources, the rest
 // objects the host already answered, staged whole only for their checksum.
-struct ReadSrc {
-    int idx;
-    int64_t off, noff, pay;  // SealedSrc's; off = noff = 0 without a cipher
-    int64_t cap;             // staged decode capacity
-    bool check;              // an expected CRC-32C came with it
-    uint32_t expect;
-};
-struct ReadOut {
-    int idx;
-    int64_t total;
-};
-
-// The GET-side mirror of compact_run / compact_seal_run (cipher < 0: no
-// envelopes), their staging and decoder choice, one pass on the lane's kernel
-// stream: stored bytes and the plan H2D, CRC-32C of every object that has an
-// expected value (for an envelope the payload's, seeded on the host with the
-// header's), open in place, decode, the opens' verdicts and then the
-// checksums' verdicts merged into the source lengths, plan and flat gather
-// into one packed area (16-byte aligned offsets), one D2H of the results and
-// that area; the host copies the good reads out.  st[0, ns) are the decoded
-// sources; src_map as in compact_run.  Returns JFS_OK with src_n / out_n /
-// crc_got of these objects filled, or JFS_ERR_NO_MEMORY / JFS_ERR_HIP.
+// Returns JFS_OK with src_n / out_n / crc_got of these objects filled, or
+// JFS_ERR_NO_MEMORY / JFS_ERR_HIP.
 // need (JFS_READ_DECODE_PREFIX with LZ4, else null): per object of the call,
 // the last byte a segment asks of it; the decode of source k stops there
 // (clamped to its capacity, staged behind the expected checksums in the same
 // H2D copy) unless every source is needed whole, which takes the full
 // launchers.
 int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src, const uint8_t *const *src_keys,
-                 const std::vector<ReadSrc> &st, int ns, const std::vector<int> &src_map, const jfs_iov *out,
-                 const std::vector<ReadOut> &oo, const int32_t *seg_first, const jfs_compact_seg *seg, int64_t *src_n,
+                 const std::vector<ChainSrc> &st, int ns, const std::vector<int> &src_map, const jfs_iov *out,
+                 const std::vector<ChainOut> &oo, const int32_t *seg_first, const jfs_compact_seg *seg, int64_t *src_n,
                  int64_t *out_n, uint32_t *crc_got, const int64_t *need) {
     LaneRun scope(dev, ln, algo * 2 + DECOMPRESS, (uint64_t)st.size());
-    const bool codec = algo != JFS_ALGO_NONE, sealed = cipher >= 0;
     const int n = (int)st.size(), no = (int)oo.size();
-    const int klen = sealed ? jfs_cipher_key_size(cipher) : 0;
     bool any_check = false;
-    std::vector<int64_t> in_off(n), out_off(no), dec_off(ns);
-    std::vector<int32_t> tile_first(no + 1);
-    int64_t tin = 0, tout = 0, scratch = 0, nseg = 0, ntiles = 0;
-    for (int k = 0; k < n; k++) {
-        in_off[k] = tin;
-        tin += align16(st[k].pay);
-        any_check = any_check || st[k].check;
-        if (codec && k < ns) {
-            dec_off[k] = scratch;
-            scratch += align16(st[k].cap);
-        }
-    }
+    for (const ChainSrc &s : st) any_check = any_check || s.check;
+    std::vector<int32_t> tile_first(no + 1), want;
+    int64_t ntiles = 0, max_want = 0;
     for (int k = 0; k < no; k++) {
-        out_off[k] = tout;
-        tout += align16(oo[k].total);
-        nseg += seg_first[oo[k].idx + 1] - seg_first[oo[k].idx];
         tile_first[k] = (int32_t)ntiles;
         ntiles += jfs_gather_tiles(oo[k].total);
         if (ntiles > INT32_MAX) return JFS_ERR_NO_MEMORY;
     }
     tile_first[no] = (int32_t)ntiles;
-    std::vector<int32_t> want;
-    int64_t max_want = 0;
-    if (need && algo == JFS_ALGO_LZ4) {
-        bool whole = true;
-        want.resize(ns);
-        for (int k = 0; k < ns; k++) {
-            want[k] = (int32_t)std::min<int64_t>(need[st[k].idx], st[k].cap);
-            max_want = std::max<int64_t>(max_want, want[k]);
-            whole = whole && want[k] >= st[k].cap;
-        }
-        if (whole) want.clear();
-    }
+    if (need && algo == JFS_ALGO_LZ4) want = jfs_plan::chain_want(need, st, ns, &max_want);
     const bool prefix = !want.empty();
-    // staged area, mirrored pinned / HBM: [stored bytes | meta | results | packed reads]
-    // meta: source descriptors (ns + 1: the last one is "a failed source"), the
-    // plan, segments, tile prefix, the opens' descriptors and key | nonce cells,
-    // the checksum descriptors with their seeds, lengths (-1: no expected value)
-    // and expected values, the preset source lengths; results, which only the
-    // device writes: opens, reads, raw checksums, checked checksums
-    const int64_t blk_b = (int64_t)sizeof(jfs_dev_block), aead_b = (int64_t)sizeof(jfs_aead_block);
-    const int64_t o_sdesc = tin;
-    const int64_t o_plan = o_sdesc + align16((ns + 1) * blk_b);
-    const int64_t o_seg = o_plan + align16((int64_t)no * (int64_t)sizeof(jfs_compact_out));
-    const int64_t o_tf = o_seg + align16(nseg * (int64_t)sizeof(jfs_compact_seg));
-    const int64_t o_sad = o_tf + align16((int64_t)(no + 1) * 4);
-    const int64_t o_kn = o_sad + align16(ns * aead_b);
-    const int64_t o_cd = o_kn + 64 * (int64_t)ns;
-    const int64_t o_seed = o_cd + align16(n * blk_b);
-    const int64_t o_len = o_seed + align16((int64_t)n * 4);
-    const int64_t o_exp = o_len + align16((int64_t)n * 4);
-    const int64_t o_want = o_exp + align16((int64_t)n * 4);
-    const int64_t o_srcn = o_want + (prefix ? align16((int64_t)ns * 4) : 0);
-    const int64_t o_open = o_srcn + align16((int64_t)(ns + 1) * 4);
-    const int64_t o_ret = o_open + align16((int64_t)ns * 4);
-    const int64_t o_crc = o_ret + align16((int64_t)no * 4);
-    const int64_t o_got = o_crc + align16((int64_t)n * 4);
-    const int64_t o_out = o_got + align16((int64_t)n * 4);
-    Slot &sl = ln.slot[0];
-    if (!sl.ensure(o_out + tout)) return JFS_ERR_NO_MEMORY;
-    if (codec && !sl.ensure_split(std::max<int64_t>(scratch, 16))) return JFS_ERR_NO_MEMORY;
-    uint8_t *h = sl.h, *d = sl.d;
-    jfs_dev_block *h_sdesc = (jfs_dev_block *)(h + o_sdesc), *h_cd = (jfs_dev_block *)(h + o_cd);
-    jfs_aead_block *h_sad = (jfs_aead_block *)(h + o_sad);
-    jfs_compact_out *h_plan = (jfs_compact_out *)(h + o_plan);
-    jfs_compact_seg *h_seg = (jfs_compact_seg *)(h + o_seg);
-    uint32_t *h_seed = (uint32_t *)(h + o_seed), *h_exp = (uint32_t *)(h + o_exp);
-    int32_t *h_len = (int32_t *)(h + o_len), *h_srcn = (int32_t *)(h + o_srcn);
-    const int32_t *h_open = (const int32_t *)(h + o_open), *h_ret = (const int32_t *)(h + o_ret);
-    const uint32_t *h_got = (const uint32_t *)(h + o_got);
-    const jfs_dev_block *d_sdesc = (const jfs_dev_block *)(d + o_sdesc), *d_cd = (const jfs_dev_block *)(d + o_cd);
-    const jfs_aead_block *d_sad = (const jfs_aead_block *)(d + o_sad);
-    int32_t *d_srcn = (int32_t *)(d + o_srcn), *d_open = (int32_t *)(d + o_open), *d_ret = (int32_t *)(d + o_ret);
-    memcpy(h + o_tf, tile_first.data(), (size_t)(no + 1) * 4);
-    if (prefix) memcpy(h + o_want, want.data(), (size_t)ns * 4);
+    Chain c;
+    const int64_t rc = chain_open(c, ln, algo, cipher, st, ns, oo, seg_first, false, false, any_check, prefix);
+    if (rc != JFS_OK) return rc;
+    const ChainLayout &L = c.L;
+    memcpy(c.h + L.tf, tile_first.data(), (size_t)(no + 1) * 4);
+    if (prefix) memcpy(c.h + L.want, want.data(), (size_t)ns * 4);
     std::vector<CopyJob> jobs;
-    for (int k = 0; k < n; k++) {
-        const ReadSrc &s = st[k];
-        const jfs_iov &v = src[s.idx];
-        if (s.pay > 0) jobs.push_back({h + in_off[k], v.src + s.off, s.pay});
+    chain_stage_sources(c, src, src_keys, st, jobs);
+    for (int k = 0; any_check && k < n; k++) {
+        const ChainSrc &s = st[k];
         // the checksum covers the object as fetched: the staged bytes, behind the envelope header's on the host
-        h_cd[k] = jfs_dev_block{d + in_off[k], nullptr, (int32_t)s.pay, 0};
-        h_seed[k] = s.check && s.off > 0 ? host_crc32c(0, v.src, s.off) : 0u;
-        h_len[k] = s.check && s.pay > 0 ? (int32_t)s.pay : -1;
-        h_exp[k] = s.expect;
-        if (k >= ns) continue;
-        const int64_t plain = sealed ? s.pay - 16 : s.pay;  // sealed: pay >= 16, the host answered shorter ones
-        if (sealed) {
-            uint8_t *cell = h + o_kn + 64 * (int64_t)k, *d_cell = d + o_kn + 64 * (int64_t)k;
-            memcpy(cell, src_keys[s.idx], (size_t)klen);
-            memcpy(cell + 32, v.src + s.noff, 12);
-            // open in place over the staged payload; the codec reads the plaintext
-            h_sad[k] = jfs_aead_block{d + in_off[k], d + in_off[k], (int32_t)s.pay, (int32_t)s.pay, d_cell, d_cell + 32};
-        }
-        // "none": the stored (opened) object is the decoded block
-        uint8_t *dec = codec ? sl.sp + dec_off[k] : d + in_off[k];
-        h_sdesc[k] = jfs_dev_block{d + in_off[k], dec, (int32_t)plain, (int32_t)(codec ? s.cap : plain)};
-        h_srcn[k] = codec ? -1 : (int32_t)plain;  // a decoder overwrites it
+        c.host<jfs_dev_block>(L.scd)[k] = jfs_dev_block{c.d_in(k), nullptr, (int32_t)s.pay, 0};
+        c.host<uint32_t>(L.sseed)[k] = s.check && s.off > 0 ? host_crc32c(0, src[s.idx].src, s.off) : 0u;
+        c.host<int32_t>(L.len)[k] = s.check && s.pay > 0 ? (int32_t)s.pay : -1;
+        c.host<uint32_t>(L.exp)[k] = s.expect;
     }
-    h_sdesc[ns] = jfs_dev_block{nullptr, nullptr, 0, 0};
-    h_srcn[ns] = -1;
     par_copy(jobs);
-    int64_t sg = 0;
-    for (int k = 0; k < no; k++) {
-        const int j = oo[k].idx;
-        const int cnt = seg_first[j + 1] - seg_first[j];
-        h_plan[k] = jfs_compact_out{d + o_out + out_off[k], (int32_t)oo[k].total, (int32_t)sg, cnt, 0};
-        for (int q = 0; q < cnt; q++) {
-            jfs_compact_seg s = seg[seg_first[j] + q];
-            if (s.src >= 0) s.src = src_map[s.src] >= 0 ? src_map[s.src] : ns;
-            h_seg[sg + q] = s;
-        }
-        sg += cnt;
-    }
-    // the small-batch LZ4 decoder's scratch (slot 1's) is sized before anything is queued (see compact_run)
-    Slot &s1 = ln.slot[1];
-    const bool lz4 = algo == JFS_ALGO_LZ4;
-    if (lz4 && ns > 0) {
-        const int64_t need = lz4_decode_scratch(ns, desc_lens(h_sdesc, ns).data(), desc_caps(h_sdesc, ns).data());
-        if (need > 0 && !s1.ensure_split(need)) return JFS_ERR_NO_MEMORY;
-    }
-    hipStream_t ks = ln.s_k;
+    chain_stage_plan(c, oo, src_map, seg_first, seg);
+    if (!chain_lz4_scratch(c, nullptr, false)) return JFS_ERR_NO_MEMORY;
+    hipStream_t ks = c.ks;
     // one H2D: stored bytes, the plan, keys, checksum inputs and the preset source lengths
-    if (hipMemcpyAsync(d, h, (size_t)o_open, hipMemcpyHostToDevice, ks) != hipSuccess) return JFS_ERR_HIP;
+    if (hipMemcpyAsync(c.d, c.h, (size_t)L.h2d, hipMemcpyHostToDevice, ks) != hipSuccess) return JFS_ERR_HIP;
+    int32_t *d_srcn = c.dev<int32_t>(L.srcn);
+    const int32_t *d_len = c.dev<int32_t>(L.len);
     int lk = 0;
     // verifyChecksum sits in front of Decrypt and Decompress: before the open rewrites the staged bytes
     if (any_check)
-        lk = jfs_launch_crc32c_lens(d_cd, n, (const int32_t *)(d + o_len), (const uint32_t *)(d + o_seed),
-                                    (uint32_t *)(d + o_crc), ks);
-    if (lk == 0 && sealed && ns > 0) lk = jfs_launch_aead(cipher, d_sad, ns, 1, d_open, nullptr, ks);
-    if (lk == 0 && lz4 && ns > 0) {
-        const int64_t r = prefix ? launch_lz4_decode_prefix(s1, h_sdesc, d_sdesc, ns, d_srcn,
-                                                            (const int32_t *)(d + o_want), max_want, ks)
-                                 : launch_lz4_decode(s1, h_sdesc, d_sdesc, ns, d_srcn, ks);
-        lk = r == JFS_OK ? 0 : -1;
-    } else if (lk == 0 && algo == JFS_ALGO_ZSTD && ns > 0) {
-        lk = jfs_launch_zstd_decode(d_sdesc, ns, d_srcn, nullptr, ks);  // plans its own scratch
-    }
-    // a failed open left zeros, which may decode: its verdict replaces the length (see compact_seal_run)
-    if (lk == 0 && sealed) lk = jfs_launch_chain_merge(d_open, ns, d_srcn, ks);
+        lk = jfs_launch_crc32c_lens(c.dev<jfs_dev_block>(L.scd), n, d_len, c.dev<uint32_t>(L.sseed),
+                                    c.dev<uint32_t>(L.scrc), ks);
+    if (lk == 0) lk = chain_decode(c, prefix ? c.dev<int32_t>(L.want) : nullptr, max_want);
     if (lk == 0 && any_check)
-        lk = jfs_launch_verify_gate((const uint32_t *)(d + o_crc), (const int32_t *)(d + o_len),
-                                    (const uint32_t *)(d + o_exp), n, ns, d_srcn, (uint32_t *)(d + o_got), ks);
+        lk = jfs_launch_verify_gate(c.dev<uint32_t>(L.scrc), d_len, c.dev<uint32_t>(L.exp), n, ns, d_srcn,
+                                    c.dev<uint32_t>(L.got), ks);
     if (lk == 0)
-        lk = jfs_launch_gather_flat(d_sdesc, d_srcn, ns + 1, (const jfs_compact_out *)(d + o_plan), no,
-                                    (const jfs_compact_seg *)(d + o_seg), d_ret, (const int32_t *)(d + o_tf), ntiles, ks);
+        lk = jfs_launch_gather_flat(c.dev<jfs_dev_block>(L.sdesc), d_srcn, ns + 1, c.dev<jfs_compact_out>(L.plan), no,
+                                    c.dev<jfs_compact_seg>(L.seg), c.dev<int32_t>(L.ret), c.dev<int32_t>(L.tf), ntiles,
+                                    ks);
     // one D2H: the results and every read, packed
-    if (lk != 0 || hipMemcpyAsync(h + o_srcn, d + o_srcn, (size_t)(o_out + tout - o_srcn), hipMemcpyDeviceToHost, ks) !=
-                       hipSuccess ||
-        hipStreamSynchronize(ks) != hipSuccess) {
-        (void)hipStreamSynchronize(ks);
-        return JFS_ERR_HIP;
-    }
+    if (!chain_results(c, lk, L.out + c.off.tout)) return JFS_ERR_HIP;
     for (int k = 0; k < n; k++) {
-        const ReadSrc &s = st[k];
-        const uint32_t got = s.check && s.pay > 0 ? h_got[k] : 0u;  // an empty object's CRC is 0
+        const ChainSrc &s = st[k];
+        const uint32_t got = s.check && s.pay > 0 ? c.host<uint32_t>(L.got)[k] : 0u;  // an empty object's CRC is 0
         if (crc_got) crc_got[s.idx] = got;
         if (s.check && got != s.expect) src_n[s.idx] = JFS_ERR_CHECKSUM;  // before aead.Open and the codec
-        else if (k >= ns) continue;                                             // the host's answer stands
-        else if (sealed && h_open[k] < 0) src_n[s.idx] = JFS_ERR_AUTH;
-        else src_n[s.idx] = codec ? finish_result(algo, DECOMPRESS, h_srcn[k]) : (int64_t)h_srcn[k];
+        else if (k < ns) src_n[s.idx] = chain_src_result(c, k);          // (else the host's answer stands)
     }
     jobs.clear();
     for (int k = 0; k < no; k++) {
         const int j = oo[k].idx;
-        const int32_t raw = h_ret[k];
-        out_n[j] = raw == JFS_CHAIN_FAILED ? JFS_ERR_CORRUPT : raw >= 0 ? (int64_t)raw : JFS_ERR_INVALID;
-        if (raw > 0) jobs.push_back({out[j].dst, h + o_out + out_off[k], raw});
+        out_n[j] = chain_out_result(algo, false, c.host<int32_t>(L.ret)[k]);
+        if (out_n[j] > 0) jobs.push_back({out[j].dst, c.h_out(k), out_n[j]});
     }
     par_copy(jobs);
     return JFS_OK;
@@ -2457,7 +2207,74 @@ bool compact_plan_ok(int algo, int nsrc, const jfs_iov *src, int nout, const jfs
     return true;
 }
 
+// The sources of a chain call.  What the host answers before the device runs
+// (chain_src_answer) goes to src_n; the sources the device decodes go to st,
+// with src_map[i] = their position, and their count is returned.  Behind them
+// st gets the answered objects that still need the device for their checksum
+// (src_crc, reads only: verifyChecksum reads the whole object first).
+int chain_sources(int algo, bool sealed, int nsrc, const jfs_iov *src, const int64_t *src_crc, int64_t *src_n,
+                  uint32_t *crc_got, std::vector<ChainSrc> &st, std::vector<int> &src_map) {
+    std::vector<ChainSrc> only_crc;
+    src_map.assign(nsrc, -1);
+    for (int i = 0; i < nsrc; i++) {
+        const jfs_iov &v = src[i];
+        const bool check = src_crc && src_crc[i] >= 0;
+        ChainSrc r{i, 0, 0, 0, 0, check, check ? (uint32_t)src_crc[i] : 0u};
+        if (crc_got) crc_got[i] = 0;
+        src_n[i] = jfs_plan::chain_src_answer(algo, sealed, v, r);
+        if (src_n[i] == JFS_OK) {
+            // with a cipher dst_cap is staged for every codec: the Zstd frame
+            // header is ciphertext on the host (see jfs_open_decompress_batch)
+            r.cap = algo == JFS_ALGO_NONE ? (sealed ? r.pay - 16 : r.pay)
+                    : sealed              ? std::min<int64_t>(v.dst_cap, INT32_MAX)
+                                          : staged_cap(algo, DECOMPRESS, v);
+            src_map[i] = (int)st.size();
+            st.push_back(r);
+        } else if (check && v.src_len == 0) {  // an empty object: CRC 0, no device needed
+            if (r.expect != 0) src_n[i] = JFS_ERR_CHECKSUM;
+        } else if (check) {
+            only_crc.push_back(r);
+        }
+    }
+    const int ns = (int)st.size();
+    st.insert(st.end(), only_crc.begin(), only_crc.end());
+    return ns;
+}
+
 std::atomic<unsigned> g_compact_turn{0};
+
+// Runs a chain call's device part, run(dev, lane), on the next device in turn
+// with one of its lanes held, if the call left the device anything to do.  A
+// chain that did not run (JFS_ERR_NO_MEMORY / JFS_ERR_HIP, which is returned):
+// every block it held reports why.
+template <class Run>
+int64_t chain_dispatch(const std::vector<DevCtx *> &ds, int algo, int dir, const std::vector<ChainSrc> &st,
+                       const std::vector<ChainOut> &oo, int64_t *src_n, int64_t *out_n, Run run) {
+    if (st.empty() && oo.empty()) return JFS_OK;
+    DevCtx *dev = ds[g_compact_turn.fetch_add(1) % ds.size()];
+    std::unique_lock<std::mutex> lk;
+    Lane &ln = dev->acquire_lane(lk, algo * 2 + dir);
+    const int64_t rc = run(dev, ln);
+    if (rc == JFS_ERR_HIP) (void)lane_healthy(dev, ln);  // leave nothing in flight into the staging
+    if (rc != JFS_OK) {
+        for (const ChainSrc &s : st) src_n[s.idx] = rc;
+        for (const ChainOut &o : oo) out_n[o.idx] = rc;
+    }
+    return rc;
+}
+
+// One direction's statistics of a chain call over its nblk blocks: len(i) =
+// block i's input bytes, batch = the device worked on some, nanos = the call's
+// time (< 0: it is counted on the other direction).
+template <class Len>
+void chain_stat(int algo, int dir, int nblk, Len len, const int64_t *res, bool batch, int64_t nanos) {
+    OpStats *st = op_stats(algo, dir);
+    if (!st) return;
+    st->calls.fetch_add(1, std::memory_order_relaxed);
+    if (batch) st->batches.fetch_add(1, std::memory_order_relaxed);
+    for (int i = 0; i < nblk; i++) stat_block(st, len(i), res[i]);
+    if (nanos >= 0) st->nanos.fetch_add((uint64_t)nanos, std::memory_order_relaxed);
+}
 
 // Small-batch device launches: per-device scratch shared by every caller,
 // ordered across streams by an event (like the Zstd device decoder's).
@@ -3042,161 +2859,93 @@ int64_t jfs_lz4_compact_device(const jfs_dev_block *d_src, int nsrc, int32_t *d_
                : JFS_ERR_HIP;
 }
 
+// jfs_compact_batch (cipher < 0) and jfs_compact_seal_batch
+static int64_t compact_call(int algo, int cipher, int nsrc, const jfs_iov *src, const uint8_t *const *src_keys,
+                            int nout, const jfs_iov *out, const jfs_seal_param *out_p, const int32_t *seg_first,
+                            const jfs_compact_seg *seg, int64_t *src_n, int64_t *out_n, uint32_t *crc,
+                            uint32_t device_mask) {
+    const bool sealed = cipher >= 0;
+    // the plan, the keys and the seal parameters are checked before any device is touched
+    std::vector<int64_t> total;
+    if (!compact_plan_ok(algo, nsrc, src, nout, out, seg_first, seg, src_n, out_n, total)) return JFS_ERR_INVALID;
+    if (sealed) {
+        if (jfs_cipher_key_size(cipher) < 0) return JFS_ERR_INVALID;
+        if ((nsrc > 0 && !src_keys) || (nout > 0 && !out_p)) return JFS_ERR_INVALID;
+        for (int i = 0; i < nsrc; i++)
+            if (!src_keys[i]) return JFS_ERR_INVALID;
+        for (int j = 0; j < nout; j++) {
+            const jfs_seal_param &q = out_p[j];
+            if (!q.key || !q.nonce || q.wrapped_len < 0 || q.wrapped_len > 65535 || (q.wrapped_len > 0 && !q.wrapped))
+                return JFS_ERR_INVALID;
+        }
+    }
+    const std::vector<DevCtx *> ds = devices_in(device_mask);
+    if (ds.empty()) return JFS_ERR_NO_DEVICE;
+    const int64_t t0 = steady_ns();
+    std::vector<ChainSrc> ss;
+    std::vector<int> src_map;
+    chain_sources(algo, sealed, nsrc, src, nullptr, src_n, nullptr, ss, src_map);
+    std::vector<ChainOut> oo;
+    std::vector<int> own;  // sealed outputs with an error of their own: a failed source still wins (below)
+    for (int j = 0; j < nout; j++) {
+        if (crc) crc[j] = 0;
+        if (jfs_plan::chain_dead(seg_first, seg, j, src_map)) {
+            out_n[j] = JFS_ERR_CORRUPT;
+            continue;
+        }
+        ChainOut o{j, total[j], 0, 0, 0};
+        int64_t err = JFS_OK;
+        if (sealed) {  // what jfs_compress_seal_batch answers for the gathered block
+            const int64_t bound = jfs_envelope_bound(algo, total[j], out_p[j].wrapped_len);
+            o.hdr = 3 + (int64_t)out_p[j].wrapped_len + 12;
+            o.cap = bound - o.hdr - 16;  // the codec's bound of total; the payload area also holds the tag
+            o.area = o.cap + 16;
+            if (bound < 0) err = JFS_ERR_INVALID;
+            else if (algo == JFS_ALGO_LZ4 && total[j] > LZ4_MAX_INPUT) err = JFS_ERR_COMPRESS_FAIL;
+            else if (out[j].dst_cap < bound) err = JFS_ERR_SHORT_BUFFER;
+        } else {  // pre_answer's rules for the gathered block as Compress sees it
+            const jfs_iov g{nullptr, total[j], out[j].dst, out[j].dst_cap};
+            if (algo == JFS_ALGO_NONE && g.dst_cap < g.src_len) err = JFS_ERR_SHORT_BUFFER;
+            else if (algo == JFS_ALGO_LZ4 && g.src_len > LZ4_MAX_INPUT) err = JFS_ERR_COMPRESS_FAIL;
+            else if (algo == JFS_ALGO_ZSTD && g.dst_cap < jfs_compress_bound(JFS_ALGO_ZSTD, g.src_len))
+                err = JFS_ERR_SHORT_BUFFER;
+            else o.area = o.cap = algo == JFS_ALGO_NONE ? total[j] : staged_cap(algo, COMPRESS, g);
+        }
+        if (err == JFS_OK) {
+            oo.push_back(o);
+        } else {
+            out_n[j] = err;
+            if (sealed) own.push_back(j);
+        }
+    }
+    const int64_t rc = chain_dispatch(ds, algo, COMPRESS, ss, oo, src_n, out_n, [&](DevCtx *dev, Lane &ln) {
+        return compact_run(dev, ln, algo, cipher, src, src_keys, ss, src_map, out, out_p, oo, seg_first, seg, src_n, out_n,
+                           crc);
+    });
+    if (rc == JFS_OK)
+        for (int j : own)  // a source that failed on the device, or is too short, wins over the block's own error
+            for (int k = seg_first[j]; k < seg_first[j + 1]; k++)
+                if (seg[k].src >= 0 && (int64_t)seg[k].src_off + seg[k].len > src_n[seg[k].src]) out_n[j] = JFS_ERR_CORRUPT;
+    const int64_t nanos = steady_ns() - t0;
+    chain_stat(algo, DECOMPRESS, nsrc, [&](int i) { return src[i].src_len; }, src_n, !ss.empty(), -1);
+    chain_stat(algo, COMPRESS, nout, [&](int j) { return total[j]; }, out_n, !oo.empty(), nanos);
+    return JFS_OK;
+}
+
 int64_t jfs_compact_batch(int algo, int nsrc, const jfs_iov *src, int nout, const jfs_iov *out,
                           const int32_t *seg_first, const jfs_compact_seg *seg, int64_t *src_n, int64_t *out_n,
                           uint32_t *crc, uint32_t device_mask) {
-    // the whole plan is checked before any device is touched
-    std::vector<int64_t> total;
-    if (!compact_plan_ok(algo, nsrc, src, nout, out, seg_first, seg, src_n, out_n, total)) return JFS_ERR_INVALID;
-    std::vector<DevCtx *> ds;
-    for (DevCtx *d : devices())
-        if (device_mask == 0 || (d->id < 32 && (device_mask >> d->id) & 1u)) ds.push_back(d);
-    if (ds.empty()) return JFS_ERR_NO_DEVICE;
-    const int64_t t0 = steady_ns();
-    // what the Go adapters answer before the codec runs (pre_answer's rules;
-    // "none" decodes by copying, here without the copy)
-    std::vector<CompactSrc> ss;
-    std::vector<int> src_map(nsrc, -1);
-    for (int i = 0; i < nsrc; i++) {
-        const jfs_iov &v = src[i];
-        if (algo == JFS_ALGO_NONE ? v.dst_cap < v.src_len : v.src_len == 0) {
-            src_n[i] = algo == JFS_ALGO_NONE ? JFS_ERR_SHORT_BUFFER : JFS_ERR_EMPTY_INPUT;
-            continue;
-        }
-        src_map[i] = (int)ss.size();
-        ss.push_back({i, algo == JFS_ALGO_NONE ? v.src_len : staged_cap(algo, DECOMPRESS, v)});
-    }
-    std::vector<CompactOut> oo;
-    for (int j = 0; j < nout; j++) {
-        if (crc) crc[j] = 0;
-        const jfs_iov g{nullptr, total[j], out[j].dst, out[j].dst_cap};  // the gathered block as Compress sees it
-        bool dead = false;  // a source answered on the host feeds it
-        for (int k = seg_first[j]; k < seg_first[j + 1] && !dead; k++) dead = seg[k].src >= 0 && src_map[seg[k].src] < 0;
-        if (dead) out_n[j] = JFS_ERR_CORRUPT;
-        else if (algo == JFS_ALGO_NONE && g.dst_cap < g.src_len) out_n[j] = JFS_ERR_SHORT_BUFFER;
-        else if (algo == JFS_ALGO_LZ4 && g.src_len > LZ4_MAX_INPUT) out_n[j] = JFS_ERR_COMPRESS_FAIL;
-        else if (algo == JFS_ALGO_ZSTD && g.dst_cap < jfs_compress_bound(JFS_ALGO_ZSTD, g.src_len))
-            out_n[j] = JFS_ERR_SHORT_BUFFER;
-        else oo.push_back({j, total[j], algo == JFS_ALGO_NONE ? total[j] : staged_cap(algo, COMPRESS, g)});
-    }
-    int64_t rc = JFS_OK;
-    if (!ss.empty() || !oo.empty()) {
-        DevCtx *dev = ds[g_compact_turn.fetch_add(1) % ds.size()];
-        std::unique_lock<std::mutex> lk;
-        Lane &ln = dev->acquire_lane(lk, algo * 2 + COMPRESS);
-        rc = compact_run(dev, ln, algo, src, ss, src_map, out, oo, seg_first, seg, src_n, out_n, crc);
-        if (rc == JFS_ERR_HIP) (void)lane_healthy(dev, ln);  // leave nothing in flight into the staging
-    }
-    if (rc != JFS_OK) {  // the chain did not run: every block it held reports why
-        for (const CompactSrc &s : ss) src_n[s.idx] = rc;
-        for (const CompactOut &o : oo) out_n[o.idx] = rc;
-    }
-    const uint64_t ns = (uint64_t)(steady_ns() - t0);
-    if (OpStats *st = op_stats(algo, DECOMPRESS)) {
-        st->calls.fetch_add(1, std::memory_order_relaxed);
-        if (!ss.empty()) st->batches.fetch_add(1, std::memory_order_relaxed);
-        for (int i = 0; i < nsrc; i++) stat_block(st, src[i].src_len, src_n[i]);
-    }
-    if (OpStats *st = op_stats(algo, COMPRESS)) {
-        st->calls.fetch_add(1, std::memory_order_relaxed);
-        if (!oo.empty()) st->batches.fetch_add(1, std::memory_order_relaxed);
-        for (int j = 0; j < nout; j++) stat_block(st, total[j], out_n[j]);
-        st->nanos.fetch_add(ns, std::memory_order_relaxed);
-    }
-    return JFS_OK;
+    return compact_call(algo, -1, nsrc, src, nullptr, nout, out, nullptr, seg_first, seg, src_n, out_n, crc,
+                        device_mask);
 }
 
 int64_t jfs_compact_seal_batch(int algo, int cipher, int nsrc, const jfs_iov *src, const uint8_t *const *src_keys,
                                int nout, const jfs_iov *out, const jfs_seal_param *out_p, const int32_t *seg_first,
                                const jfs_compact_seg *seg, int64_t *src_n, int64_t *out_n, uint32_t *crc,
                                uint32_t device_mask) {
-    // the plan, the keys and the seal parameters are checked before any device is touched
-    std::vector<int64_t> total;
-    if (!compact_plan_ok(algo, nsrc, src, nout, out, seg_first, seg, src_n, out_n, total)) return JFS_ERR_INVALID;
-    if (jfs_cipher_key_size(cipher) < 0) return JFS_ERR_INVALID;
-    if ((nsrc > 0 && !src_keys) || (nout > 0 && !out_p)) return JFS_ERR_INVALID;
-    for (int i = 0; i < nsrc; i++)
-        if (!src_keys[i]) return JFS_ERR_INVALID;
-    for (int j = 0; j < nout; j++) {
-        const jfs_seal_param &q = out_p[j];
-        if (!q.key || !q.nonce || q.wrapped_len < 0 || q.wrapped_len > 65535 || (q.wrapped_len > 0 && !q.wrapped))
-            return JFS_ERR_INVALID;
-    }
-    std::vector<DevCtx *> ds;
-    for (DevCtx *d : devices())
-        if (device_mask == 0 || (d->id < 32 && (device_mask >> d->id) & 1u)) ds.push_back(d);
-    if (ds.empty()) return JFS_ERR_NO_DEVICE;
-    const int64_t t0 = steady_ns();
-    // what jfs_open_decompress_batch answers before the device runs
-    std::vector<SealedSrc> ss;
-    std::vector<int> src_map(nsrc, -1);
-    for (int i = 0; i < nsrc; i++) {
-        const jfs_iov &v = src[i];
-        int64_t noff = 0, nlen = 0;
-        const int64_t off = envelope_parse(v.src, v.src_len, nullptr, nullptr, &noff, &nlen);
-        const int64_t pay = v.src_len - off;  // ciphertext || tag
-        if (off < 0 || nlen != 12) src_n[i] = JFS_ERR_CORRUPT;
-        else if (pay < 16) src_n[i] = JFS_ERR_AUTH;
-        else if (algo != JFS_ALGO_NONE && pay == 16) src_n[i] = JFS_ERR_EMPTY_INPUT;
-        else if (algo == JFS_ALGO_NONE && v.dst_cap < pay - 16) src_n[i] = JFS_ERR_SHORT_BUFFER;
-        else {
-            // Zstd: the frame header is ciphertext on the host, so dst_cap is staged (see jfs_open_decompress_batch)
-            src_map[i] = (int)ss.size();
-            ss.push_back({i, off, noff, pay, algo == JFS_ALGO_NONE ? pay - 16 : std::min<int64_t>(v.dst_cap, INT32_MAX)});
-        }
-    }
-    // and what jfs_compress_seal_batch answers for the gathered block
-    std::vector<SealedOut> oo;
-    std::vector<int> own;  // outputs with an error of their own: a failed source still wins (below)
-    for (int j = 0; j < nout; j++) {
-        if (crc) crc[j] = 0;
-        const int64_t bound = jfs_envelope_bound(algo, total[j], out_p[j].wrapped_len);
-        const int64_t hdr = 3 + (int64_t)out_p[j].wrapped_len + 12;
-        bool dead = false;  // a source answered on the host feeds it
-        for (int k = seg_first[j]; k < seg_first[j + 1] && !dead; k++) dead = seg[k].src >= 0 && src_map[seg[k].src] < 0;
-        if (dead) {
-            out_n[j] = JFS_ERR_CORRUPT;
-            continue;
-        }
-        if (bound < 0) out_n[j] = JFS_ERR_INVALID;
-        else if (algo == JFS_ALGO_LZ4 && total[j] > LZ4_MAX_INPUT) out_n[j] = JFS_ERR_COMPRESS_FAIL;
-        else if (out[j].dst_cap < bound) out_n[j] = JFS_ERR_SHORT_BUFFER;
-        else {
-            oo.push_back({j, total[j], bound - hdr - 16, hdr});
-            continue;
-        }
-        own.push_back(j);
-    }
-    int64_t rc = JFS_OK;
-    if (!ss.empty() || !oo.empty()) {
-        DevCtx *dev = ds[g_compact_turn.fetch_add(1) % ds.size()];
-        std::unique_lock<std::mutex> lk;
-        Lane &ln = dev->acquire_lane(lk, algo * 2 + COMPRESS);
-        rc = compact_seal_run(dev, ln, algo, cipher, src, src_keys, ss, src_map, out, out_p, oo, seg_first, seg, src_n,
-                              out_n, crc);
-        if (rc == JFS_ERR_HIP) (void)lane_healthy(dev, ln);  // leave nothing in flight into the staging
-    }
-    if (rc != JFS_OK) {  // the chain did not run: every block it held reports why
-        for (const SealedSrc &s : ss) src_n[s.idx] = rc;
-        for (const SealedOut &o : oo) out_n[o.idx] = rc;
-    } else {
-        for (int j : own)  // a source that failed on the device, or is too short, wins over the block's own error
-            for (int k = seg_first[j]; k < seg_first[j + 1]; k++)
-                if (seg[k].src >= 0 && (int64_t)seg[k].src_off + seg[k].len > src_n[seg[k].src]) out_n[j] = JFS_ERR_CORRUPT;
-    }
-    const uint64_t ns = (uint64_t)(steady_ns() - t0);
-    if (OpStats *st = op_stats(algo, DECOMPRESS)) {
-        st->calls.fetch_add(1, std::memory_order_relaxed);
-        if (!ss.empty()) st->batches.fetch_add(1, std::memory_order_relaxed);
-        for (int i = 0; i < nsrc; i++) stat_block(st, src[i].src_len, src_n[i]);
-    }
-    if (OpStats *st = op_stats(algo, COMPRESS)) {
-        st->calls.fetch_add(1, std::memory_order_relaxed);
-        if (!oo.empty()) st->batches.fetch_add(1, std::memory_order_relaxed);
-        for (int j = 0; j < nout; j++) stat_block(st, total[j], out_n[j]);
-        st->nanos.fetch_add(ns, std::memory_order_relaxed);
-    }
-    return JFS_OK;
+    if (cipher < 0) return JFS_ERR_INVALID;
+    return compact_call(algo, cipher, nsrc, src, src_keys, nout, out, out_p, seg_first, seg, src_n, out_n, crc,
+                        device_mask);
 }
 
 int64_t jfs_read_gather_device(const jfs_dev_block *d_src, const int32_t *d_src_n, int nsrc, const jfs_compact_out *d_out,
@@ -3252,86 +3001,27 @@ static int64_t read_call(int algo, int cipher, int nsrc, const jfs_iov *src, con
         for (int i = 0; i < nsrc; i++)
             if (!src_keys[i]) return JFS_ERR_INVALID;
     }
-    std::vector<DevCtx *> ds;
-    for (DevCtx *d : devices())
-        if (device_mask == 0 || (d->id < 32 && (device_mask >> d->id) & 1u)) ds.push_back(d);
+    const std::vector<DevCtx *> ds = devices_in(device_mask);
     if (ds.empty()) return JFS_ERR_NO_DEVICE;
     const int64_t t0 = steady_ns();
-    // what jfs_decompress_batch / jfs_open_decompress_batch answer before the device runs
-    std::vector<ReadSrc> st, only_crc;
-    std::vector<int> src_map(nsrc, -1);
-    for (int i = 0; i < nsrc; i++) {
-        const jfs_iov &v = src[i];
-        const bool check = src_crc && src_crc[i] >= 0;
-        const uint32_t expect = check ? (uint32_t)src_crc[i] : 0u;
-        if (crc_got) crc_got[i] = 0;
-        ReadSrc r{i, 0, 0, v.src_len, 0, check, expect};
-        bool run = false;
-        if (sealed) {
-            int64_t nlen = 0;
-            r.off = envelope_parse(v.src, v.src_len, nullptr, nullptr, &r.noff, &nlen);
-            r.pay = v.src_len - r.off;  // ciphertext || tag
-            if (r.off < 0 || nlen != 12) src_n[i] = JFS_ERR_CORRUPT;
-            else if (r.pay < 16) src_n[i] = JFS_ERR_AUTH;
-            else if (algo != JFS_ALGO_NONE && r.pay == 16) src_n[i] = JFS_ERR_EMPTY_INPUT;
-            else if (algo == JFS_ALGO_NONE && v.dst_cap < r.pay - 16) src_n[i] = JFS_ERR_SHORT_BUFFER;
-            else {
-                // Zstd: the frame header is ciphertext on the host, so dst_cap is staged (see jfs_open_decompress_batch)
-                r.cap = algo == JFS_ALGO_NONE ? r.pay - 16 : std::min<int64_t>(v.dst_cap, INT32_MAX);
-                run = true;
-            }
-        } else if (algo == JFS_ALGO_NONE ? v.dst_cap < v.src_len : v.src_len == 0) {
-            src_n[i] = algo == JFS_ALGO_NONE ? JFS_ERR_SHORT_BUFFER : JFS_ERR_EMPTY_INPUT;
-        } else {
-            r.cap = algo == JFS_ALGO_NONE ? v.src_len : staged_cap(algo, DECOMPRESS, v);
-            run = true;
-        }
-        if (run) {
-            src_map[i] = (int)st.size();
-            st.push_back(r);
-        } else if (check && v.src_len == 0) {  // an empty object: CRC 0, no device needed
-            if (expect != 0) src_n[i] = JFS_ERR_CHECKSUM;
-        } else if (check) {  // answered above, but verifyChecksum reads the whole object first
-            only_crc.push_back(ReadSrc{i, 0, 0, v.src_len, 0, true, expect});
-        }
-    }
-    const int ns = (int)st.size();
-    st.insert(st.end(), only_crc.begin(), only_crc.end());
-    std::vector<ReadOut> oo;
+    std::vector<ChainSrc> st;
+    std::vector<int> src_map;
+    const int ns = chain_sources(algo, sealed, nsrc, src, src_crc, src_n, crc_got, st, src_map);
+    std::vector<ChainOut> oo;
     for (int j = 0; j < nout; j++) {
-        bool dead = false;  // a source answered on the host feeds it
-        for (int k = seg_first[j]; k < seg_first[j + 1] && !dead; k++) dead = seg[k].src >= 0 && src_map[seg[k].src] < 0;
-        if (dead) out_n[j] = JFS_ERR_CORRUPT;
+        if (jfs_plan::chain_dead(seg_first, seg, j, src_map)) out_n[j] = JFS_ERR_CORRUPT;
         else if (total[j] == 0) out_n[j] = 0;
-        else oo.push_back({j, total[j]});
+        else oo.push_back({j, total[j], total[j], 0, 0});
     }
     // prefix mode (LZ4): the last byte the plan asks of every object
     std::vector<int64_t> need;
-    if (algo == JFS_ALGO_LZ4 && read_decode().load(std::memory_order_relaxed) == JFS_READ_DECODE_PREFIX) {
-        need.assign(nsrc, 0);
-        for (int j = 0; j < nout; j++)
-            for (int k = seg_first[j]; k < seg_first[j + 1]; k++)
-                if (seg[k].src >= 0) need[seg[k].src] = std::max(need[seg[k].src], (int64_t)seg[k].src_off + seg[k].len);
-    }
-    int64_t rc = JFS_OK;
-    if (!st.empty() || !oo.empty()) {
-        DevCtx *dev = ds[g_compact_turn.fetch_add(1) % ds.size()];
-        std::unique_lock<std::mutex> lk;
-        Lane &ln = dev->acquire_lane(lk, algo * 2 + DECOMPRESS);
-        rc = read_run(dev, ln, algo, cipher, src, src_keys, st, ns, src_map, out, oo, seg_first, seg, src_n, out_n,
-                      crc_got, need.empty() ? nullptr : need.data());
-        if (rc == JFS_ERR_HIP) (void)lane_healthy(dev, ln);  // leave nothing in flight into the staging
-    }
-    if (rc != JFS_OK) {  // the chain did not run: every object it held reports why
-        for (const ReadSrc &s : st) src_n[s.idx] = rc;
-        for (const ReadOut &o : oo) out_n[o.idx] = rc;
-    }
-    if (OpStats *os = op_stats(algo, DECOMPRESS)) {
-        os->calls.fetch_add(1, std::memory_order_relaxed);
-        if (ns > 0) os->batches.fetch_add(1, std::memory_order_relaxed);
-        for (int i = 0; i < nsrc; i++) stat_block(os, src[i].src_len, src_n[i]);
-        os->nanos.fetch_add((uint64_t)(steady_ns() - t0), std::memory_order_relaxed);
-    }
+    if (algo == JFS_ALGO_LZ4 && read_decode().load(std::memory_order_relaxed) == JFS_READ_DECODE_PREFIX)
+        need = jfs_plan::chain_need(nsrc, nout, seg_first, seg);
+    chain_dispatch(ds, algo, DECOMPRESS, st, oo, src_n, out_n, [&](DevCtx *dev, Lane &ln) {
+        return read_run(dev, ln, algo, cipher, src, src_keys, st, ns, src_map, out, oo, seg_first, seg, src_n, out_n,
+                        crc_got, need.empty() ? nullptr : need.data());
+    });
+    chain_stat(algo, DECOMPRESS, nsrc, [&](int i) { return src[i].src_len; }, src_n, ns > 0, steady_ns() - t0);
     return JFS_OK;
 }
 

@@ -329,3 +329,70 @@ def test_compact_batch_matches_parent_abi(gpu, lib, oracle, raws, name):
     for j in (0, 2, 3):
         n, e, crc = ref[j]
         assert ores[j] == (n, None) and crcs[j] == crc and bytes(dst[j][:n]) == bytes(ref_dst[j][:n]), j
+
+
+def _codes(res):
+    return [(n, e.code if e else None) for n, e in res]
+
+
+@pytest.mark.parametrize("name", ["lz4", "zstd", "none"])
+def test_degenerate_plans(gpu, lib, name):
+    """Plans that leave one side of the chain, or all of it, without work."""
+    c = C.NewCompressor(name)
+    lens = [3000, 4097, 5001]
+    small = [np.frombuffer(gen_block("T", 950 + i, n), dtype=np.uint8) for i, n in enumerate(lens)]
+    stored = []
+    for r in small:
+        d = bytearray(c.CompressBound(len(r)))
+        n, e = c.CompressBatch([(d, r)])[0]
+        assert e is None
+        stored.append(bytes(d[:n]))
+
+    def reference(blocks):
+        dst = [bytearray(c.CompressBound(len(b))) for b in blocks]
+        res = c.CompressBatchChecksum(list(zip(dst, blocks)))
+        assert all(e is None for _, e, _ in res)
+        return [(bytes(d[:n]), crc) for d, (n, _, crc) in zip(dst, res)]
+
+    def compact(objs, caps, plan, blocks):
+        dst = [bytearray(c.CompressBound(len(b))) for b in blocks]
+        back = c.DecompressBatch([(bytearray(n), s) for n, s in zip(caps, objs)]) if objs else []
+        lib.jfs_stats_reset()
+        sres, ores, crcs = c.CompactBatch(list(zip(objs, caps)), dst, plan, with_crc=True)
+        assert _codes(sres) == _codes(back)
+        return dst, sres, ores, crcs
+
+    # sources and no outputs: the sources are still decoded
+    _, sres, ores, crcs = compact(stored, lens, ([0], []), [])
+    assert _codes(sres) == [(n, None) for n in lens] and ores == [] and crcs == []
+    # no sources: an output made of holes, one without a segment, one of a single hole byte
+    plan = ([0, 2, 2, 3], [(-1, 0, 0, 1000), (-1, 0, 1000, 37), (-1, 0, 0, 1)])
+    blocks = [bytes(1037), b"", bytes(1)]
+    ref = reference(blocks)
+    dst, sres, ores, crcs = compact([], [], plan, blocks)
+    assert sres == []
+    for j, (want, crc) in enumerate(ref):
+        assert ores[j] == (len(want), None) and crcs[j] == crc and bytes(dst[j][:len(want)]) == want, j
+    # the same outputs beside sources that nothing reads, and one that reads them
+    seg = plan[1] + [(2, 5000, 0, 1), (-1, 0, 1, 15), (0, 1, 16, 2999)]
+    blocks.append(_expected(small, seg[3:]).tobytes())
+    ref = reference(blocks)
+    dst, sres, ores, crcs = compact(stored, lens, ([0, 2, 2, 3, 6], seg), blocks)
+    assert _codes(sres) == [(n, None) for n in lens]
+    for j, (want, crc) in enumerate(ref):
+        assert ores[j] == (len(want), None) and crcs[j] == crc and bytes(dst[j][:len(want)]) == want, j
+    # every source answered on the host: every output fails, and no device work is queued
+    if name == "none":
+        objs, caps = stored, [n - 1 for n in lens]  # noOp.Decompress: "buffer too short"
+    else:
+        objs, caps = [b""] * 3, lens  # "decompress an empty input"
+    plan = ([0, 1, 3], [(0, 0, 0, 10), (1, 0, 0, 10), (2, 0, 10, 10)])
+    dst, sres, ores, crcs = compact(objs, caps, plan, [bytes(10), bytes(20)])
+    assert all(e is not None for _, e in sres)
+    assert [e.code for _, e in ores] == [L.JFS_ERR_CORRUPT] * 2 and crcs == [0, 0]
+    assert all(not any(d) for d in dst)
+    dec, enc = _stat(lib, c.algo, 1), _stat(lib, c.algo, 0)
+    assert (dec.calls, dec.blocks, dec.errors, dec.batches) == (1, 3, 3, 0)
+    assert (enc.calls, enc.blocks, enc.errors, enc.batches) == (1, 2, 2, 0)
+    # neither
+    assert c.CompactBatch([], [], ([0], []), with_crc=True) == ([], [], [])
