@@ -65,6 +65,9 @@ enum { IT_SEQ = 0, IT_FSTART = 1, IT_FEND = 2, IT_BSTART = 3, IT_BEND = 4, IT_ER
 // state at the start of the block (IT_BREP item).  Composition of libzstd's
 // "rep0 - 1, and 0 becomes 1" steps is exactly max(1, x - d).
 constexpr uint32_t SYMB = 0x80000000u;
+// Item offset of a sequence with offset code 31: its real offset is >= 2^31 - 3, past any output (cap is int32),
+// and would carry SYMB.  Not symbolic, and beyond the output for every replay's offset check.
+constexpr uint32_t OFF_BEYOND = 0x7FFFFFFFu;
 enum { FE_FCS = 1, FE_CHECK = 2, FE_MISSING = 4 };
 constexpr uint32_t ZSTD_MAGIC = 0xFD2FB528u;
 constexpr int32_t BLOCK_MAX = 128 << 10;
@@ -1546,6 +1549,7 @@ __device__ __forceinline__ void zvalues(SeqSmem &sm, int gn, int b) {
             const uint32_t lv = sm.lut_ll[cl & 63], mv = sm.lut_ml[cm & 63], ofc = co & 63;
             int32_t c = 0;
             ofv = (1u << ofc) + zw_get(hi, c, ofc);
+            if (ofc == 31) ofv = OFF_BEYOND + 3u;  // the item offset is ofv - 3
             ml = (mv & 0xFFFFFFu) + zw_get(hi, c, mv >> 24);
             ll = (lv & 0xFFFFFFu) + zw_get(hi, c, lv >> 24);
         }

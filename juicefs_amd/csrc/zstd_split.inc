@@ -513,6 +513,7 @@ __global__ __launch_bounds__(128) void zsblk_kernel(const jfs_dev_block *__restr
             int32_t c = 0;
             const uint32_t ofc = bo >> 24;
             ofv = (1u << ofc) + sget(hi, c, ofc);
+            if (ofc == 31) ofv = OFF_BEYOND + 3u;  // as zvalues: the item offset is ofv - 3
             ml = (bm & 0xFFFFFFu) + sget(hi, c, bm >> 24);
             ll = (bl & 0xFFFFFFu) + sget(hi, c, bl >> 24);
         }

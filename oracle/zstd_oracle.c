@@ -24,12 +24,18 @@
 #define ZO_ERR_DSTSMALL (-2)
 #define ZO_ERR_SRCSIZE (-3)
 
-/* Symbol_Compression_Modes reserved bits (RFC 8878 3.1.1.3.2.1 "must be
- * all-zeroes"): zstd >= 1.5 (the reference pins 1.5.6) rejects them, 1.4.9
- * (the library the golden corpus was generated with) ignores them.  Default:
- * reject, like the pinned version; tests flip it to pin against 1.4.9. */
-static int zo_strict_reserved = 1;
-void oracle_zstd_set_strict_reserved(int on) { zo_strict_reserved = on; }
+/* Two rules that zstd >= 1.5 (the reference pins 1.5.6) enforces and 1.4.9
+ * (the library the golden fixtures were generated with) does not:
+ *   - the reserved bits of the Symbol_Compression_Modes byte are zero
+ *     (RFC 8878 3.1.1.3.2.1);
+ *   - a sequence bitstream is consumed exactly: no bit is left unread.
+ * zo_strict = 1 (default) enforces both, like the pinned version; tests set
+ * it to 0 to pin against 1.4.9.  A stream that is over-read stays corrupt in
+ * both modes: 1.4.9 accepts it too, but what it then decodes depends on its
+ * bit container's wrap-around, which is not restated here.  (The setter
+ * keeps its first name; it predates the second rule.) */
+static int zo_strict = 1;
+void oracle_zstd_set_strict_reserved(int on) { zo_strict = on; }
 
 /* ---------------------------------------------------------------- XXH64 */
 static const uint64_t P1 = 11400714785074694791ULL, P2 = 14029467366897019727ULL, P3 = 1609587929392839161ULL,
@@ -351,6 +357,7 @@ static int64_t zo_block(zo_state *st, const uint8_t *src, int64_t n, uint8_t *ds
         if (sf == 0 || sf == 2) { regen = src[0] >> 3; hsz = 1; }
         else if (sf == 1) { if (n < 2) return ZO_ERR_CORRUPT; regen = (src[0] >> 4) | (src[1] << 4); hsz = 2; }
         else { if (n < 3) return ZO_ERR_CORRUPT; regen = (src[0] >> 4) | (src[1] << 4) | ((int64_t)src[2] << 12); hsz = 3; }
+        if (regen > (128 << 10)) return ZO_ERR_CORRUPT;  /* litSize > ZSTD_BLOCKSIZE_MAX (and litbuf's size) */
         if (ltype == 0) {
             if (hsz + regen > n) return ZO_ERR_CORRUPT;
             memcpy(litbuf, src + hsz, regen);
@@ -421,7 +428,7 @@ static int64_t zo_block(zo_state *st, const uint8_t *src, int64_t n, uint8_t *ds
     if (nseq > 0) {
         if (ip >= n) return ZO_ERR_SRCSIZE;
         int modes = src[ip++];
-        if ((modes & 3) && zo_strict_reserved) return ZO_ERR_CORRUPT;
+        if ((modes & 3) && zo_strict) return ZO_ERR_CORRUPT;
         int64_t c;
         c = seq_table(&st->ll, &st->have_ll, modes >> 6, src + ip, n - ip, LL_DEF, 35, 6, 35, 9);
         if (c < 0) return ZO_ERR_CORRUPT;
@@ -476,7 +483,8 @@ static int64_t zo_block(zo_state *st, const uint8_t *src, int64_t n, uint8_t *ds
             for (uint64_t k2 = 0; k2 < ml; k2++) dst[op + k2] = dst[op - off + k2];
             op += ml;
         }
-        if (!bbr_done(&b)) return ZO_ERR_CORRUPT;
+        /* zstd >= 1.5 wants the stream consumed exactly; 1.4.9 never looks at unread bits */
+        if (!bbr_done(&b) && (zo_strict || bbr_overflow(&b))) return ZO_ERR_CORRUPT;
     } else if (ip != n) {
         return ZO_ERR_SRCSIZE;
     }
