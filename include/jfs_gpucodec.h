@@ -170,6 +170,15 @@ int64_t jfs_compress_seal_batch(int algo, int cipher, int nblk, const jfs_iov *i
                                 int64_t *out_n, uint32_t *crc, uint32_t device_mask);
 int64_t jfs_open_decompress_batch(int algo, int cipher, int nblk, const jfs_iov *iov, const uint8_t *const *keys,
                                   int64_t *out_n, uint32_t device_mask);
+/* jfs_open_decompress_batch plus the disk-cache checksum of every opened and
+ * decoded block, with jfs_decompress_batch_csum's contract for csum (NULL with
+ * nblk > 0: JFS_ERR_INVALID; csum[i] may be NULL; csum[i] must hold
+ * ((dst_cap-1)/32768+1)*4 bytes; nothing is written for a block that fails, a
+ * block whose tag does not verify included): the warm-up path
+ * (pkg/vfs/fill.go:93) of an encrypted volume.  Everything else is
+ * jfs_open_decompress_batch's. */
+int64_t jfs_open_decompress_batch_csum(int algo, int cipher, int nblk, const jfs_iov *iov, const uint8_t *const *keys,
+                                       int64_t *out_n, uint8_t *const *csum, uint32_t device_mask);
 
 /* ---- Device-resident surface (inputs/outputs already in HBM) ------------
  * One descriptor per block; all pointers are device pointers on the calling
@@ -499,6 +508,20 @@ int64_t jfs_read_gather_device(const jfs_dev_block *d_src, const int32_t *d_src_
                                const int32_t *dst_cap, int nout, const jfs_compact_seg *d_seg, int32_t *d_ret,
                                void *stream);
 
+/* The disk-cache checksums of gathered reads, device-resident: behind
+ * jfs_read_gather_device on the same stream, for every read j whose verdict
+ * d_ret[j] is its d_out[j].dst_cap (> 0), the big-endian CRC-32C of every
+ * 32 KiB piece of d_out[j].dst[0, dst_cap), one piece per workgroup on a
+ * one-dimensional grid.  d_piece_first (device, nout + 1 entries) is the
+ * running sum of the reads' piece counts, (dst_cap-1)/32768+1, or 0 for a read
+ * that wants no checksum; npiece is its last entry, a HOST value (it sizes the
+ * launch).  Piece p of the call writes d_csum[4p .. 4p+4) (d_csum 4-byte
+ * aligned, 4 npiece bytes), so read j's checksum starts at
+ * 4 d_piece_first[j]; nothing is written for any other read.  Asynchronous on
+ * `stream`. */
+int64_t jfs_read_csum_device(const jfs_compact_out *d_out, const int32_t *d_ret, int nout, const int32_t *d_piece_first,
+                             int64_t npiece, uint8_t *d_csum, void *stream);
+
 /* Host buffers (what a Go dataReader.Read adapter calls).  Sources as for
  * jfs_compact_batch: src[i].src/src_len the stored object, src[i].dst_cap its
  * block size, src[i].dst ignored.  out[j].dst/dst_cap receives the raw
@@ -536,6 +559,31 @@ int64_t jfs_read_open_batch(int algo, int cipher, int nsrc, const jfs_iov *src, 
                             const int64_t *src_crc /* may be NULL */, int nout, const jfs_iov *out,
                             const int32_t *seg_first /* nout+1 */, const jfs_compact_seg *seg, int64_t *src_n,
                             int64_t *out_n, uint32_t *crc_got /* nsrc, may be NULL */, uint32_t device_mask);
+
+/* jfs_read_batch / jfs_read_open_batch plus, for every read j with
+ * csum[j] != NULL, the disk-cache checksum of its gathered bytes (holes
+ * included) -- what cachedStore.load hands to the block cache with a decoded
+ * block (cached_store.go:819-821, disk_cache.go:536-537): the big-endian
+ * CRC-32C of every 32 KiB piece, ((n-1)/32768+1)*4 bytes for n = out_n[j]
+ * (4 zero bytes for n = 0), computed on the device behind the gather and
+ * returned in the same copy as the reads.  For a read that is one whole block
+ * (src_off = 0, len = the block's size) these are the bytes
+ * jfs_decompress_batch_csum writes for that block, so one call serves the
+ * reads and fills the cache.  csum has nout entries; csum[j] must hold that
+ * many bytes for the read's planned total; nothing is written for a failed
+ * read (out_n[j] < 0) or a NULL entry.  A NULL csum with nout > 0 is
+ * JFS_ERR_INVALID.  Everything else -- src_n, out_n, crc_got, the bytes, the
+ * precedence of verdicts, the decode mode, jfs_stats, the device choice and the
+ * scratch failure policy -- is the call's without _csum. */
+int64_t jfs_read_batch_csum(int algo, int nsrc, const jfs_iov *src, const int64_t *src_crc /* may be NULL */, int nout,
+                            const jfs_iov *out, const int32_t *seg_first /* nout+1 */, const jfs_compact_seg *seg,
+                            int64_t *src_n, int64_t *out_n, uint32_t *crc_got /* nsrc, may be NULL */,
+                            uint8_t *const *csum /* nout */, uint32_t device_mask);
+int64_t jfs_read_open_batch_csum(int algo, int cipher, int nsrc, const jfs_iov *src, const uint8_t *const *src_keys,
+                                 const int64_t *src_crc /* may be NULL */, int nout, const jfs_iov *out,
+                                 const int32_t *seg_first /* nout+1 */, const jfs_compact_seg *seg, int64_t *src_n,
+                                 int64_t *out_n, uint32_t *crc_got /* nsrc, may be NULL */,
+                                 uint8_t *const *csum /* nout */, uint32_t device_mask);
 
 /* Decode mode of jfs_read_batch and jfs_read_open_batch.  JFS_READ_DECODE_FULL
  * (default) decodes every source whole: the calls are what they were before

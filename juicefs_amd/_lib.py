@@ -45,6 +45,8 @@ EXPORTS = [
     "jfs_read_gather_device", "jfs_read_batch", "jfs_read_open_batch",
     "jfs_lz4_decompress_prefix_device", "jfs_lz4_decompress_prefix_device_small",
     "jfs_read_decode_mode", "jfs_set_read_decode_mode",
+    "jfs_read_batch_csum", "jfs_read_open_batch_csum", "jfs_open_decompress_batch_csum",
+    "jfs_read_csum_device",
 ]
 # the hook include/jfs_gpucodec_lz4_fast_test.h declares (the fast LZ4 encoder's host twin)
 LZ4_FAST_TEST_EXPORTS = ["jfs_test_lz4_fast_host"]
@@ -219,6 +221,16 @@ def load() -> ctypes.CDLL:
                                         ctypes.POINTER(JfsIov), ctypes.POINTER(i32), ctypes.POINTER(JfsCompactSeg),
                                         ctypes.POINTER(i64), ctypes.POINTER(i64), vp, u32]
     lib.jfs_read_open_batch.restype = i64
+    lib.jfs_read_csum_device.argtypes = [vp, vp, ctypes.c_int, vp, i64, vp, vp]
+    lib.jfs_read_csum_device.restype = i64
+    lib.jfs_read_batch_csum.argtypes = lib.jfs_read_batch.argtypes[:-1] + [ctypes.POINTER(ctypes.c_void_p), u32]
+    lib.jfs_read_batch_csum.restype = i64
+    lib.jfs_read_open_batch_csum.argtypes = lib.jfs_read_open_batch.argtypes[:-1] + [ctypes.POINTER(ctypes.c_void_p),
+                                                                                     u32]
+    lib.jfs_read_open_batch_csum.restype = i64
+    lib.jfs_open_decompress_batch_csum.argtypes = lib.jfs_open_decompress_batch.argtypes[:-1] + [
+        ctypes.POINTER(ctypes.c_void_p), u32]
+    lib.jfs_open_decompress_batch_csum.restype = i64
     lib.jfs_release_staging.argtypes = []
     lib.jfs_release_staging.restype = None
     lib.jfs_device_count.argtypes = []

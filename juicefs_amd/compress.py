@@ -182,7 +182,7 @@ class Compressor:
             return src_res, out_res, [int(crc[j]) for j in range(no)]
         return src_res, out_res
 
-    def ReadBatch(self, sources, reads, plan, crcs=None, device_mask: int = 0):
+    def ReadBatch(self, sources, reads, plan, crcs=None, device_mask: int = 0, with_csum=False):
         """Read assembly on one GPU (jfs_read_batch): check the stored source
         objects against their CRC-32C, decode them and gather the planned byte
         ranges, so that only the requested bytes come back over the host link.
@@ -195,8 +195,15 @@ class Compressor:
         ("verify checksum failed" where the CRC differs), [(n, err)] per read
         (JFS_ERR_CORRUPT for a read fed by a failed or short source; its dst is
         untouched) and the computed CRC of every source that had an expected
-        one.  read_expect gives the bytes a good read holds."""
-        return _read_call(self.algo, None, sources, None, reads, plan, crcs, device_mask)
+        one.  read_expect gives the bytes a good read holds.
+
+        with_csum (jfs_read_batch_csum): True, or per read True, False / None
+        or a writable buffer of csum_bytes(total) bytes that receives the
+        checksum in place.  The result gains a fourth list: per read its
+        disk-cache checksum bytes (the big-endian CRC-32C of every 32 KiB
+        piece, csum_bytes(n) bytes), None for a failed read and for a read
+        that asked for none."""
+        return _read_call(self.algo, None, sources, None, reads, plan, crcs, device_mask, with_csum)
 
 
 class noOp(Compressor):  # noqa: N801  (reference name, compress.go:51)
@@ -452,8 +459,9 @@ def read_expect(decoded_sources, plan):
     return outs
 
 
-def _read_call(algo: int, cipher, sources, keys, reads, plan, crcs, device_mask: int):
-    """jfs_read_batch (cipher None) / jfs_read_open_batch over host buffers"""
+def _read_call(algo: int, cipher, sources, keys, reads, plan, crcs, device_mask: int, with_csum=False):
+    """jfs_read_batch (cipher None) / jfs_read_open_batch over host buffers;
+    with_csum (True, or one flag per read): their _csum forms"""
     lib = L.load()
     seg_first, seg = plan
     ns, no = len(sources), len(reads)
@@ -485,11 +493,36 @@ def _read_call(algo: int, cipher, sources, keys, reads, plan, crcs, device_mask:
         want = (ctypes.c_int64 * max(ns, 1))(*[-1 if c is None else int(c) for c in crcs])
     src_n, out_n = (ctypes.c_int64 * max(ns, 1))(), (ctypes.c_int64 * max(no, 1))()
     got = (ctypes.c_uint32 * max(ns, 1))()
-    if cipher is None:
+    cs_bufs = None
+    if with_csum is not False and with_csum is not None:
+        flags = [True] * no if with_csum is True else list(with_csum)
+        if len(flags) != no:
+            raise ValueError("one checksum flag (or buffer) per read")
+        cs_bufs, cs_ptrs = [], (ctypes.c_void_p * max(no, 1))()
+        for j, f in enumerate(flags):
+            need = csum_bytes(sum(s[3] for s in seg[seg_first[j]:seg_first[j + 1]]))
+            if f is None or f is False:
+                cs_bufs.append(None)
+                continue
+            if f is True:
+                f = bytearray(need)
+            p, pn, kp_ = _addr(f, True)
+            if pn < need:
+                raise ValueError(f"read {j}: its checksum needs {need} bytes, the buffer holds {pn}")
+            keep.append(kp_)
+            cs_bufs.append(f)
+            cs_ptrs[j] = p.value if isinstance(p, ctypes.c_void_p) else p
+    if cipher is None and cs_bufs is None:
         rc = lib.jfs_read_batch(algo, ns, siov, want, no, oiov, first, segs, src_n, out_n, got, device_mask)
-    else:
+    elif cipher is None:
+        rc = lib.jfs_read_batch_csum(algo, ns, siov, want, no, oiov, first, segs, src_n, out_n, got, cs_ptrs,
+                                     device_mask)
+    elif cs_bufs is None:
         rc = lib.jfs_read_open_batch(algo, cipher, ns, siov, kp, want, no, oiov, first, segs, src_n, out_n, got,
                                      device_mask)
+    else:
+        rc = lib.jfs_read_open_batch_csum(algo, cipher, ns, siov, kp, want, no, oiov, first, segs, src_n, out_n, got,
+                                          cs_ptrs, device_mask)
     if rc != 0:
         raise _err(rc, 0, 0, "read")
 
@@ -511,7 +544,12 @@ def _read_call(algo: int, cipher, sources, keys, reads, plan, crcs, device_mask:
     for j in range(no):
         r = int(out_n[j])
         out_res.append((0, err_of(r, oiov[j].dst_cap, 0, "read")) if r < 0 else (r, None))
-    return src_res, out_res, [int(got[i]) for i in range(ns)]
+    crc_got = [int(got[i]) for i in range(ns)]
+    if cs_bufs is None:
+        return src_res, out_res, crc_got
+    sums = [bytes(memoryview(cs_bufs[j]).cast("B")[:csum_bytes(n)]) if e is None and cs_bufs[j] is not None else None
+            for j, (n, e) in enumerate(out_res)]
+    return src_res, out_res, crc_got, sums
 
 
 CSUM_BLOCK = 32 << 10  # disk_cache_file.go csBlock

@@ -887,7 +887,7 @@ struct BatchRun {
     BatchRun(DevCtx *dev, Lane &ln, int algo, int dir, int nblk, const jfs_iov *iov, int64_t *out, const Aead *ae,
              uint32_t *crc_out, int max_chunk_blocks, uint8_t *const *csum)
         : dev(dev), ln(ln), other(dev->lane[(&ln - dev->lane + 1) % NLANE]), algo(algo), dir(dir), iov(iov), out(out),
-          ae(ae), crc_out(crc_out), csum_out(dir == DECOMPRESS && !ae ? csum : nullptr),
+          ae(ae), crc_out(crc_out), csum_out(dir == DECOMPRESS ? csum : nullptr),
           zplan(algo == JFS_ALGO_ZSTD && dir == DECOMPRESS && !ae), zib(zplan ? (int64_t)jfs_zstd_info_bytes() : 0),
           lz4_fast(lz4_fast_mode()), zparse(zstd_parse_now()), blk(nblk) {
         for (int i = 0; i < nblk; i++) blk[i] = {iov[i].src_len, ae ? iov[i].dst_cap : staged_cap(algo, dir, iov[i])};
@@ -1113,6 +1113,7 @@ struct BatchRun {
         if (!h2d(d_desc, h_desc, (int64_t)n * (int64_t)sizeof(jfs_dev_block))) return JFS_ERR_HIP;
         if (!h2d(d_ad, h_ad, L.aead_bytes)) return JFS_ERR_HIP;
         if (!stage_crc(c, L, sl)) return JFS_ERR_HIP;
+        if (!stage_csum(c, L, sl)) return JFS_ERR_HIP;
         if (hipEventRecord(sl.ev_in, dev->s_in) != hipSuccess) return JFS_ERR_HIP;
         if (hipStreamWaitEvent(ks, sl.ev_in, 0) != hipSuccess) return JFS_ERR_HIP;
         int64_t r = JFS_OK;
@@ -1131,11 +1132,15 @@ struct BatchRun {
         }
         if (r != JFS_OK) return r;
         if (ae->seal && !run_crc(c, L, sl, d_r2, ks)) return JFS_ERR_HIP;
+        // the opened block's checksums: its length is the codec's result, for "none" the open's
+        // (a failed open's zeros may decode: finish() hands out nothing for it)
+        if (!run_csum(c, L, sl, algo == JFS_ALGO_NONE ? d_r2 : d_ret, ks)) return JFS_ERR_HIP;
         if (hipEventRecord(sl.ev_k, ks) != hipSuccess) return JFS_ERR_HIP;
         if (hipStreamWaitEvent(dev->s_out, sl.ev_k, 0) != hipSuccess) return JFS_ERR_HIP;
         if (!d2h(Layout::at(sl.h, L.ret), d_ret, (int64_t)n * 4)) return JFS_ERR_HIP;
         if (!d2h(Layout::at(sl.h, L.aead_ret), d_r2, (int64_t)n * 4)) return JFS_ERR_HIP;
         if (ae->seal && !fetch_crc(c, L, sl)) return JFS_ERR_HIP;
+        if (!fetch_csum(L, sl)) return JFS_ERR_HIP;
         if (!d2h(Layout::at(sl.h, L.out), d_out, c.tout)) return JFS_ERR_HIP;
         if (hipEventRecord(sl.ev, dev->s_out) != hipSuccess) return JFS_ERR_HIP;
         return JFS_OK;
@@ -1767,7 +1772,8 @@ int64_t deal(int algo, int dir, const std::vector<int> &todo, const std::vector<
         if (ae_all) {
             Aead a{ae_all->cipher, ae_all->seal, p.orig.data(), p.key.data(), p.nonce.data(),
                    ae_all->sp ? p.sp.data() : nullptr, ae_all->hdr ? p.hdr.data() : nullptr};
-            run_isolated(ds[g], ln, algo, dir, (int)p.iov.size(), p.iov.data(), p.res.data(), &a, pc);
+            run_isolated(ds[g], ln, algo, dir, (int)p.iov.size(), p.iov.data(), p.res.data(), &a, pc,
+                         csum ? p.csum.data() : nullptr);
         } else {
             run_isolated(ds[g], ln, algo, dir, (int)p.iov.size(), p.iov.data(), p.res.data(), nullptr, pc,
                          csum ? p.csum.data() : nullptr);
@@ -1824,8 +1830,8 @@ int64_t batch_common(int algo, int dir, int nblk, const jfs_iov *iov, int64_t *o
 // the on-device chains, one device and one lane per call:
 //   compaction     (open ->) decode -> gather -> encode (-> seal)
 //                  jfs_compact_batch, jfs_compact_seal_batch
-//   read assembly  verify -> (open ->) decode -> gather
-//                  jfs_read_batch, jfs_read_open_batch
+//   read assembly  verify -> (open ->) decode -> gather (-> the reads' checksums)
+//                  jfs_read_batch, jfs_read_open_batch and their _csum forms
 // cipher < 0: no envelopes.  The planning arithmetic is chain_plan.h's.
 // ---------------------------------------------------------------------------
 using jfs_plan::ChainFlags;
@@ -1861,7 +1867,7 @@ struct Chain {
 // Lays the call out and sizes slot 0 for it: JFS_OK or JFS_ERR_NO_MEMORY.
 int64_t chain_open(Chain &c, Lane &ln, int algo, int cipher, const std::vector<ChainSrc> &st, int ns,
                    const std::vector<ChainOut> &oo, const int32_t *seg_first, bool encode, bool out_crc, bool src_crc,
-                   bool prefix) {
+                   bool prefix, int64_t npiece = 0) {
     c.algo = algo;
     c.cipher = cipher;
     c.ns = ns;
@@ -1873,7 +1879,8 @@ int64_t chain_open(Chain &c, Lane &ln, int algo, int cipher, const std::vector<C
     c.off = jfs_plan::chain_offsets(st, ns, oo, c.codec, encode);
     int64_t nseg = 0;
     for (const ChainOut &o : oo) nseg += seg_first[o.idx + 1] - seg_first[o.idx];
-    c.L = ChainLayout(c.off.tin, ns, c.n, c.no, nseg, ChainFlags{c.sealed, encode, out_crc, src_crc, prefix});
+    c.L = ChainLayout(c.off.tin, ns, c.n, c.no, nseg, ChainFlags{c.sealed, encode, out_crc, src_crc, prefix, npiece > 0},
+                      npiece);
     c.sl = &ln.slot[0];
     c.s1 = &ln.slot[1];
     c.ks = ln.s_k;
@@ -2103,10 +2110,16 @@ int64_t compact_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *
 // (clamped to its capacity, staged behind the expected checksums in the same
 // H2D copy) unless every source is needed whole, which takes the full
 // launchers.
+// csum (the _csum calls, else null): per read of the call, where its
+// disk-cache checksum goes (null: none).  The piece prefix of the reads that
+// want one is staged with the plan, read_csum_flat_kernel runs behind the
+// gather on the same stream, and the checksum area comes back in front of the
+// reads in the same D2H copy.  A call without such a read is laid out and
+// queued exactly like one without csum.
 int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src, const uint8_t *const *src_keys,
                  const std::vector<ChainSrc> &st, int ns, const std::vector<int> &src_map, const jfs_iov *out,
                  const std::vector<ChainOut> &oo, const int32_t *seg_first, const jfs_compact_seg *seg, int64_t *src_n,
-                 int64_t *out_n, uint32_t *crc_got, const int64_t *need) {
+                 int64_t *out_n, uint32_t *crc_got, const int64_t *need, uint8_t *const *csum) {
     LaneRun scope(dev, ln, algo * 2 + DECOMPRESS, (uint64_t)st.size());
     const int n = (int)st.size(), no = (int)oo.size();
     bool any_check = false;
@@ -2121,11 +2134,21 @@ int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src
     tile_first[no] = (int32_t)ntiles;
     if (need && algo == JFS_ALGO_LZ4) want = jfs_plan::chain_want(need, st, ns, &max_want);
     const bool prefix = !want.empty();
+    std::vector<uint8_t> cs_want(no, 0);
+    std::vector<int32_t> piece_first;
+    std::vector<int64_t> cs_off;
+    int64_t npiece = 0;
+    if (csum) {
+        for (int k = 0; k < no; k++) cs_want[k] = csum[oo[k].idx] != nullptr;
+        npiece = jfs_plan::chain_csum_pieces(oo, cs_want, piece_first, cs_off);
+        if (npiece < 0) return JFS_ERR_NO_MEMORY;
+    }
     Chain c;
-    const int64_t rc = chain_open(c, ln, algo, cipher, st, ns, oo, seg_first, false, false, any_check, prefix);
+    const int64_t rc = chain_open(c, ln, algo, cipher, st, ns, oo, seg_first, false, false, any_check, prefix, npiece);
     if (rc != JFS_OK) return rc;
     const ChainLayout &L = c.L;
     memcpy(c.h + L.tf, tile_first.data(), (size_t)(no + 1) * 4);
+    if (npiece > 0) memcpy(c.h + L.pf, piece_first.data(), (size_t)(no + 1) * 4);
     if (prefix) memcpy(c.h + L.want, want.data(), (size_t)ns * 4);
     std::vector<CopyJob> jobs;
     chain_stage_sources(c, src, src_keys, st, jobs);
@@ -2158,7 +2181,10 @@ int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src
         lk = jfs_launch_gather_flat(c.dev<jfs_dev_block>(L.sdesc), d_srcn, ns + 1, c.dev<jfs_compact_out>(L.plan), no,
                                     c.dev<jfs_compact_seg>(L.seg), c.dev<int32_t>(L.ret), c.dev<int32_t>(L.tf), ntiles,
                                     ks);
-    // one D2H: the results and every read, packed
+    if (lk == 0 && npiece > 0)
+        lk = jfs_launch_read_csum_flat(c.dev<jfs_compact_out>(L.plan), no, c.dev<int32_t>(L.ret), c.dev<int32_t>(L.pf),
+                                       npiece, c.dev<uint32_t>(L.csum), ks);
+    // one D2H: the results, the checksums and every read, packed
     if (!chain_results(c, lk, L.out + c.off.tout)) return JFS_ERR_HIP;
     for (int k = 0; k < n; k++) {
         const ChainSrc &s = st[k];
@@ -2172,6 +2198,7 @@ int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src
         const int j = oo[k].idx;
         out_n[j] = chain_out_result(algo, false, c.host<int32_t>(L.ret)[k]);
         if (out_n[j] > 0) jobs.push_back({out[j].dst, c.h_out(k), out_n[j]});
+        if (out_n[j] > 0 && cs_want[k]) jobs.push_back({csum[j], c.h + L.csum + cs_off[k], 4 * jfs_plan::csum_pieces(out_n[j])});
     }
     par_copy(jobs);
     return JFS_OK;
@@ -2440,8 +2467,9 @@ int64_t jfs_compress_seal_batch(int algo, int cipher, int nblk, const jfs_iov *i
     return rc;
 }
 
-int64_t jfs_open_decompress_batch(int algo, int cipher, int nblk, const jfs_iov *iov, const uint8_t *const *keys,
-                                  int64_t *out_n, uint32_t device_mask) {
+// jfs_open_decompress_batch (csum null) and jfs_open_decompress_batch_csum
+static int64_t open_batch_call(int algo, int cipher, int nblk, const jfs_iov *iov, const uint8_t *const *keys,
+                               int64_t *out_n, uint32_t device_mask, uint8_t *const *csum) {
     if (nblk < 0 || (nblk > 0 && (!iov || !out_n || !keys))) return JFS_ERR_INVALID;
     if (algo != JFS_ALGO_NONE && algo != JFS_ALGO_LZ4 && algo != JFS_ALGO_ZSTD) return JFS_ERR_INVALID;
     if (jfs_cipher_key_size(cipher) < 0) return JFS_ERR_INVALID;
@@ -2495,10 +2523,21 @@ int64_t jfs_open_decompress_batch(int algo, int cipher, int nblk, const jfs_iov 
     int64_t rc = JFS_OK;
     if (!todo.empty()) {
         Aead ae{cipher, false, orig.data(), key.data(), nonce.data(), nullptr, nullptr};
-        rc = deal(algo, DECOMPRESS, todo, iov2, out_n, device_mask, &ae);
+        rc = deal(algo, DECOMPRESS, todo, iov2, out_n, device_mask, &ae, nullptr, csum);
     }
     stat_call(algo, DECOMPRESS, rc, nblk, iov, out_n, t0);
     return rc;
+}
+
+int64_t jfs_open_decompress_batch(int algo, int cipher, int nblk, const jfs_iov *iov, const uint8_t *const *keys,
+                                  int64_t *out_n, uint32_t device_mask) {
+    return open_batch_call(algo, cipher, nblk, iov, keys, out_n, device_mask, nullptr);
+}
+
+int64_t jfs_open_decompress_batch_csum(int algo, int cipher, int nblk, const jfs_iov *iov, const uint8_t *const *keys,
+                                       int64_t *out_n, uint8_t *const *csum, uint32_t device_mask) {
+    if (nblk > 0 && !csum) return JFS_ERR_INVALID;
+    return open_batch_call(algo, cipher, nblk, iov, keys, out_n, device_mask, csum);
 }
 
 int64_t jfs_compress_batch(int algo, int nblk, const jfs_iov *iov, int64_t *out_n, uint32_t device_mask) {
@@ -2983,11 +3022,23 @@ int64_t jfs_read_gather_device(const jfs_dev_block *d_src, const int32_t *d_src_
     return hipEventRecord(z.ev_done, st) == hipSuccess ? JFS_OK : JFS_ERR_HIP;
 }
 
-// jfs_read_batch (cipher < 0) and jfs_read_open_batch
+int64_t jfs_read_csum_device(const jfs_compact_out *d_out, const int32_t *d_ret, int nout, const int32_t *d_piece_first,
+                             int64_t npiece, uint8_t *d_csum, void *stream) {
+    if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
+    if (nout < 0 || npiece < 0 || npiece > INT32_MAX || (nout > 0 && (!d_out || !d_ret || !d_piece_first)) ||
+        (npiece > 0 && (!d_csum || ((uintptr_t)d_csum & 3u) != 0)))
+        return JFS_ERR_INVALID;
+    if (nout == 0 || npiece == 0) return JFS_OK;
+    return launch_rc(
+        jfs_launch_read_csum_flat(d_out, nout, d_ret, d_piece_first, npiece, (uint32_t *)d_csum, (hipStream_t)stream));
+}
+
+// jfs_read_batch (cipher < 0) and jfs_read_open_batch; csum: the _csum calls'
+// array (nout entries), else null
 static int64_t read_call(int algo, int cipher, int nsrc, const jfs_iov *src, const uint8_t *const *src_keys,
                          const int64_t *src_crc, int nout, const jfs_iov *out, const int32_t *seg_first,
                          const jfs_compact_seg *seg, int64_t *src_n, int64_t *out_n, uint32_t *crc_got,
-                         uint32_t device_mask) {
+                         uint32_t device_mask, uint8_t *const *csum = nullptr) {
     const bool sealed = cipher >= 0;
     // the plan, the keys and the checksums are checked before any device is touched
     std::vector<int64_t> total;
@@ -3012,6 +3063,8 @@ static int64_t read_call(int algo, int cipher, int nsrc, const jfs_iov *src, con
         if (jfs_plan::chain_dead(seg_first, seg, j, src_map)) out_n[j] = JFS_ERR_CORRUPT;
         else if (total[j] == 0) out_n[j] = 0;
         else oo.push_back({j, total[j], total[j], 0, 0});
+        // an empty read's checksum is checksum() of no bytes: one zero word, no device needed
+        if (csum && csum[j] && out_n[j] == 0 && total[j] == 0) memset(csum[j], 0, 4);
     }
     // prefix mode (LZ4): the last byte the plan asks of every object
     std::vector<int64_t> need;
@@ -3019,7 +3072,7 @@ static int64_t read_call(int algo, int cipher, int nsrc, const jfs_iov *src, con
         need = jfs_plan::chain_need(nsrc, nout, seg_first, seg);
     chain_dispatch(ds, algo, DECOMPRESS, st, oo, src_n, out_n, [&](DevCtx *dev, Lane &ln) {
         return read_run(dev, ln, algo, cipher, src, src_keys, st, ns, src_map, out, oo, seg_first, seg, src_n, out_n,
-                        crc_got, need.empty() ? nullptr : need.data());
+                        crc_got, need.empty() ? nullptr : need.data(), csum);
     });
     chain_stat(algo, DECOMPRESS, nsrc, [&](int i) { return src[i].src_len; }, src_n, ns > 0, steady_ns() - t0);
     return JFS_OK;
@@ -3039,6 +3092,23 @@ int64_t jfs_read_open_batch(int algo, int cipher, int nsrc, const jfs_iov *src, 
     if (cipher < 0) return JFS_ERR_INVALID;
     return read_call(algo, cipher, nsrc, src, src_keys, src_crc, nout, out, seg_first, seg, src_n, out_n, crc_got,
                      device_mask);
+}
+
+int64_t jfs_read_batch_csum(int algo, int nsrc, const jfs_iov *src, const int64_t *src_crc, int nout, const jfs_iov *out,
+                            const int32_t *seg_first, const jfs_compact_seg *seg, int64_t *src_n, int64_t *out_n,
+                            uint32_t *crc_got, uint8_t *const *csum, uint32_t device_mask) {
+    if (nout > 0 && !csum) return JFS_ERR_INVALID;
+    return read_call(algo, -1, nsrc, src, nullptr, src_crc, nout, out, seg_first, seg, src_n, out_n, crc_got,
+                     device_mask, csum);
+}
+
+int64_t jfs_read_open_batch_csum(int algo, int cipher, int nsrc, const jfs_iov *src, const uint8_t *const *src_keys,
+                                 const int64_t *src_crc, int nout, const jfs_iov *out, const int32_t *seg_first,
+                                 const jfs_compact_seg *seg, int64_t *src_n, int64_t *out_n, uint32_t *crc_got,
+                                 uint8_t *const *csum, uint32_t device_mask) {
+    if (cipher < 0 || (nout > 0 && !csum)) return JFS_ERR_INVALID;
+    return read_call(algo, cipher, nsrc, src, src_keys, src_crc, nout, out, seg_first, seg, src_n, out_n, crc_got,
+                     device_mask, csum);
 }
 
 int jfs_device_count(void) { return (int)devices().size(); }

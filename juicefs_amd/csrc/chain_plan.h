@@ -126,6 +126,36 @@ inline std::vector<int32_t> chain_want(const int64_t *need, const std::vector<Ch
 }
 
 // ---------------------------------------------------------------------------
+// the reads' disk-cache checksums (disk_cache_file.go checksum()): the
+// big-endian CRC-32C of every 32 KiB piece of a read's gathered bytes
+// ---------------------------------------------------------------------------
+constexpr int64_t CSUM_PIECE = 32 << 10;  // csBlock
+
+// Go's ((n-1)/csBlock+1): one piece for n = 0
+inline int64_t csum_pieces(int64_t n) { return n > 0 ? (n - 1) / CSUM_PIECE + 1 : 1; }
+
+// piece_first[k] = the first piece of output k among all pieces of the call
+// (no + 1 entries, the last one their count); an output with want[k] == 0 has
+// none.  Piece p of the call has its 4 bytes at 4 p of the checksum area, so
+// output k's checksum starts at off[k] = 4 piece_first[k].  Returns the piece
+// count, or -1 when it does not fit an int32.
+inline int64_t chain_csum_pieces(const std::vector<ChainOut> &oo, const std::vector<uint8_t> &want,
+                                 std::vector<int32_t> &piece_first, std::vector<int64_t> &off) {
+    const size_t no = oo.size();
+    piece_first.assign(no + 1, 0);
+    off.assign(no, 0);
+    int64_t np = 0;
+    for (size_t k = 0; k < no; k++) {
+        piece_first[k] = (int32_t)np;
+        off[k] = 4 * np;
+        if (k < want.size() && want[k]) np += csum_pieces(oo[k].total);
+        if (np > INT32_MAX) return -1;
+    }
+    piece_first[no] = (int32_t)np;
+    return np;
+}
+
+// ---------------------------------------------------------------------------
 // staging of one call
 // ---------------------------------------------------------------------------
 // Where each object lies in its area: in[k] in the stored bytes (every staged
@@ -164,11 +194,13 @@ struct ChainFlags {
     bool out_crc;  // CRC-32C of every output
     bool src_crc;  // expected CRC-32C of stored objects
     bool prefix;   // per-source decode limits
+    bool read_csum = false;  // disk-cache checksums of the reads (last: the initialisers above leave it off)
 };
 
 // The staged area, mirrored pinned / HBM: [stored bytes | meta | results |
 // outputs], byte offsets from the slot's base.  ns decoded sources, n staged
-// objects (n - ns of them only for their checksum), no outputs, nseg segments.
+// objects (n - ns of them only for their checksum), no outputs, nseg segments,
+// npiece 32 KiB pieces of the reads that asked for their checksums.
 // An area the call does not use has no bytes and sits where the next one
 // starts.  The host writes [0, h2d), which goes to the device in one copy;
 // [results, out) comes back in one copy.  srcn, the source lengths, lies in
@@ -184,17 +216,20 @@ struct ChainLayout {
     int64_t oseed;      // checksum seeds of sealed outputs (the envelope header's CRC)
     int64_t scd, sseed, len, exp;  // stored objects' checksums: descriptors, seeds, lengths (-1: none), expected
     int64_t want;                  // prefix mode's decode limits
+    int64_t pf;                    // piece prefix of the reads' checksums, no + 1
     int64_t srcn;                  // source lengths, ns + 1, preset
     // results, which only the device writes:
     int64_t open;        // the opens'
     int64_t ret, r2;     // the outputs': gather / encoder, seal
     int64_t ocrc;        // output checksums
     int64_t scrc, got;   // stored objects' checksums: raw, checked
+    int64_t csum;        // the reads' checksums, 4 bytes per piece
     int64_t out;         // the output area
     int64_t h2d, results;
 
     ChainLayout() = default;
-    ChainLayout(int64_t tin, int64_t ns, int64_t n, int64_t no, int64_t nseg, const ChainFlags &f) {
+    ChainLayout(int64_t tin, int64_t ns, int64_t n, int64_t no, int64_t nseg, const ChainFlags &f,
+                int64_t npiece = 0) {
         int64_t o = align16(tin);
         auto take = [&o](bool used, int64_t count, int64_t size) {
             const int64_t at = o;
@@ -217,6 +252,7 @@ struct ChainLayout {
         len = take(f.src_crc, n, 4);
         exp = take(f.src_crc, n, 4);
         want = take(f.prefix, ns, 4);
+        pf = take(f.read_csum, no + 1, 4);
         results = srcn = take(true, ns + 1, 4);
         h2d = o;
         open = take(f.sealed, ns, 4);
@@ -225,6 +261,7 @@ struct ChainLayout {
         ocrc = take(f.out_crc, no, 4);
         scrc = take(f.src_crc, n, 4);
         got = take(f.src_crc, n, 4);
+        csum = take(f.read_csum, npiece, 4);
         out = o;
     }
 };

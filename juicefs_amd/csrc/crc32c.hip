@@ -221,6 +221,95 @@ __global__ __launch_bounds__(LANES) void crc32c_kernel(const jfs_dev_block *__re
     }
 }
 
+// The read path's disk-cache checksums (capi.hip, read_run): the big-endian
+// CRC-32C of every 32 KiB piece of the reads that asked for them, taken from
+// the packed output area behind gather_copy_flat_kernel.  crc32c_kernel walks a
+// block's pieces in turn on one workgroup, which suits thousands of equal
+// blocks; a read batch mixes 4 KiB reads with 4 MiB cache fills, whose 128
+// pieces would queue on one workgroup beside hundreds that hold one.  Here the
+// work item is the piece: piece_first is the host-staged running sum of every
+// read's piece count (nout + 1 entries; 0 pieces for a read without a
+// checksum), a workgroup finds its read by binary search, as the flat gather
+// finds its tile, and piece p's word goes to csum[p].
+// One workgroup of 256 lanes per piece, not one wave: a 32 KiB piece is eight
+// 4 KiB rows, so every lane has its eight 16-byte loads in flight at once and
+// the piece costs one cross-wave fold -- the segment body of crc32c_kernel.
+// The grid is capped at what the chip holds at once (87 VGPRs: 5 waves per
+// SIMD, so 5 such workgroups per CU) and strides over the pieces, so a large
+// batch copies the 13 KiB of tables to LDS once per workgroup, not once per
+// piece.
+// ret[j] is the gather's verdict: nothing is written for a read whose verdict
+// is not its planned total (out[j].dst_cap).  A piece shorter than 32 KiB (a
+// read's tail) is front-padded with zero bytes like a block's tail above.
+__global__ __launch_bounds__(LANES) void read_csum_flat_kernel(const jfs_compact_out *__restrict__ out, int nout,
+                                                                const int32_t *__restrict__ ret,
+                                                                const int32_t *__restrict__ piece_first,
+                                                                uint32_t *__restrict__ csum) {
+    __shared__ Smem s;
+    constexpr int64_t S = 32 << 10;
+    constexpr int ROWS = (int)(S / ROW);
+    const int t = threadIdx.x, l = t & 63, w = t >> 6;
+    {  // constant tables -> LDS
+        const uint32_t *g = (const uint32_t *)&g_tab;
+        uint32_t *d = (uint32_t *)&s.T;
+        for (int i = t; i < (int)(sizeof(Tables) / 4); i += LANES) d[i] = g[i];
+    }
+    __syncthreads();
+    const Tables &T = s.T;
+    const JFS_GLOBAL int32_t *pf = (const JFS_GLOBAL int32_t *)piece_first;
+    const int32_t npiece = pf[nout];
+    const uint32_t laneK = T.lane[t];
+    for (int32_t p = (int32_t)blockIdx.x; p < npiece; p += (int32_t)gridDim.x) {
+        int lo = 0, hi = nout - 1;  // the last read whose first piece is at or before p (reads without pieces share a start)
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (pf[mid] <= p) lo = mid;
+            else hi = mid - 1;
+        }
+        const int j = lo;
+        const jfs_compact_out o = ((const JFS_GLOBAL jfs_compact_out *)out)[j];
+        const int64_t n = (int64_t)((const JFS_GLOBAL int32_t *)ret)[j];  // the plan kernel's verdict
+        const int64_t s0 = (int64_t)(p - pf[j]) * S;
+        if (n <= 0 || n != (int64_t)o.dst_cap || s0 >= n) continue;  // (the same in every lane)
+        const gc_u8 *src = (const gc_u8 *)o.dst;
+        const bool aligned = (((uintptr_t)src) & 15u) == 0;
+        const int64_t e = s0 + S < n ? s0 + S : n;
+        const int64_t len = e - s0;
+        const int64_t v0 = e - S;  // virtual piece start: front-padded with zeros when len < S
+        const bool fast = aligned && len == S;
+        const bool words = aligned && (len & 15) == 0;  // a short piece whose chunks are aligned words all the same
+        uint4 c[ROWS];
+#pragma unroll
+        for (int k = 0; k < ROWS; k++) {
+            const int64_t q = v0 + (int64_t)k * ROW + 16 * t;
+            if (fast || (words && q >= s0)) c[k] = *(const gc_u4 *)(src + q);
+            else if (q + 16 <= s0) c[k] = make_uint4(0, 0, 0, 0);
+            else c[k] = load_masked(src, q, s0, e);
+        }
+        uint32_t A = 0;
+#pragma unroll
+        for (int k = 0; k < ROWS; k++) A = mul_row(T, A) ^ raw16(T, c[k]);
+        // the piece's raw CRC = XOR over lanes of A_t * x^(8*16*(255-t))
+        uint32_t v = mulp(A, laneK);
+        v ^= (uint32_t)__shfl_xor((int)v, 32, 64);
+        v ^= (uint32_t)__shfl_xor((int)v, 16, 64);
+        v ^= (uint32_t)__shfl_xor((int)v, 8, 64);
+        v ^= (uint32_t)__shfl_xor((int)v, 4, 64);
+        v ^= (uint32_t)__shfl_xor((int)v, 2, 64);
+        v ^= (uint32_t)__shfl_xor((int)v, 1, 64);
+        if (l == 0) s.part[w] = v;
+        __syncthreads();
+        if (t == 0) {
+            uint32_t seg = 0;
+            for (int i = 0; i < LANES / 64; i++) seg ^= s.part[i];
+            const uint32_t std_v = ~(seg ^ mulp(0xFFFFFFFFu, xpow8(T, (uint64_t)len)));
+            // big-endian bytes, one aligned 4-byte store
+            ((JFS_GLOBAL uint32_t *)csum)[p] = (std_v >> 24) | ((std_v >> 8) & 0xFF00u) | ((std_v << 8) & 0xFF0000u) | (std_v << 24);
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace crc
 }  // namespace jfs
 
@@ -254,5 +343,21 @@ extern "C" int jfs_launch_crc32c_segs_lens(const jfs_dev_block *d_blocks, int nb
     if (seg_bytes <= 0 || seg_bytes % ROW != 0 || seg_bytes > (64 << 20)) return -1;
     hipLaunchKernelGGL(crc32c_kernel, dim3(nblk), dim3(LANES), 0, stream, d_blocks, nblk, seg_bytes / ROW, 1,
                        (uint32_t *)nullptr, (int32_t *)nullptr, d_lens, (const uint32_t *)nullptr);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// The reads' disk-cache checksums on the flat piece grid (read_csum_flat_kernel).
+// d_out / d_ret: the gather's plan and verdicts; d_piece_first: the device copy
+// of the piece prefix (nout + 1 entries); npiece: its last entry, a host value
+// (it sizes the launch); d_csum: npiece 4-byte words.
+extern "C" int jfs_launch_read_csum_flat(const jfs_compact_out *d_out, int nout, const int32_t *d_ret,
+                                         const int32_t *d_piece_first, int64_t npiece, uint32_t *d_csum,
+                                         hipStream_t stream) {
+    using namespace jfs::crc;
+    if (nout <= 0 || npiece == 0) return 0;
+    if (npiece < 0 || npiece > INT32_MAX || (((uintptr_t)d_csum) & 3u) != 0) return -1;
+    const int64_t resident = 256 * 5;  // CUs x workgroups a CU holds (see the kernel)
+    hipLaunchKernelGGL(read_csum_flat_kernel, dim3((unsigned)(npiece < resident ? npiece : resident)), dim3(LANES), 0,
+                       stream, d_out, nout, d_ret, d_piece_first, d_csum);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -110,6 +110,13 @@ int jfs_launch_gather_flat(const jfs_dev_block *d_src, const int32_t *d_src_n, i
 // a mismatch with d_expect[i] writes JFS_CHECKSUM_FAILED over d_src_n[i] (i < ndec)
 int jfs_launch_verify_gate(const uint32_t *d_crc, const int32_t *d_lens, const uint32_t *d_expect, int n, int ndec,
                            int32_t *d_src_n, uint32_t *d_crc_got, hipStream_t stream);
+// read path: the disk-cache checksums of the gathered reads (crc32c.hip,
+// read_csum_flat_kernel) on a one-dimensional grid over d_piece_first, the
+// running sum of the reads' 32 KiB piece counts (nout + 1 entries; npiece = its
+// last entry on the host); piece p's big-endian CRC-32C goes to d_csum[p].
+// Nothing is written for a read whose verdict d_ret[j] is not d_out[j].dst_cap.
+int jfs_launch_read_csum_flat(const jfs_compact_out *d_out, int nout, const int32_t *d_ret,
+                              const int32_t *d_piece_first, int64_t npiece, uint32_t *d_csum, hipStream_t stream);
 int jfs_launch_gen(uint8_t *d_dst, int nblk, int64_t block_bytes, char cls, uint64_t seed_base,
                    const uint8_t *d_vocab, hipStream_t stream);
 }

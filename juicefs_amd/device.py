@@ -274,6 +274,19 @@ def read_gather(src_desc: torch.Tensor, src_n: torch.Tensor, out_desc: torch.Ten
                                            _stream_ptr(stream)), "jfs_read_gather_device")
 
 
+def read_csum(out_desc: torch.Tensor, ret: torch.Tensor, piece_first: torch.Tensor, npiece: int, csum: torch.Tensor,
+              stream=None):
+    """jfs_read_csum_device: the big-endian CRC-32C of every 32 KiB piece of the
+    gathered reads whose verdict in `ret` is their dst_cap; piece_first (int32,
+    one entry per read plus one) and its last entry npiece size the flat grid,
+    piece p goes to csum[4p:4p+4]."""
+    no = out_desc.numel() // COMPACT_OUT_DTYPE.itemsize
+    if piece_first.numel() != no + 1 or csum.numel() * csum.element_size() < 4 * npiece:
+        raise ValueError("piece_first needs one entry per read plus one, csum 4 bytes per piece")
+    _check(L.load().jfs_read_csum_device(out_desc.data_ptr(), ret.data_ptr(), no, piece_first.data_ptr(), int(npiece),
+                                         csum.data_ptr(), _stream_ptr(stream)), "jfs_read_csum_device")
+
+
 def lz4_compact(src_desc: torch.Tensor, src_ret: torch.Tensor, gather_desc: torch.Tensor, seg: torch.Tensor,
                 enc_desc: torch.Tensor, max_dst_cap: int, ret: torch.Tensor, stream=None):
     """Fused LZ4 decode -> gather -> LZ4 encode (jfs_lz4_compact_device)."""

@@ -19,7 +19,7 @@ from __future__ import annotations
 import ctypes
 
 from . import _lib as L
-from .compress import CompressError, _addr, _err, _read_call
+from .compress import CompressError, _addr, _err, _read_call, csum_bytes
 
 AES256GCM_RSA = "aes256gcm-rsa"
 CHACHA20_RSA = "chacha20-rsa"
@@ -105,8 +105,11 @@ def compress_seal_batch(codec: int, algo: str, pairs, params, device_mask: int =
             (0, _err_of(int(out[i]), iov[i].dst_cap, iov[i].src_len, "compress+seal")) for i in range(nb)]
 
 
-def open_decompress_batch(codec: int, algo: str, pairs, keys, device_mask: int = 0):
-    """pairs: [(dst, envelope)], keys: [data key] -> [(n, err)] (n as jfs_decompress returns it)"""
+def open_decompress_batch(codec: int, algo: str, pairs, keys, device_mask: int = 0, with_csum: bool = False):
+    """pairs: [(dst, envelope)], keys: [data key] -> [(n, err)] (n as jfs_decompress returns it).
+    with_csum (jfs_open_decompress_batch_csum): [(n, err, csum)] as
+    Compressor.DecompressBatchChecksum gives, the disk-cache checksum bytes
+    of every opened and decoded block (None for a block that fails)."""
     lib = L.load()
     nb = len(pairs)
     _check_keys(algo, keys, None)
@@ -121,7 +124,12 @@ def open_decompress_batch(codec: int, algo: str, pairs, keys, device_mask: int =
         iov[i].src, iov[i].src_len, iov[i].dst, iov[i].dst_cap = s, sn, d, dn
         kp[i] = kk.value if isinstance(kk, ctypes.c_void_p) else kk
     out = (ctypes.c_int64 * max(nb, 1))()
-    rc = lib.jfs_open_decompress_batch(codec, cipher_id(algo), nb, iov, kp, out, device_mask)
+    if with_csum:
+        cs_bufs = [ctypes.create_string_buffer(csum_bytes(max(iov[i].dst_cap, 0))) for i in range(nb)]
+        cs_ptrs = (ctypes.c_void_p * max(nb, 1))(*[ctypes.cast(b, ctypes.c_void_p) for b in cs_bufs])
+        rc = lib.jfs_open_decompress_batch_csum(codec, cipher_id(algo), nb, iov, kp, out, cs_ptrs, device_mask)
+    else:
+        rc = lib.jfs_open_decompress_batch(codec, cipher_id(algo), nb, iov, kp, out, device_mask)
     if rc != 0:
         raise _err_of(rc, 0, 0, "open batch")
     res = []
@@ -132,7 +140,14 @@ def open_decompress_batch(codec: int, algo: str, pairs, keys, device_mask: int =
             res.append((n, _err_of(r, iov[i].dst_cap, iov[i].src_len, "open+decompress")))
         else:
             res.append((r, None))
+    if with_csum:
+        return [(n, e, cs_bufs[i].raw[:csum_bytes(n)] if e is None else None) for i, (n, e) in enumerate(res)]
     return res
+
+
+def open_decompress_batch_csum(codec: int, algo: str, pairs, keys, device_mask: int = 0):
+    """The sealed DecompressBatchChecksum: open_decompress_batch(with_csum=True)."""
+    return open_decompress_batch(codec, algo, pairs, keys, device_mask, with_csum=True)
 
 
 def compact_seal_batch(codec: int, algo: str, sources, keys, outputs, params, plan, device_mask: int = 0,
@@ -204,14 +219,15 @@ def compact_seal_batch(codec: int, algo: str, sources, keys, outputs, params, pl
     return src_res, out_res
 
 
-def read_open_batch(codec: int, algo: str, sources, keys, reads, plan, crcs=None, device_mask: int = 0):
+def read_open_batch(codec: int, algo: str, sources, keys, reads, plan, crcs=None, device_mask: int = 0,
+                    with_csum=False):
     """Read assembly of an encrypted volume on one GPU (jfs_read_open_batch):
     Compressor.ReadBatch with open_decompress_batch in front.  sources:
     [(envelope, block_size)], keys: [data key] (one per source); reads, plan,
     crcs and the result as for ReadBatch -- the expected CRC-32C covers the
     whole envelope, and a source that does not authenticate is a failed
-    source."""
+    source.  with_csum (jfs_read_open_batch_csum): as for ReadBatch."""
     if len(keys) != len(sources):
         raise ValueError("one key per source")
     _check_keys(algo, keys, None)
-    return _read_call(codec, cipher_id(algo), sources, keys, reads, plan, crcs, device_mask)
+    return _read_call(codec, cipher_id(algo), sources, keys, reads, plan, crcs, device_mask, with_csum)
