@@ -238,6 +238,36 @@ int64_t jfs_lz4_decompress_prefix_device(const jfs_dev_block *d_blocks, const in
 int64_t jfs_lz4_decompress_prefix_device_small(const jfs_dev_block *d_blocks, const int32_t *src_len,
                                                const int32_t *dst_cap, const int32_t *d_want, int nblk,
                                                int32_t *d_ret, void *stream);
+/* Zstd prefix decode: input i is decoded only as far as the Zstd block that
+ * reaches its first d_want[i] output bytes; the blocks behind it are neither
+ * entropy-decoded nor replayed.  d_want is a device array of nblk int32.
+ * Result codes, stream behaviour and scratch are jfs_zstd_decompress_device's.
+ * Every stage walks the frame with a lower bound `lb` of the output so far
+ * (exact for raw and RLE blocks, literals + 3 * sequences for a compressed
+ * block) and stops in front of the next block header once lb >= want.  Let
+ * `size` be the full decoder's result, S the block boundary at which that rule
+ * stops (fixed by the input and want alone, the same on both paths) and B the
+ * block that holds output byte want - 1 in the full decode.
+ *   The walk ends before the rule fires (a frame whose last block has been
+ *     walked ends with its content-size and checksum checks): ret is the full
+ *     decoder's result, min(size, want) when size >= 0.
+ *   The walk stops and no fault lies in front of S: ret = want and
+ *     dst[0, want) is that prefix of the full decode.
+ *   A fault in a block in front of B: the full decoder's negative value (the
+ *     first error in stream order is the same one).
+ *   A fault in a block from B up to S: that value or want (the replay may
+ *     leave at want).
+ *   A fault at or behind S -- a wrong content size or checksum, trailing
+ *     garbage, output past dst_cap included -- is unseen: ret = want.
+ * want > dst_cap acts as dst_cap; want <= 0 stops in front of the first block
+ * and gives 0 unless the frame header itself is rejected.  Nothing outside
+ * dst[0, dst_cap) is written, and nothing at or above the output end of the
+ * last walked block; the small-batch path (jfs_zstd_split_counts counts these
+ * inputs too), for an input it decodes itself, writes nothing at or above ret.
+ * A highly compressible block has a tiny lb, so such frames are walked to
+ * their end and only the result is cut. */
+int64_t jfs_zstd_decompress_prefix_device(const jfs_dev_block *d_blocks, const int32_t *d_want, int nblk,
+                                          int32_t *d_ret, void *stream);
 /* Diagnostics for the small-batch path (used by it, by jfs_decompress and by
  * small jfs_decompress_batch calls), six counters: out[0] = blocks it decoded
  * itself, out[1] = blocks it handed to the one-workgroup kernel (inputs outside
@@ -597,18 +627,28 @@ int64_t jfs_read_open_batch_csum(int algo, int cipher, int nsrc, const jfs_iov *
  * precedence, out_n and the output bytes are those of full mode for every read
  * whose sources are well-formed, and a source too short for a segment still
  * fails that read (JFS_ERR_CORRUPT).  A call in which every source is needed to
- * its dst_cap takes the full decoders.  Zstd and "none" decode whole in either
- * mode, with full mode's src_n.  jfs_stats' bytes_out counts src_n.  The
- * compaction calls do not consult the mode.
- * The initial value is read once from JFS_READ_DECODE = "full" | "prefix"
- * (case-insensitive; anything else, or unset: full).
+ * its dst_cap takes the full decoders.  Zstd and "none" decode whole in these
+ * two modes, with full mode's src_n.
+ * JFS_READ_DECODE_PREFIX_ALL is JFS_READ_DECODE_PREFIX for LZ4 and also stops
+ * each Zstd decode at the Zstd block a read ends in: the same `need` is the
+ * `want` of jfs_zstd_decompress_prefix_device, whose contract gives src_n[i]
+ * (min(size, need) for a well-formed source); everything else is as above.
+ * "none" stays whole.  jfs_stats' bytes_out counts src_n.  The compaction calls
+ * do not consult the mode.
+ * The initial value is read once from JFS_READ_DECODE = "full" | "prefix" |
+ * "prefix-all" (case-insensitive; anything else, or unset: full).
  * jfs_set_read_decode_mode returns the previous mode, or -1 for an unknown
  * value (which changes nothing); it is atomic and applies to calls that start
  * afterwards. */
 #define JFS_READ_DECODE_FULL 0
 #define JFS_READ_DECODE_PREFIX 1
+#define JFS_READ_DECODE_PREFIX_ALL 2 /* JFS_READ_DECODE=prefix-all */
 int jfs_read_decode_mode(void);
 int jfs_set_read_decode_mode(int mode);
+/* jfs_set_read_decode_mode knows the two modes it was introduced with and keeps
+ * answering -1 for any other value, JFS_READ_DECODE_PREFIX_ALL included.
+ * jfs_set_read_decode_mode_ext is the same call for all three modes. */
+int jfs_set_read_decode_mode_ext(int mode);
 
 /* ---- Runtime / utilities ------------------------------------------------- */
 

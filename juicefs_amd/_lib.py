@@ -47,6 +47,7 @@ EXPORTS = [
     "jfs_read_decode_mode", "jfs_set_read_decode_mode",
     "jfs_read_batch_csum", "jfs_read_open_batch_csum", "jfs_open_decompress_batch_csum",
     "jfs_read_csum_device",
+    "jfs_zstd_decompress_prefix_device", "jfs_set_read_decode_mode_ext",
 ]
 # the hook include/jfs_gpucodec_lz4_fast_test.h declares (the fast LZ4 encoder's host twin)
 LZ4_FAST_TEST_EXPORTS = ["jfs_test_lz4_fast_host"]
@@ -56,7 +57,7 @@ ZSTD_FAST_TEST_EXPORTS = ["jfs_test_zstd_fast_host_seqs", "jfs_test_zstd_fast_se
 MODE_OFF, MODE_AUTO, MODE_FORCE = 0, 1, 2
 LZ4_PARSE_EXACT, LZ4_PARSE_FAST = 0, 1
 ZSTD_PARSE_EXACT, ZSTD_PARSE_FAST = 0, 1
-READ_DECODE_FULL, READ_DECODE_PREFIX = 0, 1
+READ_DECODE_FULL, READ_DECODE_PREFIX, READ_DECODE_PREFIX_ALL = 0, 1, 2
 CIPHER_AES256GCM, CIPHER_CHACHA20POLY1305, CIPHER_SM4GCM = 0, 1, 2
 STATS_N = 6  # index algo * 2 + dir (0 compress, 1 decompress)
 
@@ -131,10 +132,14 @@ def load() -> ctypes.CDLL:
     lib.jfs_lz4_decompress_prefix_device.restype = i64
     lib.jfs_lz4_decompress_prefix_device_small.argtypes = [vp, vp, vp, vp, ctypes.c_int, vp, vp]
     lib.jfs_lz4_decompress_prefix_device_small.restype = i64
+    lib.jfs_zstd_decompress_prefix_device.argtypes = [vp, vp, ctypes.c_int, vp, vp]
+    lib.jfs_zstd_decompress_prefix_device.restype = i64
     lib.jfs_read_decode_mode.argtypes = []
     lib.jfs_read_decode_mode.restype = ctypes.c_int
     lib.jfs_set_read_decode_mode.argtypes = [ctypes.c_int]
     lib.jfs_set_read_decode_mode.restype = ctypes.c_int
+    lib.jfs_set_read_decode_mode_ext.argtypes = [ctypes.c_int]
+    lib.jfs_set_read_decode_mode_ext.restype = ctypes.c_int
     lib.jfs_lz4_split_counts.argtypes = [vp, ctypes.c_int]
     lib.jfs_lz4_split_counts.restype = ctypes.c_int
     lib.jfs_zstd_split_counts.argtypes = [vp, ctypes.c_int]

@@ -286,12 +286,13 @@ def zstd_parse_mode(mode: str):
         lib.jfs_set_zstd_parse_mode(prev)
 
 
-_READ_DECODE = {"full": L.READ_DECODE_FULL, "prefix": L.READ_DECODE_PREFIX}
+_READ_DECODE = {"full": L.READ_DECODE_FULL, "prefix": L.READ_DECODE_PREFIX, "prefix-all": L.READ_DECODE_PREFIX_ALL}
 
 
 def read_decode_mode() -> str:
     """The decode mode of the read calls (jfs_read_decode_mode): "full", or
-    "prefix" -- every LZ4 decode stops at the last byte a read needs."""
+    "prefix" -- every LZ4 decode stops at the last byte a read needs, or
+    "prefix-all" -- so does every Zstd decode, at the Zstd block that holds it."""
     m = L.load().jfs_read_decode_mode()
     return next(k for k, v in _READ_DECODE.items() if v == m)
 
@@ -300,8 +301,8 @@ def set_read_decode_mode(mode: str) -> str:
     """Set it (process-wide, for calls that start afterwards) and return the
     previous mode's name."""
     if mode not in _READ_DECODE:
-        raise ValueError(f"read decode mode {mode!r}: expected 'full' or 'prefix'")
-    prev = L.load().jfs_set_read_decode_mode(_READ_DECODE[mode])
+        raise ValueError(f"read decode mode {mode!r}: expected 'full', 'prefix' or 'prefix-all'")
+    prev = L.load().jfs_set_read_decode_mode_ext(_READ_DECODE[mode])
     return next(k for k, v in _READ_DECODE.items() if v == prev)
 
 

@@ -302,14 +302,14 @@ std::atomic<int> &lz4_parse() {
 }
 inline bool lz4_fast_mode() { return lz4_parse().load(std::memory_order_relaxed) == JFS_LZ4_PARSE_FAST; }
 
-// JFS_READ_DECODE (include/jfs_gpucodec.h): full (default) | prefix
+// JFS_READ_DECODE (include/jfs_gpucodec.h): full (default) | prefix | prefix-all
 std::atomic<int> &read_decode() {
     static std::atomic<int> m{[] {
         const char *e = getenv("JFS_READ_DECODE");
         if (!e) return JFS_READ_DECODE_FULL;
         std::string v(e);
         for (auto &ch : v) ch = (char)tolower((unsigned char)ch);
-        return v == "prefix" ? JFS_READ_DECODE_PREFIX : JFS_READ_DECODE_FULL;
+        return v == "prefix" ? JFS_READ_DECODE_PREFIX : v == "prefix-all" ? JFS_READ_DECODE_PREFIX_ALL : JFS_READ_DECODE_FULL;
     }()};
     return m;
 }
@@ -1955,7 +1955,7 @@ bool chain_lz4_scratch(const Chain &c, const jfs_dev_block *h_enc, bool fast) {
 }
 
 // Queues open -> decode -> the opens' verdicts merged into the source lengths.
-// d_want (prefix mode, LZ4; else null): where each decode stops.
+// d_want (prefix modes: LZ4, and Zstd in JFS_READ_DECODE_PREFIX_ALL; else null): where each decode stops.
 int chain_decode(const Chain &c, const int32_t *d_want, int64_t max_want) {
     const jfs_dev_block *h_sdesc = c.host<jfs_dev_block>(c.L.sdesc), *d_sdesc = c.dev<jfs_dev_block>(c.L.sdesc);
     int32_t *d_srcn = c.dev<int32_t>(c.L.srcn), *d_open = c.dev<int32_t>(c.L.open);
@@ -1968,7 +1968,8 @@ int chain_decode(const Chain &c, const int32_t *d_want, int64_t max_want) {
         lk = r == JFS_OK ? 0 : -1;
     } else if (lk == 0 && c.algo == JFS_ALGO_ZSTD && ns > 0) {
         // (with a cipher the frame headers are ciphertext on the host) it plans its own scratch
-        lk = jfs_launch_zstd_decode(d_sdesc, ns, d_srcn, nullptr, c.ks);
+        lk = d_want ? jfs_launch_zstd_decode_prefix(d_sdesc, ns, d_srcn, d_want, c.ks)
+                    : jfs_launch_zstd_decode(d_sdesc, ns, d_srcn, nullptr, c.ks);
     }
     // a failed open left zeros, which may decode (for "none" they are the block): its verdict replaces the length
     if (lk == 0 && c.sealed) lk = jfs_launch_chain_merge(d_open, ns, d_srcn, c.ks);
@@ -2105,7 +2106,7 @@ int64_t compact_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *
 // objects the host already answered, staged whole only for their checksum.
 // Returns JFS_OK with src_n / out_n / crc_got of these objects filled, or
 // JFS_ERR_NO_MEMORY / JFS_ERR_HIP.
-// need (JFS_READ_DECODE_PREFIX with LZ4, else null): per object of the call,
+// need (the prefix modes with a codec they cover, else null): per object of the call,
 // the last byte a segment asks of it; the decode of source k stops there
 // (clamped to its capacity, staged behind the expected checksums in the same
 // H2D copy) unless every source is needed whole, which takes the full
@@ -2132,7 +2133,7 @@ int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src
         if (ntiles > INT32_MAX) return JFS_ERR_NO_MEMORY;
     }
     tile_first[no] = (int32_t)ntiles;
-    if (need && algo == JFS_ALGO_LZ4) want = jfs_plan::chain_want(need, st, ns, &max_want);
+    if (need && (algo == JFS_ALGO_LZ4 || algo == JFS_ALGO_ZSTD)) want = jfs_plan::chain_want(need, st, ns, &max_want);
     const bool prefix = !want.empty();
     std::vector<uint8_t> cs_want(no, 0);
     std::vector<int32_t> piece_first;
@@ -2787,11 +2788,25 @@ int jfs_set_read_decode_mode(int mode) {
     return read_decode().exchange(mode);
 }
 
+int jfs_set_read_decode_mode_ext(int mode) {
+    if (mode != JFS_READ_DECODE_FULL && mode != JFS_READ_DECODE_PREFIX && mode != JFS_READ_DECODE_PREFIX_ALL) return -1;
+    return read_decode().exchange(mode);
+}
+
 int jfs_zstd_parse_mode(void) { return zstd_parse_now(); }
 
 int jfs_set_zstd_parse_mode(int mode) {
     if (mode != JFS_ZSTD_PARSE_EXACT && mode != JFS_ZSTD_PARSE_FAST) return -1;
     return zstd_parse().exchange(mode);
+}
+
+int64_t jfs_zstd_decompress_prefix_device(const jfs_dev_block *d_blocks, const int32_t *d_want, int nblk,
+                                          int32_t *d_ret, void *stream) {
+    if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
+    if (nblk > 0 && !d_want) return JFS_ERR_INVALID;
+    stat_launch(JFS_ALGO_ZSTD, DECOMPRESS, nblk);
+    return jfs_launch_zstd_decode_prefix(d_blocks, nblk, d_ret, d_want, (hipStream_t)stream) == 0 ? JFS_OK
+                                                                                                  : JFS_ERR_HIP;
 }
 
 int64_t jfs_zstd_decompress_device(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, void *stream) {
@@ -3066,9 +3081,10 @@ static int64_t read_call(int algo, int cipher, int nsrc, const jfs_iov *src, con
         // an empty read's checksum is checksum() of no bytes: one zero word, no device needed
         if (csum && csum[j] && out_n[j] == 0 && total[j] == 0) memset(csum[j], 0, 4);
     }
-    // prefix mode (LZ4): the last byte the plan asks of every object
+    // prefix modes (LZ4 in both, Zstd in prefix-all): the last byte the plan asks of every object
     std::vector<int64_t> need;
-    if (algo == JFS_ALGO_LZ4 && read_decode().load(std::memory_order_relaxed) == JFS_READ_DECODE_PREFIX)
+    const int dmode = read_decode().load(std::memory_order_relaxed);
+    if ((algo == JFS_ALGO_LZ4 && dmode != JFS_READ_DECODE_FULL) || (algo == JFS_ALGO_ZSTD && dmode == JFS_READ_DECODE_PREFIX_ALL))
         need = jfs_plan::chain_need(nsrc, nout, seg_first, seg);
     chain_dispatch(ds, algo, DECOMPRESS, st, oo, src_n, out_n, [&](DevCtx *dev, Lane &ln) {
         return read_run(dev, ln, algo, cipher, src, src_keys, st, ns, src_map, out, oo, seg_first, seg, src_n, out_n,

@@ -38,9 +38,30 @@
 
 #include "jfs_internal.h"
 #include "wave.cuh"
+#include "zstd_walk.h"
+
+// zstd_decode_prefix.hip compiles this file again with
+// JFS_ZSTD_DECODE_PREFIX_TU set: the same kernels in a namespace of their own
+// with ZPFX = true, where every walk takes the input's `want` from its ZInfo
+// and stops at the block that reaches it.  Here ZPFX = false compiles the rule
+// out, and this unit holds the kernels it always held.
+#ifdef JFS_ZSTD_DECODE_PREFIX_TU
+#define JFS_ZNS zstdp
+#else
+#define JFS_ZNS zstdd
+#endif
 
 namespace jfs {
-namespace zstdd {
+namespace JFS_ZNS {
+using namespace zstdd;  // zstd_walk.h: Walk, ZInfo, the header readers
+
+#ifdef JFS_ZSTD_DECODE_PREFIX_TU
+constexpr bool ZPFX = true;
+#else
+constexpr bool ZPFX = false;
+#endif
+// where the walks of this input stop (full decode: nowhere)
+__host__ __device__ __forceinline__ int32_t zwant(const ZInfo &zi) { return ZPFX ? zinfo_want(zi) : INT32_MAX; }
 
 #ifdef JFS_PROF
 // diagnostic build only: cycle sums / counts of the sequence wave
@@ -58,7 +79,6 @@ __device__ unsigned long long g_zsprof[8];
 #define ZP_ADD(i, v) do { } while (0)
 #endif
 
-enum { E_CORRUPT = -1, E_DSTSMALL = -2, E_SRCSIZE = -3, E_SCRATCH = -4, E_BUG = -100 };
 enum { IT_SEQ = 0, IT_FSTART = 1, IT_FEND = 2, IT_BSTART = 3, IT_BEND = 4, IT_ERR = 5, IT_BREP = 6 };
 // Offsets of sequence items may be symbolic: bit 31 set, bits 29-30 = j,
 // bits 0-28 = d  ->  offset = max(1, rep_j - d) with rep_j the repeat-offset
@@ -68,25 +88,7 @@ constexpr uint32_t SYMB = 0x80000000u;
 // Item offset of a sequence with offset code 31: its real offset is >= 2^31 - 3, past any output (cap is int32),
 // and would carry SYMB.  Not symbolic, and beyond the output for every replay's offset check.
 constexpr uint32_t OFF_BEYOND = 0x7FFFFFFFu;
-enum { FE_FCS = 1, FE_CHECK = 2, FE_MISSING = 4 };
-constexpr uint32_t ZSTD_MAGIC = 0xFD2FB528u;
-constexpr int32_t BLOCK_MAX = 128 << 10;
 
-// per-input bookkeeping
-struct ZInfo {
-    uint64_t item_off;      // first item (host scan)
-    uint64_t lit_off;       // first literal byte (host scan)
-    uint64_t tab_off;       // first FSE table cell (host scan)
-    uint32_t n_items;       // zscan: capacity; zseq: items written
-    uint32_t lit_bytes;     // zscan: capacity
-    uint32_t n_cblk;        // zscan: compressed blocks (TAB_CELLS table cells each)
-    uint32_t lit_err_blk;   // zlit: ordinal of the block whose literals failed
-    int32_t lit_err_code;
-    uint32_t ovf;           // zplan: the scratch cannot hold this input (ret = E_SCRATCH)
-    uint32_t n_sblk;        // zseqa: compressed blocks described (ZDesc after each table area)
-    uint32_t n_blk;         // zscan: blocks of every type (small-batch path: one record each)
-    int32_t cap;            // zscan: the input's dst_cap
-};
 constexpr int TAB_CELLS = 1280;  // u16 FSE cells per compressed block: LL 512, OF 256, ML 512
 constexpr int TAB_STRIDE = TAB_CELLS + 32;  // table area stride: the cells, then the block's ZDesc (64 B)
 
@@ -117,185 +119,6 @@ __constant__ int16_t ML_DEF[53] = {1, 4, 3, 2, 2, 2, 2, 2, 2, 1, 1, 1, 1, 1, 1, 
                                    1, 1, 1, 1, 1, 1, 1, 1, 1, 1, -1, -1, -1, -1, -1, -1, -1};
 __constant__ int16_t OF_DEF[29] = {1, 1, 1, 1, 1, 1, 2, 2, 2, 1, 1, 1, 1, 1, 1,
                                    1, 1, 1, 1, 1, 1, 1, 1, 1, -1, -1, -1, -1, -1};
-
-__host__ __device__ __forceinline__ uint32_t rd8(const gc_u8 *s, int32_t p) { return s[p]; }
-__host__ __device__ __forceinline__ uint32_t rd16(const gc_u8 *s, int32_t p) { return s[p] | (s[p + 1] << 8); }
-__host__ __device__ __forceinline__ uint32_t rd24(const gc_u8 *s, int32_t p) { return rd16(s, p) | (s[p + 2] << 16); }
-__host__ __device__ __forceinline__ uint32_t rd32(const gc_u8 *s, int32_t p) { return rd16(s, p) | (rd16(s, p + 2) << 16); }
-
-// ---------------------------------------------------------------------------
-// frame / block walk (ZSTD_decompressMultiFrame + ZSTD_decompressFrame order)
-// ---------------------------------------------------------------------------
-enum { EV_DONE = 0, EV_ERROR, EV_FSTART, EV_FEND, EV_BLOCK };
-
-struct Walk {
-    const gc_u8 *s;
-    int32_t n, p;
-    int32_t cap;       // dst capacity (stop rule)
-    int64_t lb;        // lower bound of the output produced so far
-    int32_t phase;     // 0 between frames, 1 in a frame, 2 finished
-    int32_t frames_done, after_last;
-    int32_t check, has_fcs;
-    uint64_t fcs;
-    uint32_t ordinal;  // blocks seen
-    // current block
-    int32_t btype, bsize, bpos;
-};
-
-__host__ __device__ __forceinline__ void walk_init(Walk &w, const gc_u8 *s, int32_t n, int32_t cap) {
-    w.s = s; w.n = n; w.p = 0; w.cap = cap; w.lb = 0; w.phase = 0; w.frames_done = 0; w.after_last = 0;
-    w.check = 0; w.has_fcs = 0; w.fcs = 0; w.ordinal = 0; w.btype = 0; w.bsize = 0; w.bpos = 0;
-}
-
-// Next event.  *err for EV_ERROR; for EV_FEND *flags/*chk describe the frame end.
-__host__ __device__ __forceinline__ int walk_next(Walk &w, int32_t *err, uint32_t *flags, uint32_t *chk) {
-    const gc_u8 *s = w.s;
-    if (w.phase == 2) return EV_DONE;
-    if (w.phase == 1 && w.after_last) {
-        w.after_last = 0;
-        uint32_t f = (w.has_fcs ? FE_FCS : 0) | (w.check ? FE_CHECK : 0);
-        *chk = 0;
-        if (w.check) {
-            if (w.n - w.p < 4) { f |= FE_MISSING; w.phase = 2; }
-            else { *chk = rd32(s, w.p); w.p += 4; w.phase = 0; }
-        } else {
-            w.phase = 0;
-        }
-        w.frames_done = 1;
-        *flags = f;
-        return EV_FEND;
-    }
-    if (w.phase == 1) {
-        if (w.lb > (int64_t)w.cap) { w.phase = 2; return EV_DONE; }  // zexec fails inside the last block
-        if (w.n - w.p < 3) { *err = E_SRCSIZE; w.phase = 2; return EV_ERROR; }
-        uint32_t bh = rd24(s, w.p);
-        w.p += 3;
-        int32_t btype = (bh >> 1) & 3, bsize = (int32_t)(bh >> 3);
-        if (btype == 3) { *err = E_CORRUPT; w.phase = 2; return EV_ERROR; }
-        int32_t csize = btype == 1 ? 1 : bsize;
-        if (csize > w.n - w.p) { *err = E_SRCSIZE; w.phase = 2; return EV_ERROR; }
-        if (btype == 2 && bsize >= BLOCK_MAX) { *err = E_SRCSIZE; w.phase = 2; return EV_ERROR; }
-        w.btype = btype; w.bsize = bsize; w.bpos = w.p;
-        w.p += csize;
-        w.after_last = bh & 1;
-        w.ordinal++;
-        return EV_BLOCK;
-    }
-    // between frames
-    for (;;) {
-        int32_t rem = w.n - w.p;
-        if (rem < 5) {
-            w.phase = 2;
-            if (rem > 0) { *err = E_SRCSIZE; return EV_ERROR; }
-            return EV_DONE;
-        }
-        uint32_t magic = rd32(s, w.p);
-        if ((magic & 0xFFFFFFF0u) == 0x184D2A50u) {
-            if (rem < 8) { *err = E_SRCSIZE; w.phase = 2; return EV_ERROR; }
-            uint32_t sz = rd32(s, w.p + 4);
-            if ((uint32_t)(rem - 8) < sz) { *err = E_SRCSIZE; w.phase = 2; return EV_ERROR; }
-            w.p += 8 + (int32_t)sz;
-            continue;
-        }
-        if (rem < 9) { *err = E_SRCSIZE; w.phase = 2; return EV_ERROR; }
-        uint32_t fhd = rd8(s, w.p + 4);
-        int32_t fcs_flag = fhd >> 6, single = (fhd >> 5) & 1, did = fhd & 3;
-        int32_t did_size = did == 0 ? 0 : did == 1 ? 1 : did == 2 ? 2 : 4;
-        int32_t fcs_size = fcs_flag == 0 ? (single ? 1 : 0) : fcs_flag == 1 ? 2 : fcs_flag == 2 ? 4 : 8;
-        int32_t fhs = 5 + (single ? 0 : 1) + did_size + fcs_size;
-        if (rem < fhs + 3) { *err = E_SRCSIZE; w.phase = 2; return EV_ERROR; }
-        if (magic != ZSTD_MAGIC) { *err = w.frames_done ? E_SRCSIZE : E_CORRUPT; w.phase = 2; return EV_ERROR; }
-        if (fhd & 8) { *err = E_CORRUPT; w.phase = 2; return EV_ERROR; }
-        int32_t q = w.p + 5;
-        if (!single) {
-            if ((rd8(s, q) >> 3) + 10 > 31) { *err = E_CORRUPT; w.phase = 2; return EV_ERROR; }
-            q++;
-        }
-        if (did) {
-            uint32_t id = 0;
-            for (int i = 0; i < did_size; i++) id |= rd8(s, q + i) << (8 * i);
-            q += did_size;
-            if (id != 0) { *err = E_CORRUPT; w.phase = 2; return EV_ERROR; }
-        }
-        w.has_fcs = fcs_size != 0;
-        uint64_t v = 0;
-        for (int i = 0; i < fcs_size; i++) v |= (uint64_t)rd8(s, q + i) << (8 * i);
-        if (fcs_size == 2) v += 256;
-        w.fcs = v;
-        q += fcs_size;
-        w.check = (fhd >> 2) & 1;
-        w.p = q;
-        w.phase = 1;
-        w.after_last = 0;
-        return EV_FSTART;
-    }
-}
-
-// Literal section header (ZSTD_decodeLiteralsBlock size logic).  Returns 0 or
-// an error; *sec = total bytes of the literal section.
-struct LitHdr {
-    int32_t type, regen, csize, hsz, streams, sec;
-};
-__host__ __device__ __forceinline__ int32_t lit_header(const gc_u8 *s, int32_t bpos, int32_t bsize, LitHdr &h) {
-    if (bsize < 3) return E_CORRUPT;  // MIN_CBLOCK_SIZE
-    uint32_t b0 = rd8(s, bpos);
-    h.type = b0 & 3;
-    int32_t sf = (b0 >> 2) & 3;
-    h.streams = 1;
-    h.csize = 0;
-    if (h.type <= 1) {
-        if (sf == 0 || sf == 2) { h.regen = b0 >> 3; h.hsz = 1; }
-        else if (sf == 1) { h.regen = rd16(s, bpos) >> 4; h.hsz = 2; }
-        else { h.regen = rd24(s, bpos) >> 4; h.hsz = 3; }
-        if (h.type == 0) {
-            if (h.hsz + h.regen > bsize) return E_CORRUPT;
-            h.sec = h.hsz + h.regen;
-        } else {
-            if (h.hsz + 1 > bsize) return E_CORRUPT;
-            if (h.regen > BLOCK_MAX) return E_CORRUPT;
-            h.sec = h.hsz + 1;
-        }
-        return 0;
-    }
-    if (bsize < 5) return E_CORRUPT;
-    uint32_t lhc = rd32(s, bpos);
-    if (sf <= 1) {
-        h.hsz = 3; h.streams = sf == 0 ? 1 : 4;
-        h.regen = (lhc >> 4) & 0x3FF; h.csize = (lhc >> 14) & 0x3FF;
-    } else if (sf == 2) {
-        h.hsz = 4; h.streams = 4;
-        h.regen = (lhc >> 4) & 0x3FFF; h.csize = lhc >> 18;
-    } else {
-        h.hsz = 5; h.streams = 4;
-        h.regen = (lhc >> 4) & 0x3FFFF; h.csize = (lhc >> 22) + (rd8(s, bpos + 4) << 10);
-    }
-    if (h.regen > BLOCK_MAX) return E_CORRUPT;
-    if (h.csize + h.hsz > bsize) return E_CORRUPT;
-    h.sec = h.hsz + h.csize;
-    return 0;
-}
-
-// nbSeq field (ZSTD_decodeSeqHeaders prefix).  Returns 0 or error; *nseq, *used.
-__host__ __device__ __forceinline__ int32_t nbseq_header(const gc_u8 *s, int32_t ip, int32_t end, int32_t *nseq, int32_t *used) {
-    if (ip >= end) return E_SRCSIZE;
-    int32_t v = (int32_t)rd8(s, ip);
-    int32_t u = 1;
-    if (v >= 128) {
-        if (v == 255) {
-            if (ip + 3 > end) return E_SRCSIZE;
-            v = (int32_t)rd16(s, ip + 1) + 0x7F00;
-            u = 3;
-        } else {
-            if (ip + 2 > end) return E_SRCSIZE;
-            v = ((v - 128) << 8) + (int32_t)rd8(s, ip + 1);
-            u = 2;
-        }
-    }
-    *nseq = v;
-    *used = u;
-    if (v == 0 && ip + u != end) return E_SRCSIZE;
-    return 0;
-}
 
 // ---------------------------------------------------------------------------
 // backward bit reader with a 2-block (32 B) prefetch queue (per lane)
@@ -494,52 +317,23 @@ __device__ __forceinline__ int32_t build_fse(uint32_t *t, const int16_t *norm, i
 // ---------------------------------------------------------------------------
 // kernel 1: header scan -> scratch sizes
 // ---------------------------------------------------------------------------
-// Scratch one input needs (exact): items, literal bytes, compressed blocks.
-// Host and device: run_batch plans from the host copy of its inputs.
-__host__ __device__ inline void zscan_one(const gc_u8 *src, int32_t n, int32_t cap, ZInfo &out) {
-    Walk w;
-    walk_init(w, src, n, cap);
-    uint64_t items = 0, lits = 0;
-    uint32_t cblk = 0;
-    for (;;) {
-        int32_t err = 0;
-        uint32_t fl = 0, chk = 0;
-        int ev = walk_next(w, &err, &fl, &chk);
-        if (ev == EV_DONE) break;
-        items++;  // FSTART / FEND / ERROR / BSTART
-        if (ev == EV_ERROR) break;
-        if (ev == EV_FEND && (fl & FE_MISSING)) break;
-        if (ev != EV_BLOCK) continue;
-        items++;  // BEND or ERR
-        if (w.btype != 2) {
-            items++;  // one literal-only item
-            int64_t room = (int64_t)w.cap - w.lb;
-            if ((int64_t)w.bsize <= room) lits += w.bsize;  // bytes past cap are never read
-            w.lb += w.bsize;
-            continue;
-        }
-        LitHdr h;
-        if (lit_header(w.s, w.bpos, w.bsize, h)) break;
-        lits += (uint64_t)h.regen + (h.type >= 2 ? 4 : 0);  // 4-stream segments may overhang by <= 3
-        int32_t nseq = 0, used = 0;
-        if (nbseq_header(w.s, w.bpos + h.sec, w.bpos + w.bsize, &nseq, &used)) break;
-        items += (uint64_t)nseq + 1;  // sequences + BREP
-        cblk++;
-        w.lb += (int64_t)h.regen + 3 * (int64_t)nseq;
-    }
-    out.n_items = (uint32_t)(items + 1);
-    out.lit_bytes = (uint32_t)(lits + 16);
-    out.n_cblk = cblk;
-    out.n_blk = w.ordinal;
-    out.cap = cap;
+// (zstd_walk.h: zscan_one)
+#ifdef JFS_ZSTD_DECODE_PREFIX_TU
+__global__ void zscan_kernel(const jfs_dev_block *__restrict__ blocks, int nblk, ZInfo *__restrict__ info,
+                             const int32_t *__restrict__ want) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nblk) return;
+    jfs_dev_block b = blocks[i];
+    zscan_one<true>((const gc_u8 *)b.src, b.src_len, b.dst_cap, want_clamp(want[i], b.dst_cap), info[i]);
 }
-
+#else
 __global__ void zscan_kernel(const jfs_dev_block *__restrict__ blocks, int nblk, ZInfo *__restrict__ info) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nblk) return;
     jfs_dev_block b = blocks[i];
-    zscan_one((const gc_u8 *)b.src, b.src_len, b.dst_cap, info[i]);
+    zscan_one<false>((const gc_u8 *)b.src, b.src_len, b.dst_cap, INT32_MAX, info[i]);
 }
+#endif
 
 // Offsets of every input's scratch (exclusive prefix sums over the inputs,
 // one workgroup), the capacity check, and the totals the launch needed
@@ -567,7 +361,8 @@ __global__ __launch_bounds__(PLAN_T) void zplan_kernel(ZInfo *__restrict__ info,
         const uint64_t c = info[i].cap > 0 ? (uint64_t)info[i].cap : 0u;
         nbk += info[i].n_blk;
         norg += (c + 3) & ~3ull;
-        mcap = c > mcap ? c : mcap;
+        const uint64_t m = ZPFX ? (uint64_t)zinfo_want(info[i]) : c;  // prefix: the replay covers [0, want)
+        mcap = m > mcap ? m : mcap;
     }
     __syncthreads();
     if (nbk) atomicAdd(&xb, (unsigned long long)nbk);
@@ -1000,7 +795,7 @@ __device__ __forceinline__ void lit_wave(LitSmem &sm, const jfs_dev_block &b, ZI
     const int l = lane_id();
     const gc_u8 *s = (const gc_u8 *)b.src;
     Walk w;
-    walk_init(w, s, b.src_len, b.dst_cap);
+    walk_init(w, s, b.src_len, b.dst_cap, zwant(zi));
     int64_t lpos = (int64_t)zi.lit_off;
     const int64_t lend = (int64_t)zi.lit_off + zi.lit_bytes;
     uint32_t err_blk = 0xFFFFFFFFu;
@@ -1024,7 +819,7 @@ __device__ __forceinline__ void lit_wave(LitSmem &sm, const jfs_dev_block &b, ZI
     for (;;) {
         int32_t err = 0;
         uint32_t fl = 0, chk = 0;
-        int ev = walk_next(w, &err, &fl, &chk);
+        int ev = walk_next<ZPFX>(w, &err, &fl, &chk);
         if (ev == EV_DONE || ev == EV_ERROR) break;
         if (ev == EV_FSTART) {
             if (!flush()) break;
@@ -1778,7 +1573,7 @@ __global__ __launch_bounds__(64) void zseqa_kernel(const jfs_dev_block *__restri
         g_u16 *tabs = (g_u16 *)tabs_all + zi.tab_off;
         g_u4 *items = (g_u4 *)items_all + zi.item_off;
         Walk w;
-        walk_init(w, s, b.src_len, b.dst_cap);
+        walk_init(w, s, b.src_len, b.dst_cap, zwant(zi));
         const uint32_t cap_items = zi.n_items, cap_cblk = zi.n_cblk;
         uint32_t cur = 0, cblk = 0, nd = 0;  // next item slot, next table area, descriptors
         int first = 0, bug = 0;
@@ -1792,7 +1587,7 @@ __global__ __launch_bounds__(64) void zseqa_kernel(const jfs_dev_block *__restri
         for (;;) {
             int32_t err = 0;
             uint32_t fl = 0, chk = 0;
-            int ev = walk_next(w, &err, &fl, &chk);
+            int ev = walk_next<ZPFX>(w, &err, &fl, &chk);
             if (ev == EV_DONE) break;
             if (ev == EV_ERROR) { put(0, 0, (uint32_t)err, IT_ERR); break; }
             if (ev == EV_FSTART) {
@@ -2408,6 +2203,10 @@ __global__ __launch_bounds__(64) void zexec_kernel(const jfs_dev_block *__restri
     int32_t regen = 0, lused = 0;
     uint32_t rin0 = 1, rin1 = 4, rin2 = 8;  // repeat offsets at the start of the current block
     bool done = false;
+    // prefix decode: `want` bytes are enough.  Only an input whose walk stopped
+    // may leave there: one walked to its end owes its frame-end checks.
+    [[maybe_unused]] const int32_t want = zwant(zi);
+    [[maybe_unused]] const bool leave = ZPFX && zinfo_stopped(zi);
     // items one chunk ahead: the next 64 are loaded while this chunk runs
     uint4 ahead = make_uint4(0, 0, 0, 0);
     if ((uint32_t)l < nit) ahead = it[l];
@@ -2452,6 +2251,9 @@ __global__ __launch_bounds__(64) void zexec_kernel(const jfs_dev_block *__restri
                 if (nexec) x_run(s, x, nexec, ll, ml, off, &lp, xincl, xlincl);
                 lused += (int32_t)totll;
                 if (bad) { result = code; done = true; break; }
+                if constexpr (ZPFX) {
+                    if (leave && x.op >= want) { result = want; done = true; break; }
+                }
                 k += r - 1;
             } else if (kind == IT_BSTART) {
                 if (zi.lit_err_blk == ix) { result = zi.lit_err_code; done = true; break; }
@@ -2463,6 +2265,9 @@ __global__ __launch_bounds__(64) void zexec_kernel(const jfs_dev_block *__restri
                 x_lit(s, x, lp, rest);
                 lp += rest;
                 lused = regen;
+                if constexpr (ZPFX) {
+                    if (leave && x.op >= want) { result = want; done = true; break; }
+                }
             } else if (kind == IT_BREP) {
                 rin0 = ix; rin1 = iy; rin2 = iz;
             } else if (kind == IT_FSTART) {
@@ -2491,7 +2296,7 @@ __global__ __launch_bounds__(64) void zexec_kernel(const jfs_dev_block *__restri
             }
         }
     }
-    if (!done) result = x.op;
+    if (!done) result = ZPFX && x.op > want ? want : x.op;
     if (x.bug) result = -x.bug;
     XP_ADD(7, ZP_NOW() - tz0);
 #ifdef JFS_PROF
@@ -2504,7 +2309,7 @@ __global__ __launch_bounds__(64) void zexec_kernel(const jfs_dev_block *__restri
 
 #include "zstd_split.inc"
 
-}  // namespace zstdd
+}  // namespace JFS_ZNS
 }  // namespace jfs
 
 // ---------------------------------------------------------------------------
@@ -2549,7 +2354,7 @@ constexpr int g_strict_reserved = 1;
 
 int launch_entropy_exec(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, jfs::zstdd::ZInfo *d_info,
                         uint8_t *d_lit, uint16_t *d_tabs, uint4 *d_items, hipStream_t stream) {
-    using namespace jfs::zstdd;
+    using namespace jfs::JFS_ZNS;
     hipLaunchKernelGGL(zlit_kernel, dim3(nblk), dim3(64), 0, stream, d_blocks, nblk, d_info, d_lit);
     if (hipGetLastError() != hipSuccess) return -1;
     hipLaunchKernelGGL(zseqa_kernel, dim3(nblk), dim3(64), 0, stream, d_blocks, nblk, d_info, d_tabs, d_items,
@@ -2597,14 +2402,14 @@ bool split_ok(int nblk, const uint64_t *tot) {
 // tot: the plan totals (zplan need[] / jfs_zstd_plan_host): [3] blocks,
 // [4] origin entries, [5] largest dst_cap
 int64_t split_bytes(int nblk, const uint64_t *tot) {
-    using namespace jfs::zstdd;
+    using namespace jfs::JFS_ZNS;
     return a256((int64_t)nblk * (int64_t)sizeof(SIn)) + a256((int64_t)tot[3] * (int64_t)sizeof(SBlk)) +
            a256((int64_t)nblk * 4) + a256((int64_t)tot[4] * 4) + 256;
 }
 
 int launch_split(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, jfs::zstdd::ZInfo *d_info, uint8_t *d_lit,
                  uint4 *d_items, void *d_split, const uint64_t *tot, hipStream_t st) {
-    using namespace jfs::zstdd;
+    using namespace jfs::JFS_ZNS;
     uint8_t *p = (uint8_t *)(((uintptr_t)d_split + 255) & ~(uintptr_t)255);
     SScr sc;
     sc.in = (SIn *)p;
@@ -2644,23 +2449,37 @@ int launch_split(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, jfs::z
 }
 }  // namespace
 
+namespace {
+// this unit's small-batch counters, added to out[0..1]
+int split_counts_add(uint64_t *out, int reset) {
+    unsigned long long v[2] = {0, 0};
+    if (hipMemcpyFromSymbol(v, HIP_SYMBOL(jfs::JFS_ZNS::g_zsplit_counts), sizeof(v)) != hipSuccess) return -1;
+    out[0] += v[0];
+    out[1] += v[1];
+    if (reset) {
+        unsigned long long z[2] = {0, 0};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(jfs::JFS_ZNS::g_zsplit_counts), z, sizeof(z)) != hipSuccess) return -1;
+    }
+    return 0;
+}
+}  // namespace
+
+#ifdef JFS_ZSTD_DECODE_PREFIX_TU
+extern "C" int jfs_zstd_prefix_split_counts_add(uint64_t *out, int reset) { return split_counts_add(out, reset); }
+#else
+extern "C" int jfs_zstd_prefix_split_counts_add(uint64_t *out, int reset);
 extern "C" int jfs_zstd_split_ok(int nblk, const uint64_t *tot) { return split_ok(nblk, tot) ? 1 : 0; }
 extern "C" int64_t jfs_zstd_split_bytes(int nblk, const uint64_t *tot) { return split_bytes(nblk, tot); }
 
 // Diagnostics: inputs the small-batch path replayed itself (out[0]) and
 // inputs it handed to the exact replay (out[1]) on the current device since
-// the last reset; synchronous.
+// the last reset, full and prefix decodes together; synchronous.
 extern "C" int jfs_zstd_split_counts(uint64_t *out, int reset) {
-    unsigned long long v[2] = {0, 0};
-    if (hipMemcpyFromSymbol(v, HIP_SYMBOL(jfs::zstdd::g_zsplit_counts), sizeof(v)) != hipSuccess) return -1;
-    out[0] = v[0];
-    out[1] = v[1];
-    if (reset) {
-        unsigned long long z[2] = {0, 0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(jfs::zstdd::g_zsplit_counts), z, sizeof(z)) != hipSuccess) return -1;
-    }
-    return 0;
+    out[0] = out[1] = 0;
+    if (split_counts_add(out, reset) != 0) return -1;
+    return jfs_zstd_prefix_split_counts_add(out, reset);
 }
+#endif
 
 // Device API: zscan -> zplan -> entropy -> execute on `stream`.  The call
 // waits once on the host for zscan/zplan (the inputs' frame headers: a few
@@ -2668,9 +2487,11 @@ extern "C" int jfs_zstd_split_counts(uint64_t *out, int reset) {
 // the scratch the launch needs, grows the device's scratch if it is short and
 // re-plans, then enqueues the entropy and execute kernels without waiting.
 // So every input fits its scratch and ret is never E_SCRATCH.
-extern "C" int jfs_launch_zstd_decode(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, uint8_t *,
-                                      hipStream_t stream) {
-    using namespace jfs::zstdd;
+// d_want (the prefix unit only): where each input's decode may stop.
+namespace {
+int launch_device(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, [[maybe_unused]] const int32_t *d_want,
+                  hipStream_t stream) {
+    using namespace jfs::JFS_ZNS;
     if (nblk <= 0) return 0;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -1;
@@ -2690,7 +2511,11 @@ extern "C" int jfs_launch_zstd_decode(const jfs_dev_block *d_blocks, int nblk, i
     }
     // launches that share the scratch run in call order across streams
     if (hipStreamWaitEvent(stream, z.ev_done, 0) != hipSuccess) return -1;
+#ifdef JFS_ZSTD_DECODE_PREFIX_TU
+    hipLaunchKernelGGL(zscan_kernel, dim3((nblk + 63) / 64), dim3(64), 0, stream, d_blocks, nblk, z.d_info, d_want);
+#else
     hipLaunchKernelGGL(zscan_kernel, dim3((nblk + 63) / 64), dim3(64), 0, stream, d_blocks, nblk, z.d_info);
+#endif
     if (hipGetLastError() != hipSuccess) return -1;
     hipLaunchKernelGGL(zplan_kernel, dim3(1), dim3(PLAN_T), 0, stream, z.d_info, nblk, (uint64_t)z.items_cap,
                        (uint64_t)z.lit_cap, (uint64_t)z.tabs_cap, z.d_need);
@@ -2721,6 +2546,55 @@ extern "C" int jfs_launch_zstd_decode(const jfs_dev_block *d_blocks, int nblk, i
     }
     return hipEventRecord(z.ev_done, stream) == hipSuccess ? 0 : -1;
 }
+}  // namespace
+
+#ifdef JFS_ZSTD_DECODE_PREFIX_TU
+// Input i stops at the block that reaches d_want[i] output bytes (DESIGN.md
+// 12d; the contract is jfs_zstd_decompress_prefix_device's in the header).
+extern "C" int jfs_launch_zstd_decode_prefix(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret,
+                                             const int32_t *d_want, hipStream_t stream) {
+    return launch_device(d_blocks, nblk, d_ret, d_want, stream);
+}
+
+// jfs_zstd_plan_host for a prefix decode: wants[i] as d_want above.  info[i]
+// records the clamped want and whether the walk stopped (ZInfo::want_st), n_blk
+// the blocks walked; totals[5] is the largest clamped want.
+extern "C" void jfs_zstd_plan_host_prefix(const uint8_t *const *srcs, const int32_t *lens, const int32_t *caps,
+                                          const int32_t *wants, int nblk, void *info_out, uint64_t *totals) {
+    using namespace jfs::JFS_ZNS;
+    ZInfo *info = (ZInfo *)info_out;
+    uint64_t oi = 0, ol = 0, ot = 0, ob = 0, oo = 0, mw = 0;
+    for (int i = 0; i < nblk; i++) {
+        ZInfo &z = info[i];
+        z = ZInfo{};
+        const int32_t want = want_clamp(wants[i], caps[i]);
+        zscan_one<true>((const gc_u8 *)srcs[i], lens[i], caps[i], want, z);
+        z.item_off = oi;
+        z.lit_off = ol;
+        z.tab_off = ot;
+        z.lit_err_blk = 0xFFFFFFFFu;
+        z.lit_err_code = 0;
+        z.ovf = 0;
+        oi += z.n_items;
+        ol += (z.lit_bytes + 15u) & ~15u;
+        ot += (uint64_t)z.n_cblk * TAB_STRIDE;
+        const uint64_t c = caps[i] > 0 ? (uint64_t)caps[i] : 0u;
+        ob += z.n_blk;
+        oo += (c + 3) & ~3ull;
+        mw = std::max(mw, (uint64_t)want);
+    }
+    totals[0] = oi + 64;
+    totals[1] = ol + 4096 + 64;
+    totals[2] = ot + 64;
+    totals[3] = ob;
+    totals[4] = oo;
+    totals[5] = mw;
+}
+#else
+extern "C" int jfs_launch_zstd_decode(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, uint8_t *,
+                                      hipStream_t stream) {
+    return launch_device(d_blocks, nblk, d_ret, nullptr, stream);
+}
 
 // Batch path (capi.hip run_batch): the caller planned the scratch on the host
 // from its host copy of the inputs (jfs_zstd_plan_host) and owns the scratch
@@ -2742,13 +2616,14 @@ extern "C" int jfs_launch_zstd_decode_planned(const jfs_dev_block *d_blocks, int
 extern "C" size_t jfs_zstd_info_bytes(void) { return sizeof(jfs::zstdd::ZInfo); }
 extern "C" void jfs_zstd_plan_host(const uint8_t *const *srcs, const int32_t *lens, const int32_t *caps, int nblk,
                                    void *info_out, uint64_t *totals) {
-    using namespace jfs::zstdd;
+    using namespace jfs::JFS_ZNS;
     ZInfo *info = (ZInfo *)info_out;
     uint64_t oi = 0, ol = 0, ot = 0, ob = 0, oo = 0, mc = 0;
     for (int i = 0; i < nblk; i++) {
         ZInfo &z = info[i];
         z = ZInfo{};
-        zscan_one((const gc_u8 *)srcs[i], lens[i], caps[i], z);
+        zscan_one<false>((const gc_u8 *)srcs[i], lens[i], caps[i], INT32_MAX, z);
+        z.want_st = (uint32_t)INT32_MAX;  // the whole input, not stopped
         z.item_off = oi;
         z.lit_off = ol;
         z.tab_off = ot;
@@ -2770,6 +2645,7 @@ extern "C" void jfs_zstd_plan_host(const uint8_t *const *srcs, const int32_t *le
     totals[4] = oo;
     totals[5] = mc;
 }
+#endif  // JFS_ZSTD_DECODE_PREFIX_TU
 
 #ifdef JFS_PROF
 extern "C" int jfs_zprof_read(unsigned long long *out) {

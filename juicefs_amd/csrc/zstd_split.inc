@@ -117,7 +117,7 @@ __global__ __launch_bounds__(64) void zswalk_kernel(const jfs_dev_block *__restr
     const uint32_t cap_items = zi.n_items, cap_blk = zi.n_blk;
     const int64_t lend = zi.lit_bytes;
     Walk w;
-    walk_init(w, s, b.src_len, b.dst_cap);
+    walk_init(w, s, b.src_len, b.dst_cap, zwant(zi));
     uint32_t cur = 0, nb = 0;
     int bug = 0, clean = 0, frames = 0, in_frame = 0, check = 0, first = 0, has_fcs = 0;
     uint64_t fcs = 0;
@@ -135,8 +135,9 @@ __global__ __launch_bounds__(64) void zswalk_kernel(const jfs_dev_block *__restr
     for (;;) {
         int32_t err = 0;
         uint32_t fl = 0, chk = 0;
-        const int ev = walk_next(w, &err, &fl, &chk);
-        if (ev == EV_DONE) { clean = !in_frame; break; }
+        const int ev = walk_next<ZPFX>(w, &err, &fl, &chk);
+        // (prefix decode) a walk stopped inside its one frame is a proven case too: no frame end, so no checks
+        if (ev == EV_DONE) { clean = !in_frame || (ZPFX && w.stopped); break; }
         if (ev == EV_ERROR) { put(0, 0, (uint32_t)err, IT_ERR); break; }
         if (ev == EV_FSTART) {
             frames++;
@@ -680,6 +681,9 @@ __global__ __launch_bounds__(64) void zsfix_kernel(const jfs_dev_block *__restri
     }
     if (si.has_fcs && (uint64_t)run != si.fcs) ok = 0;
     if (run > 0x7FFFFFFF) ok = 0;
+    // prefix decode: the origin map is settled and gathered over [0, want) only
+    // (origins point backwards), and that is the result
+    if (ZPFX && run > (int64_t)zwant(zi)) run = zwant(zi);
     if (l == 0) {
         zi.lit_err_blk = lerr_blk;
         zi.lit_err_code = lerr_code;
@@ -718,6 +722,7 @@ __global__ __launch_bounds__(ST) void zsemit_kernel(int nblk, const ZInfo *__res
     g_u32 *org = (g_u32 *)(sc.org + si.org_off);
     const int t = threadIdx.x;
     const int64_t o0 = d.out;
+    if (ZPFX && o0 >= si.total) return;  // prefix decode: a block behind `want` (si.total <= want) is never read
     if (d.btype != 2) {
         for (int64_t i = part * ST + t; i < d.bsize; i += ST * ZSE_PARTS)
             org[o0 + i] = (uint32_t)(-(int64_t)(d.lpos + i) - 1);

@@ -85,6 +85,17 @@ def lz4_decompress_prefix_small(desc: torch.Tensor, want: torch.Tensor, ret: tor
            "jfs_lz4_decompress_prefix_device_small")
 
 
+def zstd_decompress_prefix(desc: torch.Tensor, want: torch.Tensor, ret: torch.Tensor, stream=None):
+    """jfs_zstd_decompress_prefix_device: input i is decoded as far as the Zstd
+    block that reaches its first want[i] bytes (want: an int32 device tensor,
+    one entry per descriptor); ret[i] = min(size, want[i]) for a well-formed
+    input."""
+    n = desc.numel() // DESC_DTYPE.itemsize
+    assert want.dtype == torch.int32 and want.numel() >= n
+    _check(L.load().jfs_zstd_decompress_prefix_device(desc.data_ptr(), want.data_ptr(), n, ret.data_ptr(),
+                                                      _stream_ptr(stream)), "jfs_zstd_decompress_prefix_device")
+
+
 def lz4_split_counts(reset: bool = False):
     """(blocks the small-batch path decoded itself, blocks it handed to the
     one-workgroup kernel, ... the reasons: fix-up, jumping, token, no last run)

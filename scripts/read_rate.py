@@ -17,6 +17,14 @@ out of 64 text-class source blocks x 4 MiB, on one GPU.
       and 64 sources with every segment ending at its block's last byte
       (need == dst_cap everywhere: prefix mode takes the full launchers).
       --only-decode skips (a)-(c).
+  (e) --zstd-front (with --decode full prefix-all): Zstd sources, modes
+      alternating call by call in one process, on two workloads: "front" -- one
+      128 KiB read from offset 0 of each of 64 sources x 4 MiB, what sequential
+      readers and the prefetcher produce -- and (a)'s random reads.  Beside the
+      call's wall time: the decode stage alone under device events
+      (jfs_zstd_decompress_device against jfs_zstd_decompress_prefix_device on
+      the staged sources), and the Zstd blocks walked against the blocks in the
+      frames (jfs_zstd_plan_host_prefix).  Runs alone, like --only-decode.
 
 Medians of --reps calls after --warmup calls, one process.  Needs a GPU;
 writes one JSON file."""
@@ -91,7 +99,7 @@ def decode_modes(a, res):
                     t1 = time.perf_counter()
                     assert all(e is None for _, e in sres + rres)
                     if it == 0:
-                        assert [n for n, _ in sres] == (need if mode == "prefix" else [U] * nsrc)
+                        assert [n for n, _ in sres] == (need if mode != "full" else [U] * nsrc)
                         for j in range(NREAD):
                             assert np.array_equal(dst[j], want[j]), (wname, mode, j)
                     if it >= a.warmup:
@@ -103,6 +111,115 @@ def decode_modes(a, res):
             w["prefix_over_full"] = w["prefix"]["read_batch_ms"] / w["full"]["read_batch_ms"]
         out[wname] = w
     res["decode_modes"] = out
+
+
+def zstd_front(a, res):
+    """(e): ReadBatch on Zstd sources, full and prefix-all alternating"""
+    import ctypes
+    import struct
+    import torch
+    from juicefs_amd import compress as C
+    from juicefs_amd import device as D
+    from juicefs_amd import _lib as L
+    lib = L.load()
+    lib.jfs_zstd_plan_host_prefix.restype = None
+    dev = torch.device("cuda:0")
+    c = C.NewCompressor("zstd")
+    raw_t = torch.empty(NSRC * U, dtype=torch.uint8, device=dev)
+    D.gen_blocks(raw_t, NSRC, U, "T", 7000)
+    torch.cuda.synchronize()
+    raw = raw_t.cpu().numpy()
+    del raw_t
+    sd = [bytearray(c.CompressBound(U)) for _ in range(NSRC)]
+    r = c.CompressBatch([(sd[i], raw[i * U:(i + 1) * U]) for i in range(NSRC)])
+    assert all(e is None for _, e in r)
+    stored = [bytes(sd[i][:r[i][0]]) for i in range(NSRC)]
+    srcs = [(s, U) for s in stored]
+    modes = [m for m in a.decode if m in ("full", "prefix-all")]
+    assert modes, "--zstd-front measures the modes full and prefix-all"
+    out = {}
+    for wname in ("front", "random"):
+        if wname == "front":
+            seg_first, seg = list(range(NSRC + 1)), [(i, 0, 0, READ) for i in range(NSRC)]
+        else:
+            seg_first, seg = plan()
+        nread = len(seg_first) - 1
+        need = [0] * NSRC
+        for src, so, _, n in seg:
+            need[src] = max(need[src], so + n)
+        dst = [np.empty(READ, dtype=np.uint8) for _ in range(nread)]
+        want = [np.empty(READ, dtype=np.uint8) for _ in range(nread)]
+        for j in range(nread):
+            for src, so, do, n in seg[seg_first[j]:seg_first[j + 1]]:
+                want[j][do:do + n] = raw[src * U + so:src * U + so + n]
+        # blocks walked against blocks in the frames (host plan)
+        walked = total = 0
+        for s, nd in zip(stored, need):
+            buf = ctypes.create_string_buffer(s, len(s))
+            for w, acc in ((nd, "walked"), (U, "total")):
+                info, tot = ctypes.create_string_buffer(64), (ctypes.c_uint64 * 6)()
+                lib.jfs_zstd_plan_host_prefix((ctypes.c_void_p * 1)(ctypes.addressof(buf)), (ctypes.c_int32 * 1)(len(s)),
+                                              (ctypes.c_int32 * 1)(U), (ctypes.c_int32 * 1)(w), 1, info, tot)
+                nb = struct.unpack_from("<I", info.raw, 52)[0]
+                if acc == "walked":
+                    walked += nb
+                else:
+                    total += nb
+        w = {"sources": NSRC, "reads": nread, "segments": len(seg), "decoded_bytes_full": NSRC * U,
+             "decoded_bytes_needed": sum(need), "zstd_blocks_in_frames": total, "zstd_blocks_walked": walked}
+        ms = {m: [] for m in modes}
+        for it in range(a.warmup + a.reps):
+            for mode in modes:  # alternating
+                prev = C.set_read_decode_mode(mode)
+                try:
+                    t0 = time.perf_counter()
+                    sres, rres, _ = c.ReadBatch(srcs, dst, (seg_first, seg))
+                    t1 = time.perf_counter()
+                finally:
+                    C.set_read_decode_mode(prev)
+                assert all(e is None for _, e in sres + rres)
+                if it == 0:
+                    assert [n for n, _ in sres] == ([min(U, x) for x in need] if mode == "prefix-all" else [U] * NSRC)
+                    for j in range(nread):
+                        assert np.array_equal(dst[j], want[j]), (wname, mode, j)
+                if it >= a.warmup:
+                    ms[mode].append((t1 - t0) * 1e3)
+        for m in modes:
+            w[m] = {"read_batch_ms": med(ms[m]), "min_ms": min(ms[m]), "max_ms": max(ms[m])}
+        # the decode stage alone, sources staged in HBM, device events
+        offs, o = [], 0
+        for s in stored:
+            offs.append(o)
+            o = (o + len(s) + 15) & ~15
+        host = np.zeros(o + 64, dtype=np.uint8)
+        for s, q in zip(stored, offs):
+            host[q:q + len(s)] = np.frombuffer(s, dtype=np.uint8)
+        src_t = torch.from_numpy(host).to(dev)
+        dst_t = torch.empty(NSRC * U, dtype=torch.uint8, device=dev)
+        desc = D.make_desc(src_t, offs, [len(s) for s in stored], dst_t, np.arange(NSRC, dtype=np.int64) * U, [U] * NSRC)
+        ret = torch.empty(NSRC, dtype=torch.int32, device=dev)
+        want_t = torch.tensor(need, dtype=torch.int32, device=dev)
+        ev = {"full": [], "prefix-all": []}
+        for it in range(a.warmup + a.reps):
+            for mode in modes:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                if mode == "full":
+                    D.zstd_decompress(desc, ret)
+                else:
+                    D.zstd_decompress_prefix(desc, want_t, ret)
+                e1.record()
+                torch.cuda.synchronize()
+                assert ret.cpu().tolist() == ([U] * NSRC if mode == "full" else [min(U, x) for x in need])
+                if it >= a.warmup:
+                    ev[mode].append(e0.elapsed_time(e1))
+        for m in modes:
+            w[m].update({"decode_stage_ms": med(ev[m]), "decode_stage_min_ms": min(ev[m]), "decode_stage_max_ms": max(ev[m])})
+        if len(modes) == 2:
+            w["prefix_all_over_full"] = w["prefix-all"]["read_batch_ms"] / w["full"]["read_batch_ms"]
+            w["decode_stage_prefix_all_over_full"] = w["prefix-all"]["decode_stage_ms"] / w["full"]["decode_stage_ms"]
+        out[wname] = w
+    res["zstd_front"] = out
 
 
 def slice_reads(dec, seg_first, seg, outs):
@@ -120,9 +237,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--decode", nargs="+", choices=["full", "prefix"], default=["full"],
+    ap.add_argument("--decode", nargs="+", choices=["full", "prefix", "prefix-all"], default=["full"],
                     help="decode modes of the read calls to measure in (d), in this order")
     ap.add_argument("--only-decode", action="store_true", help="measure (d) alone")
+    ap.add_argument("--zstd-front", action="store_true", help="measure (e) alone: Zstd, full against prefix-all")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "read_assembly", "read_rate.json"))
     a = ap.parse_args()
     import torch
@@ -131,6 +249,10 @@ def main():
     from juicefs_amd import _lib as L
     assert torch.cuda.is_available(), "read_rate.py measures on a GPU"
     dev = torch.device("cuda:0")
+    if a.zstd_front:
+        res = {"shape": {"block_bytes": U, "read_bytes": READ}, "reps": a.reps, "warmup": a.warmup}
+        zstd_front(a, res)
+        return write(a, res)
     if a.only_decode:
         res = {"shape": {"block_bytes": U, "reads": NREAD, "read_bytes": READ, "gathered_bytes": NREAD * READ},
                "reps": a.reps, "warmup": a.warmup}
