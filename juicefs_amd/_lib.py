@@ -48,6 +48,7 @@ EXPORTS = [
     "jfs_read_batch_csum", "jfs_read_open_batch_csum", "jfs_open_decompress_batch_csum",
     "jfs_read_csum_device",
     "jfs_zstd_decompress_prefix_device", "jfs_set_read_decode_mode_ext",
+    "jfs_test_set_split_jump_rounds",
 ]
 # the hook include/jfs_gpucodec_lz4_fast_test.h declares (the fast LZ4 encoder's host twin)
 LZ4_FAST_TEST_EXPORTS = ["jfs_test_lz4_fast_host"]
@@ -144,6 +145,8 @@ def load() -> ctypes.CDLL:
     lib.jfs_lz4_split_counts.restype = ctypes.c_int
     lib.jfs_zstd_split_counts.argtypes = [vp, ctypes.c_int]
     lib.jfs_zstd_split_counts.restype = ctypes.c_int
+    lib.jfs_test_set_split_jump_rounds.argtypes = [ctypes.c_int, ctypes.c_int]
+    lib.jfs_test_set_split_jump_rounds.restype = ctypes.c_int
     lib.jfs_lz4_compress_device_small.argtypes = [vp, vp, ctypes.c_int, vp, vp]
     lib.jfs_lz4_compress_device_small.restype = ctypes.c_int64
     lib.jfs_lz4_compress_fast_device.argtypes = [vp, vp, ctypes.c_int, vp, vp]

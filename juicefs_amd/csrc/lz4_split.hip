@@ -75,7 +75,7 @@ struct SBlock {
 };
 
 struct BStat {
-    int32_t bad, last_ok, total, todo;
+    int32_t bad, last_ok, total, todo;  // bad: 1 = outside the proven cases, 2 = the stream ends in a match
     int32_t unsettled;  // the gather met an entry that is not a literal yet
     int32_t fix[FIX_ROUNDS];
     int32_t jmp[JUMP_ROUNDS];
@@ -380,6 +380,11 @@ __device__ __forceinline__ bool tok_ok(uint32_t tok, const Tok &t, int32_t n, in
     return ok;
 }
 
+// a rejected token that is a whole sequence, match included, and ends the
+// stream: the block has no final literal run (BStat::bad = 2, the verdict's
+// reason [5]; such a token always fails tok_ok -- its literals end past n - 8)
+__device__ __forceinline__ bool ends_in_match(const Tok &t, int32_t n) { return !t.last && !t.cut && t.next >= n; }
+
 // One WAVE per segment: the segment's true tokens are parsed wave-uniformly
 // and each token's origin run is written by the whole wave (consecutive
 // entries per lane: coalesced stores).  (One thread per segment wrote ~2 KB
@@ -438,7 +443,7 @@ __global__ __launch_bounds__(T) void emit_kernel(int nb, int nseg_all, Scratch s
         const Tok t = parse_rd(rd, n, x, true);
         const bool ok = tok_ok(t.tok, t, n, op, cap);
         if (!ok) {
-            if (l == 0) st.bad = 1;
+            if (l == 0) st.bad = ends_in_match(t, n) ? 2 : 1;
             return;
         }
         const uint32_t v0 = (uint32_t)(-(t.lenip) - 1);  // literal entry i = v0 - i
@@ -491,7 +496,7 @@ __global__ __launch_bounds__(T) void emit_thread_kernel(int nb, int nseg_all, Sc
         const Tok t = parse(s, n, x, true);
         const bool ok = tok_ok(t.tok, t, n, op, cap);
         if (!ok) {
-            st.bad = 1;
+            st.bad = ends_in_match(t, n) ? 2 : 1;
             return;
         }
         // origin entries, 16-byte stores where the run is 4-aligned (the
@@ -604,8 +609,8 @@ __global__ void verdict_kernel(int nb, Scratch sc, int32_t *__restrict__ ret, in
     // why a block was handed over: fix-up / jumping did not converge, a token
     // outside the proven cases, no final literal run
     if (st.fix[FIX_ROUNDS - 1]) atomicAdd(&g_split_counts[2], 1ull);
-    else if (st.bad) atomicAdd(&g_split_counts[4], 1ull);
-    else if (!st.last_ok && st.total <= want) atomicAdd(&g_split_counts[5], 1ull);
+    else if (st.bad == 1) atomicAdd(&g_split_counts[4], 1ull);
+    else if (st.bad || (!st.last_ok && st.total <= want)) atomicAdd(&g_split_counts[5], 1ull);
     else if (st.unsettled) atomicAdd(&g_split_counts[3], 1ull);
 }
 
@@ -659,6 +664,10 @@ extern "C" int64_t jfs_lz4_split_scratch_bytes(int nb, const int32_t *src_len, c
     return a256(nb * (int64_t)sizeof(SBlock)) + a256(nb * (int64_t)sizeof(BStat)) + 3 * a256(seg * 4) +
            a256(seg * (SEG / 8)) + a256(org * 4) + a256(nb * 4) + 256;
 }
+
+// Test only (jfs_test_set_split_jump_rounds): the pointer-jumping rounds to
+// launch instead of the computed count; 0 = the computed count.
+static int g_test_jump_rounds = 0;
 
 // nseg_all / max_cap: Σ segments and the largest dst_cap (grid sizes); the
 // host computes both from the same (src_len, cap) it sized the scratch with.
@@ -715,6 +724,7 @@ static int launch_split(const jfs_dev_block *d_desc, int nb, int32_t *d_ret, con
     // of a lone decode).  The gather checks every entry regardless.
     int jr = 1;
     for (double reach = HOPS; reach <= (double)max_want / 4 + 1 && jr < JUMP_ROUNDS; reach *= HOPS) jr++;
+    if (g_test_jump_rounds > 0) jr = g_test_jump_rounds;
     for (int r = 0; r < jr; r++) hipLaunchKernelGGL(jump_kernel, dim3(jx, (unsigned)nb), dim3(T), 0, st, sc, r);
     hipLaunchKernelGGL(gather_kernel, gp, dim3(T), 0, st, sc);
     hipLaunchKernelGGL(verdict_kernel, dim3((nb + 63) / 64), dim3(64), 0, st, nb, sc, d_ret, todo);
@@ -734,6 +744,15 @@ extern "C" int jfs_launch_lz4_split_prefix(const jfs_dev_block *d_desc, int nb, 
                                            int64_t max_want, hipStream_t st) {
     if (!d_want) return -1;
     return launch_split<true>(d_desc, nb, d_ret, d_want, d_scratch, nseg_all, max_cap, norg_all, max_want, st);
+}
+
+// Test hook (include/jfs_gpucodec_test.h): each translation unit that sizes a
+// jump loop keeps its own override.
+extern "C" int jfs_test_set_split_jump_rounds(int lz4_rounds, int zstd_rounds) {
+    g_test_jump_rounds = std::max(0, std::min(lz4_rounds, JUMP_ROUNDS));
+    jfs_zstd_split_test_jump_rounds(zstd_rounds);
+    jfs_zstd_prefix_split_test_jump_rounds(zstd_rounds);
+    return 0;
 }
 
 // Diagnostics: blocks the small-batch path decoded itself (out[0]) and blocks

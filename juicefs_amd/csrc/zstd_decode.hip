@@ -2407,6 +2407,10 @@ int64_t split_bytes(int nblk, const uint64_t *tot) {
            a256((int64_t)nblk * 4) + a256((int64_t)tot[4] * 4) + 256;
 }
 
+// Test only (jfs_test_set_split_jump_rounds): the pointer-jumping rounds to
+// launch instead of the computed count; 0 = the computed count.
+int g_test_jump_rounds = 0;
+
 int launch_split(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, jfs::zstdd::ZInfo *d_info, uint8_t *d_lit,
                  uint4 *d_items, void *d_split, const uint64_t *tot, hipStream_t st) {
     using namespace jfs::JFS_ZNS;
@@ -2439,6 +2443,7 @@ int launch_split(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, jfs::z
     // for 4 MiB).  The gather checks every entry regardless.
     int jr = 1;
     for (double reach = SJ_HOPS; reach <= (double)max_cap / 3 + 1 && jr < SJ_ROUNDS; reach *= SJ_HOPS) jr++;
+    if (g_test_jump_rounds > 0) jr = g_test_jump_rounds;
     for (int r = 0; r < jr; r++) hipLaunchKernelGGL(zsjump_kernel, dim3(jx, (unsigned)nblk), dim3(ST), 0, st, sc, r);
     hipLaunchKernelGGL(zsgather_kernel, dim3((unsigned)((max_cap / 4 + ST) / ST), (unsigned)nblk), dim3(ST), 0, st,
                        d_blocks, (const ZInfo *)d_info, (const uint8_t *)d_lit, sc);
@@ -2466,8 +2471,14 @@ int split_counts_add(uint64_t *out, int reset) {
 
 #ifdef JFS_ZSTD_DECODE_PREFIX_TU
 extern "C" int jfs_zstd_prefix_split_counts_add(uint64_t *out, int reset) { return split_counts_add(out, reset); }
+extern "C" void jfs_zstd_prefix_split_test_jump_rounds(int rounds) {
+    g_test_jump_rounds = std::max(0, std::min(rounds, (int)jfs::JFS_ZNS::SJ_ROUNDS));
+}
 #else
 extern "C" int jfs_zstd_prefix_split_counts_add(uint64_t *out, int reset);
+extern "C" void jfs_zstd_split_test_jump_rounds(int rounds) {
+    g_test_jump_rounds = std::max(0, std::min(rounds, (int)jfs::JFS_ZNS::SJ_ROUNDS));
+}
 extern "C" int jfs_zstd_split_ok(int nblk, const uint64_t *tot) { return split_ok(nblk, tot) ? 1 : 0; }
 extern "C" int64_t jfs_zstd_split_bytes(int nblk, const uint64_t *tot) { return split_bytes(nblk, tot); }
 

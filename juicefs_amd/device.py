@@ -113,6 +113,13 @@ def zstd_split_counts(reset: bool = False):
     return tuple(int(x) for x in out)
 
 
+def set_split_jump_rounds(lz4: int = 0, zstd: int = 0):
+    """Test hook (jfs_test_set_split_jump_rounds): the pointer-jumping rounds
+    the small-batch decoders launch, full and prefix; 0 = the computed count.
+    Process-global: a test that sets it restores (0, 0)."""
+    _check(L.load().jfs_test_set_split_jump_rounds(int(lz4), int(zstd)), "jfs_test_set_split_jump_rounds")
+
+
 def lz4_compress_small(desc: torch.Tensor, ret: torch.Tensor, src_lens, stream=None):
     """jfs_lz4_compress_device_small: few blocks, each parsed as segments
     across the GPU (same bytes as lz4_compress); src_lens = host copies."""

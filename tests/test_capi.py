@@ -23,7 +23,9 @@ def header_functions(names=("jfs_gpucodec.h", "jfs_gpucodec_test.h")):
 def test_test_hooks_not_in_public_header():
     # the lock-order test hook is not part of the drop-in ABI
     assert "jfs_test_spread_locking" not in header_functions(("jfs_gpucodec.h",))
-    assert header_functions(("jfs_gpucodec_test.h",)) == ["jfs_test_spread_locking"]
+    # nor is the small-batch decoders' jump-round override
+    assert "jfs_test_set_split_jump_rounds" not in header_functions(("jfs_gpucodec.h",))
+    assert header_functions(("jfs_gpucodec_test.h",)) == ["jfs_test_set_split_jump_rounds", "jfs_test_spread_locking"]
 
 
 def test_exports_every_header_symbol(lib):

@@ -15,6 +15,7 @@ import torch
 from juicefs_amd import compress as C
 from juicefs_amd import device as D
 from juicefs_amd.blockgen import gen_block
+from tests.split_streams import chain_stream as _chain_stream
 
 pytestmark = pytest.mark.gpu
 
@@ -229,19 +230,6 @@ def test_split_device_sizes_beyond_host_budget_go_exact(gpu, oracle):
         assert dh[o:o + len(s)].tobytes() == s
     done, handed = D.lz4_split_counts()[:2]
     assert handed == len(srcs), (done, handed)
-
-
-def _chain_stream(units, seed=7):
-    """An LZ4 stream of `units` 11-byte output units, each one literal byte and
-    a 10-byte match at offset 11: every match byte copies the same byte of the
-    unit before, so its origin chain runs back through every earlier unit."""
-    rng = random.Random(seed)
-    first = bytes(rng.randrange(256) for _ in range(11))
-    out = bytearray([0xB6]) + first + (11).to_bytes(2, "little")  # ll 11, ml 10
-    for _ in range(units - 1):
-        out += bytes([0x16, rng.randrange(256)]) + (11).to_bytes(2, "little")  # ll 1, ml 10
-    out += bytes([0xF0, 1]) + bytes(rng.randrange(256) for _ in range(16))  # last: 16 literals
-    return bytes(out)
 
 
 def test_split_deep_origin_chains(gpu, oracle):
