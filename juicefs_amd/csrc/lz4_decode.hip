@@ -31,6 +31,7 @@
 #include "jfs_internal.h"
 #include "lz4_put16.h"
 #include "lz4_tailpack.h"
+#include "lz4_walkstep.h"
 #include "wave.cuh"
 
 namespace jfs {
@@ -76,17 +77,25 @@ static_assert(R == (int)TP_RING && LMAX <= (int)TP_LEN_MAX, "tail_pack field wid
 
 #ifdef JFS_PROF
 // diagnostic build only: per-phase cycle sums (s_memtime), never in the product .so
-#define NPROF 20  // 0..9 phase cycles, 10..19 event counts
+// 0..9 phase cycles, 10..19 event counts; 20..29 the waits and the walk by
+// where a window sits in its span: 20 / 21 copier / parser wait
+// cycles of a span's first window, 22 spans, 23 walk iterations the blocking
+// advance at a span boundary ran, 24 its cycles, 25 boundaries that found the
+// walk final, 26 lane steps redone exactly after a deferred e2 test (their
+// re-loads are dropped), 27 walk iterations with such a lane, 28 lanes that
+// only arrived (a step past the segment's end to settle the test)
+#define NPROF 30
 __device__ uint64_t g_prof[NPROF];
 struct Prof {
-    uint64_t t, acc[NPROF];
+    uint64_t t, last, acc[NPROF];
     __device__ void start() {
         t = __builtin_amdgcn_s_memtime();
         for (int i = 0; i < NPROF; i++) acc[i] = 0;
     }
     __device__ void stamp(int k) {
         uint64_t x = __builtin_amdgcn_s_memtime();
-        acc[k] += x - t;
+        last = x - t;
+        acc[k] += last;
         t = x;
     }
     __device__ void flush_out() {
@@ -96,17 +105,28 @@ struct Prof {
 };
 #define PSTAMP(k) pr.stamp(k)
 #define PCOUNT(k, n) (pr.acc[k] += (n))
+#define PFIRST(...) __VA_ARGS__
+#define PWALK(kind)                                                        \
+    do {                                                                   \
+        const uint64_t re_ = __ballot((kind) == WS_REDONE);                \
+        pr.acc[26] += (uint64_t)__popcll(re_);                             \
+        pr.acc[27] += re_ != 0;                                            \
+        pr.acc[28] += (uint64_t)__popcll(__ballot((kind) == WS_ARRIVED)); \
+    } while (0)
 #define PROF_ARG , Prof &pr
 #define PROF_PASS , pr
 #else
 #define PSTAMP(k)
 #define PCOUNT(k, n)
+#define PFIRST(...)
+#define PWALK(kind) (void)(kind)
 #define PROF_ARG
 #define PROF_PASS
 #endif
 
 // Published by the parser wave for each window it stages (double-buffered).
 enum { W_NONE = 0, W_WIN = 1, W_SER = 2, W_BUG = 3 };
+constexpr int32_t W_PFIRST = 16;  // profiling build only: the window is its span's first
 struct Meta {
     int32_t kind, wbase, cbase;
     uint32_t T, efin;
@@ -963,74 +983,17 @@ constexpr int SEG_MIN = 4;       // at least this many (more while the copier is
 
 // Next token position after p (or STOP | p): the exact chain rule of
 // parse_tok, bytes from HBM.
+static_assert(WS_STOP == STOP && WS_KEXT == KEXT, "lz4_walkstep.h restates the parser's constants");
 __device__ __noinline__ uint32_t g_next_exact(const Ctx &c, int32_t p) {
-    const int32_t n = c.n;
-    if (p > n - 18) return STOP | (uint32_t)p;
-    const uint32_t tb = c.src[p];
-    int32_t q = p + 1;
-    int32_t ll = (int32_t)(tb >> 4);
-    if (ll == 15) {
-        int k = 0;
-        uint32_t sv;
-        do {
-            sv = c.src[q];
-            q++;
-            ll += (int32_t)sv;
-            if (q >= n - 15 || ++k > KEXT) return STOP | (uint32_t)p;
-        } while (sv == 255);
-        if (q + ll > n - 32) return STOP | (uint32_t)p;
-    }
-    q += ll + 2;
-    if ((tb & 15u) == 15u) {
-        int k = 0;
-        uint32_t sv;
-        do {
-            sv = c.src[q];
-            q++;
-            if (q >= n - 4 || ++k > KEXT) return STOP | (uint32_t)p;
-        } while (sv == 255);
-    }
-    return (uint32_t)q;
+    return ws_next_exact([&](uint32_t i) { return (uint32_t)c.src[i]; }, c.n, p);
 }
 
-// Lean step from HBM: the token byte and the byte after it, then the first
-// match-length byte (two dependent load rounds).  A literal length with one
-// extension byte is taken here; tokens with a 255 extension byte (runs of
-// >= 270 literals or >= 274-byte matches) take g_next_exact.
-__device__ __forceinline__ uint32_t g_step(const Ctx &c, int32_t p, bool act) {
-    // unsigned 32-bit offsets from the uniform base: saddr loads, no 64-bit
-    // address arithmetic; bitwise 0/1 logic: no exec-mask branches
-    const int32_t n = c.n;
-    const uint32_t edge = (uint32_t)(p > n - 18);
-    const uint32_t up = (uint32_t)p;
-    const uint32_t tb = c.src[edge ? 0u : up], e1 = c.src[edge ? 0u : up + 1u];
-    const uint32_t hi = tb >> 4;
-    const uint32_t llx = (uint32_t)(hi == 15u);
-    const uint32_t L = llx ? 15u + e1 : hi;
-    const uint32_t lstop = llx & ((uint32_t)(p + 2 >= n - 15) | (uint32_t)(p + 2 + (int32_t)L > n - 32));
-    const uint32_t q = up + 3u + llx + L;  // first match-length extension byte
-    const uint32_t e2 = c.src[(edge | lstop) ? 0u : q];
-    const uint32_t mlx = (uint32_t)((tb & 15u) == 15u);
-    uint32_t x = q + mlx;
-    const uint32_t slow = (uint32_t)act & (edge ^ 1u) & (lstop ^ 1u) & ((llx & (uint32_t)(e1 == 255u)) | (mlx & (uint32_t)(e2 == 255u)));
-    x = (edge | lstop | (mlx & (uint32_t)((int32_t)x >= n - 4))) ? (STOP | up) : x;
-    if (__ballot(slow)) {
-        if (slow) x = g_next_exact(c, p);
-    }
-    return x;
-}
-
-// 128-bit sets as two u64 (bit d = position plo + d)
-__device__ __forceinline__ bool tbit2(uint64_t a0, uint64_t a1, uint32_t d) {
-    return (((d < 64u ? a0 : a1) >> (d & 63u)) & 1ull) != 0;
-}
-__device__ __forceinline__ void sbit2(uint64_t &a0, uint64_t &a1, uint32_t d) {
-    const uint64_t m = 1ull << (d & 63u);
-    a0 |= d < 64u ? m : 0ull;
-    a1 |= d < 64u ? 0ull : m;
-}
-__device__ __forceinline__ uint64_t from_lo(uint32_t d) { return d < 64u ? (~0ull << (d & 63u)) : 0ull; }
-__device__ __forceinline__ uint64_t from_hi(uint32_t d) { return d < 64u ? ~0ull : (~0ull << (d & 63u)); }
+// The lean step from HBM is ws_round / ws_take of lz4_walkstep.h: the token
+// byte and the byte after it, one load round; the first match-length byte is
+// fetched but tested an iteration later (the deferred state pe2, pend of
+// SegWalk).  A literal length with one extension byte is taken there; tokens
+// with a 255 extension byte (runs of >= 270 literals or >= 274-byte matches)
+// take g_next_exact.
 
 // Chain of the span [base, base + SW), resumable: advance() runs at most
 // `budget` walk steps (one HBM load round each) and returns true once the
@@ -1047,6 +1010,8 @@ struct SegWalk {
     uint64_t vt0, vt1;    // true chain positions
     uint64_t vp0, vp1;    // positions of a fix-up walk
     bool mv;              // this lane is walking
+    uint32_t pe2;         // the byte fetched for a step's owed e2 test (lz4_walkstep.h)
+    bool pend;            // whether one is owed (the step: sx / ex while the lane moves)
     int phase;            // 0 speculative walk, 1 fix-up rounds, 2 final
     bool round;           // a fix-up round is to be started
     int steps, rounds;
@@ -1061,25 +1026,25 @@ struct SegWalk {
         vs0 = vs1 = vt0 = vt1 = vp0 = vp1 = 0;
         sx = ex = 0;
         mv = true;
+        pe2 = 0;
+        pend = false;
         phase = 0;
         round = false;
         steps = rounds = 0;
     }
 
     __device__ __forceinline__ bool advance(Ctx &c, int budget PROF_ARG) {
+        // unsigned 32-bit offsets from the uniform base: saddr loads, no 64-bit
+        // address arithmetic
+        const auto fetch = [&](uint32_t i) { return (uint32_t)c.src[i]; };
+        const auto exact = [&](int32_t p) { return g_next_exact(c, p); };
         // speculative walks (one load round trip per step for every lane)
         if (phase == 0) {
             for (; budget > 0 && __ballot(mv); --budget) {
                 PCOUNT(11, 1);
-                if (mv) {
-                    const uint32_t x = g_step(c, q, true);
-                    const bool stop = (x & STOP) != 0;
-                    if (!stop && q >= plo) sbit2(vs0, vs1, (uint32_t)(q - plo));
-                    const bool out = stop || (int32_t)x >= phi;
-                    sx = out ? x : sx;
-                    mv = !out;
-                    q = (int32_t)x;
-                }
+                int kind = WS_STEPPED;
+                if (mv) kind = ws_spec_iter(*this, fetch, exact, c.n);
+                PWALK(kind);
                 if (++steps > SEG + SPRE) { c.bug = 6; phase = 2; return true; }
             }
             if (budget == 0) return false;
@@ -1120,21 +1085,9 @@ struct SegWalk {
             }
             for (; budget > 0 && __ballot(mv); --budget) {
                 PCOUNT(13, 1);
-                if (mv) {
-                    const uint32_t d = (uint32_t)(q - plo);
-                    const bool join = tbit2(vs0, vs1, d);
-                    const uint32_t x = g_step(c, q, !join);
-                    const bool stop = !join && (x & STOP) != 0;
-                    if (!join && !stop) sbit2(vp0, vp1, d);
-                    const bool out = join || stop || (int32_t)x >= phi;
-                    if (out) {
-                        vt0 = vp0 | (join ? vs0 & from_lo(d) : 0ull);
-                        vt1 = vp1 | (join ? vs1 & from_hi(d) : 0ull);
-                        ex = join ? sx : x;
-                    }
-                    mv = !out;
-                    q = (int32_t)x;
-                }
+                int kind = WS_STEPPED;
+                if (mv) kind = ws_fix_iter(*this, fetch, exact, c.n);
+                PWALK(kind);
                 if (++steps > SEG + 1) { c.bug = 7; phase = 2; return true; }
             }
             if (!__ballot(mv)) round = true;
@@ -1262,6 +1215,7 @@ __device__ __forceinline__ void parser_wave(Smem &s, Ctx &c PROF_ARG) {
         m.cbase = 0;
         m.T = 0;
         m.efin = 0;
+        PFIRST(bool pfirst = false);
         if (!pstop) {
             if (pip < c.n - 64) {
                 use_buffer(s, c, buf);
@@ -1269,8 +1223,11 @@ __device__ __forceinline__ void parser_wave(Smem &s, Ctx &c PROF_ARG) {
                 if (!spv || pip >= sp.base + SW) {
                     // the span at pip: the walk started ahead of time, or a fresh one
                     if (!(spv && nxt && wk.base == pip)) wk.start(pip);
+                    PFIRST(const uint64_t it0 = pr.acc[11] + pr.acc[13]; pfirst = true);
                     wk.advance(c, 1 << 20 PROF_PASS);
                     PSTAMP(1);
+                    PFIRST(const uint64_t its = pr.acc[11] + pr.acc[13] - it0; pr.acc[22] += 1; pr.acc[23] += its;
+                           pr.acc[24] += pr.last; pr.acc[25] += its == 0);
                     sp.v0 = wk.vt0;
                     sp.v1 = wk.vt1;
                     sp.base = pip;
@@ -1292,6 +1249,7 @@ __device__ __forceinline__ void parser_wave(Smem &s, Ctx &c PROF_ARG) {
                 }
                 PSTAMP(1);
                 m.kind = c.bug ? W_BUG : W_WIN;
+                PFIRST(if (pfirst && !c.bug) m.kind |= W_PFIRST);
                 m.cbase = c.cbase;
                 m.T = T;
                 m.efin = efin;
@@ -1308,6 +1266,7 @@ __device__ __forceinline__ void parser_wave(Smem &s, Ctx &c PROF_ARG) {
                       rip = (int32_t)uniform((uint32_t)s.ctl.rip);
         wg_sync();
         PSTAMP(9);
+        PFIRST(if (pfirst) pr.acc[21] += pr.last);
         if (done) break;
         if (restart) {
             pip = rip;
@@ -1334,6 +1293,7 @@ __device__ __forceinline__ void copier_wave(Smem &s, Ctx &c, int32_t *retp, int3
     bool skip = false;
     int32_t result = INT32_MIN;
     int64_t nser = 0;
+    PFIRST(uint64_t wait8 = 0);
     if (lane_id() == 0) __hip_atomic_store(&s.ctl.step, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     for (uint32_t k = 0;; ++k) {
         int32_t done = 0, restart = 0, rip = 0;
@@ -1341,6 +1301,8 @@ __device__ __forceinline__ void copier_wave(Smem &s, Ctx &c, int32_t *retp, int3
             const int buf = (int)((k - 1) & 1u);
             Meta m;
             m.kind = (int32_t)uniform((uint32_t)s.meta[buf].kind);
+            // the wait before this step was for this window: a span's first?
+            PFIRST(if (m.kind & W_PFIRST) pr.acc[20] += wait8; m.kind &= ~W_PFIRST);
             m.wbase = (int32_t)uniform((uint32_t)s.meta[buf].wbase);
             m.cbase = (int32_t)uniform((uint32_t)s.meta[buf].cbase);
             m.T = uniform(s.meta[buf].T);
@@ -1420,6 +1382,7 @@ __device__ __forceinline__ void copier_wave(Smem &s, Ctx &c, int32_t *retp, int3
         wg_sync();
         wg_sync();
         PSTAMP(8);
+        PFIRST(wait8 = pr.last);
         if (done) break;
         skip = restart != 0;
     }
