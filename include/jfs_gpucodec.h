@@ -337,6 +337,49 @@ int64_t jfs_zstd_compress_device(const jfs_dev_block *d_blocks, int nblk, int32_
  * Synchronous with respect to `stream` (it uses per-device scratch).  Does not
  * consult jfs_zstd_parse_mode. */
 int64_t jfs_zstd_compress_fast_device(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, void *stream);
+/* Seekable Zstd encode: jfs_zstd_compress_fast_device's parse, contract and
+ * calling rules (host-synchronous, per-device scratch, -2 with no byte written
+ * when dst_cap < CompressBound(src_len), bytes that depend on the input bytes
+ * alone, never larger than jfs_compress_bound(ZSTD, n)) in a layout that can be
+ * decoded from the middle.  src_len <= 131072 gives the fast call's frame, byte
+ * for byte.  A longer input becomes nb = ceil(src_len / 131072) frames and a
+ * seek table.  Frame k holds bytes [131072 k, min(n, 131072 (k + 1))): header
+ * as for an input of that length (single segment, content size, no checksum,
+ * no dictionary), then one block with its last-block bit set, which carries no
+ * Huffman table over from the frame before and is never an RLE block.  The table is one skippable frame
+ * in the Zstandard seekable format, all fields little-endian:
+ *     u32 0x184D2A5E | u32 8 nb + 9 | nb x (u32 compressed size of the frame,
+ *     u32 decompressed size) | u32 nb | u8 0x00 | u32 0x8F92EAB1
+ * To every Zstd reader -- ZSTD_decompress, jfs_decompress, the reference's
+ * ZStandard.Decompress -- the object is concatenated frames and a frame to
+ * skip.  Does not consult jfs_zstd_parse_mode. */
+int64_t jfs_zstd_compress_seekable_device(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, void *stream);
+/* Range decode: input i is decoded for its output bytes [d_lo[i], d_hi[i])
+ * (device arrays of nblk int32).  The seek table is read on the device and only
+ * the frames the range touches are decoded, each as an independent input of
+ * jfs_zstd_decompress_prefix_device; result codes, stream behaviour (one wait
+ * on the host, for the number of selected frames, in front of that call's own)
+ * and scratch are that call's.  Let lo' = max(lo, 0), hi' = min(hi, dst_cap).
+ *   NULL src, src_len == 0, dst_cap == 0: the full decoder's answers.
+ *   Otherwise hi' <= lo': 0, nothing written.
+ *   A valid table (src_len >= 25; the footer magic; descriptor byte 0x00, so no
+ *     per-frame checksums and no reserved bit; 1 <= nf <= 16384 frames, the most
+ *     the encoder writes, with 8 nf + 17 <= src_len; the skippable magic and
+ *     the size 8 nf + 9 at src_len - (8 nf + 17); compressed sizes all >= 1 that add up to exactly that position;
+ *     decompressed sizes that add up to D < 2^32): D > dst_cap gives -2.  Else
+ *     the frames whose output range [D_k, D_k+1) meets [lo', hi') are decoded,
+ *     each into dst[D_k, D_k+1) with that size as its capacity; ret = min(D,
+ *     hi') when every one of them returns exactly its table size, else -1.
+ *     dst[flo, fhi) -- from the first selected frame's start to the last one's
+ *     end -- equals the full decode's bytes, and nothing outside it is written.
+ *     A fault in a frame that was not selected, or a table entry that lies
+ *     about such a frame, is unseen: a caller that needs the whole object
+ *     validated uses the CRC-32C check or the full decoders.
+ *   Anything else -- every Zstd object written without a table, a table with
+ *     checksums -- is no error: the input is decoded by
+ *     jfs_zstd_decompress_prefix_device with want = hi, same result, same bytes. */
+int64_t jfs_zstd_decompress_range_device(const jfs_dev_block *d_blocks, const int32_t *d_lo, const int32_t *d_hi,
+                                         int nblk, int32_t *d_ret, void *stream);
 
 /* CRC-32C (Castagnoli) of device-resident blocks.
  * d_blocks[i].src / src_len: the data.  d_crc[i] (if d_crc != NULL) receives
@@ -650,6 +693,26 @@ int jfs_set_read_decode_mode(int mode);
  * jfs_set_read_decode_mode_ext is the same call for all three modes. */
 int jfs_set_read_decode_mode_ext(int mode);
 
+/* Seek switch of the same calls, beside the decode mode.  JFS_READ_SEEK_OFF
+ * (default): nothing changes.  JFS_READ_SEEK_ON: in every decode mode each Zstd
+ * source is decoded by jfs_zstd_decompress_range_device for [from, need), need
+ * as above and from = the smallest src_off of the segments that reference the
+ * source (both 0 for a source nothing references), so a read from the middle of
+ * a seekable object pays for the frames it touches and any other object is
+ * prefix-decoded to `need`.  src_n[i] = min(size, need) for a well-formed
+ * source; out_n, the gathered bytes, the checksums and the precedence of
+ * verdicts are those of the switch being off for every read whose sources are
+ * well-formed.  LZ4 and "none" are untouched; the compaction calls do not
+ * consult the switch.  The initial value is read once from JFS_READ_SEEK =
+ * "off" | "on" (case-insensitive; anything else, or unset: off).
+ * jfs_set_read_seek_mode returns the previous value, or -1 for an unknown one
+ * (which changes nothing); it is atomic and applies to calls that start
+ * afterwards. */
+#define JFS_READ_SEEK_OFF 0
+#define JFS_READ_SEEK_ON 1
+int jfs_read_seek_mode(void);
+int jfs_set_read_seek_mode(int mode);
+
 /* ---- Runtime / utilities ------------------------------------------------- */
 
 /* Number of usable gfx950 devices (0 when none; never an error).  Only the
@@ -700,8 +763,15 @@ int jfs_set_lz4_parse_mode(int mode);
  * atomic and applies to calls that start afterwards. */
 #define JFS_ZSTD_PARSE_EXACT 0
 #define JFS_ZSTD_PARSE_FAST 1
+#define JFS_ZSTD_PARSE_SEEKABLE 2 /* JFS_ZSTD_PARSE=seekable */
 int jfs_zstd_parse_mode(void);
 int jfs_set_zstd_parse_mode(int mode);
+/* JFS_ZSTD_PARSE_SEEKABLE makes the same calls write the objects of
+ * jfs_zstd_compress_seekable_device: the fast parse, one frame per 128 KiB
+ * block and a seek table.  jfs_set_zstd_parse_mode knows the two modes it was
+ * introduced with and keeps answering -1 for any other value;
+ * jfs_set_zstd_parse_mode_ext is the same call for all three modes. */
+int jfs_set_zstd_parse_mode_ext(int mode);
 
 /* Per-codec counters (the data behind cachedStore's object_request_data_bytes
  * and block-size metrics, cached_store.go:931-974).  Index algo * 2 + dir,

@@ -49,6 +49,8 @@ EXPORTS = [
     "jfs_read_csum_device",
     "jfs_zstd_decompress_prefix_device", "jfs_set_read_decode_mode_ext",
     "jfs_test_set_split_jump_rounds",
+    "jfs_zstd_compress_seekable_device", "jfs_zstd_decompress_range_device", "jfs_set_zstd_parse_mode_ext",
+    "jfs_read_seek_mode", "jfs_set_read_seek_mode",
 ]
 # the hook include/jfs_gpucodec_lz4_fast_test.h declares (the fast LZ4 encoder's host twin)
 LZ4_FAST_TEST_EXPORTS = ["jfs_test_lz4_fast_host"]
@@ -57,7 +59,8 @@ ZSTD_FAST_TEST_EXPORTS = ["jfs_test_zstd_fast_host_seqs", "jfs_test_zstd_fast_se
 
 MODE_OFF, MODE_AUTO, MODE_FORCE = 0, 1, 2
 LZ4_PARSE_EXACT, LZ4_PARSE_FAST = 0, 1
-ZSTD_PARSE_EXACT, ZSTD_PARSE_FAST = 0, 1
+ZSTD_PARSE_EXACT, ZSTD_PARSE_FAST, ZSTD_PARSE_SEEKABLE = 0, 1, 2
+READ_SEEK_OFF, READ_SEEK_ON = 0, 1
 READ_DECODE_FULL, READ_DECODE_PREFIX, READ_DECODE_PREFIX_ALL = 0, 1, 2
 CIPHER_AES256GCM, CIPHER_CHACHA20POLY1305, CIPHER_SM4GCM = 0, 1, 2
 STATS_N = 6  # index algo * 2 + dir (0 compress, 1 decompress)
@@ -124,7 +127,7 @@ def load() -> ctypes.CDLL:
         f.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(JfsIov), ctypes.POINTER(i64), u32]
         f.restype = i64
     for f in (lib.jfs_lz4_decompress_device, lib.jfs_lz4_compress_device, lib.jfs_zstd_decompress_device,
-              lib.jfs_zstd_compress_device, lib.jfs_zstd_compress_fast_device):
+              lib.jfs_zstd_compress_device, lib.jfs_zstd_compress_fast_device, lib.jfs_zstd_compress_seekable_device):
         f.argtypes = [vp, ctypes.c_int, vp, vp]
         f.restype = i64
     lib.jfs_lz4_decompress_device_small.argtypes = [vp, vp, vp, ctypes.c_int, vp, vp]
@@ -135,6 +138,14 @@ def load() -> ctypes.CDLL:
     lib.jfs_lz4_decompress_prefix_device_small.restype = i64
     lib.jfs_zstd_decompress_prefix_device.argtypes = [vp, vp, ctypes.c_int, vp, vp]
     lib.jfs_zstd_decompress_prefix_device.restype = i64
+    lib.jfs_zstd_decompress_range_device.argtypes = [vp, vp, vp, ctypes.c_int, vp, vp]
+    lib.jfs_zstd_decompress_range_device.restype = i64
+    lib.jfs_read_seek_mode.argtypes = []
+    lib.jfs_read_seek_mode.restype = ctypes.c_int
+    lib.jfs_set_read_seek_mode.argtypes = [ctypes.c_int]
+    lib.jfs_set_read_seek_mode.restype = ctypes.c_int
+    lib.jfs_set_zstd_parse_mode_ext.argtypes = [ctypes.c_int]
+    lib.jfs_set_zstd_parse_mode_ext.restype = ctypes.c_int
     lib.jfs_read_decode_mode.argtypes = []
     lib.jfs_read_decode_mode.restype = ctypes.c_int
     lib.jfs_set_read_decode_mode.argtypes = [ctypes.c_int]

@@ -267,23 +267,33 @@ def lz4_fast_host(src) -> bytes:
     return dst.raw[:n]
 
 
-_ZSTD_PARSE = {"exact": L.ZSTD_PARSE_EXACT, "fast": L.ZSTD_PARSE_FAST}
+_ZSTD_PARSE = {"exact": L.ZSTD_PARSE_EXACT, "fast": L.ZSTD_PARSE_FAST, "seekable": L.ZSTD_PARSE_SEEKABLE}
+
+
+def set_zstd_parse_mode(mode: str) -> str:
+    """Set the Zstd parse of the host-buffer compress calls (process-wide, for
+    calls that start afterwards; jfs_set_zstd_parse_mode_ext) and return the
+    previous mode's name: "exact", "fast", or "seekable" -- the fast parse laid
+    out as one frame per 128 KiB block and a seek table
+    (jfs_zstd_compress_seekable_device's objects)."""
+    if mode not in _ZSTD_PARSE:
+        raise ValueError(f"zstd parse mode {mode!r}: expected 'exact', 'fast' or 'seekable'")
+    prev = L.load().jfs_set_zstd_parse_mode_ext(_ZSTD_PARSE[mode])
+    return next(k for k, v in _ZSTD_PARSE.items() if v == prev)
 
 
 @contextlib.contextmanager
 def zstd_parse_mode(mode: str):
     """Hold the Zstd parse of the host-buffer compress calls at "exact"
-    (ZSTD_compress level 1's bytes) or "fast" (jfs_zstd_compress_fast_device's
-    frames) and put the previous mode back on exit.  The mode is process-wide
-    (jfs_set_zstd_parse_mode)."""
-    if mode not in _ZSTD_PARSE:
-        raise ValueError(f"zstd parse mode {mode!r}: expected 'exact' or 'fast'")
-    lib = L.load()
-    prev = lib.jfs_set_zstd_parse_mode(_ZSTD_PARSE[mode])
+    (ZSTD_compress level 1's bytes), "fast" (jfs_zstd_compress_fast_device's
+    frames) or "seekable" (jfs_zstd_compress_seekable_device's objects) and put
+    the previous mode back on exit.  The mode is process-wide
+    (jfs_set_zstd_parse_mode_ext)."""
+    prev = set_zstd_parse_mode(mode)
     try:
         yield
     finally:
-        lib.jfs_set_zstd_parse_mode(prev)
+        set_zstd_parse_mode(prev)
 
 
 _READ_DECODE = {"full": L.READ_DECODE_FULL, "prefix": L.READ_DECODE_PREFIX, "prefix-all": L.READ_DECODE_PREFIX_ALL}
@@ -304,6 +314,26 @@ def set_read_decode_mode(mode: str) -> str:
         raise ValueError(f"read decode mode {mode!r}: expected 'full', 'prefix' or 'prefix-all'")
     prev = L.load().jfs_set_read_decode_mode_ext(_READ_DECODE[mode])
     return next(k for k, v in _READ_DECODE.items() if v == prev)
+
+
+_READ_SEEK = {"off": L.READ_SEEK_OFF, "on": L.READ_SEEK_ON}
+
+
+def read_seek_mode() -> str:
+    """The seek switch of the read calls (jfs_read_seek_mode): "off", or "on" --
+    every Zstd source is decoded through its seek table for the byte range the
+    reads ask of it (an object without one: prefix-decoded to their end)."""
+    m = L.load().jfs_read_seek_mode()
+    return next(k for k, v in _READ_SEEK.items() if v == m)
+
+
+def set_read_seek_mode(mode: str) -> str:
+    """Set it (process-wide, for calls that start afterwards) and return the
+    previous value's name."""
+    if mode not in _READ_SEEK:
+        raise ValueError(f"read seek mode {mode!r}: expected 'off' or 'on'")
+    prev = L.load().jfs_set_read_seek_mode(_READ_SEEK[mode])
+    return next(k for k, v in _READ_SEEK.items() if v == prev)
 
 
 def zstd_fast_seqs(src, device_ptr: int | None = None):

@@ -314,14 +314,26 @@ std::atomic<int> &read_decode() {
     return m;
 }
 
-// JFS_ZSTD_PARSE (include/jfs_gpucodec.h): exact (default) | fast
+// JFS_READ_SEEK (include/jfs_gpucodec.h): off (default) | on
+std::atomic<int> &read_seek() {
+    static std::atomic<int> m{[] {
+        const char *e = getenv("JFS_READ_SEEK");
+        if (!e) return JFS_READ_SEEK_OFF;
+        std::string v(e);
+        for (auto &ch : v) ch = (char)tolower((unsigned char)ch);
+        return v == "on" ? JFS_READ_SEEK_ON : JFS_READ_SEEK_OFF;
+    }()};
+    return m;
+}
+
+// JFS_ZSTD_PARSE (include/jfs_gpucodec.h): exact (default) | fast | seekable
 std::atomic<int> &zstd_parse() {
     static std::atomic<int> m{[] {
         const char *e = getenv("JFS_ZSTD_PARSE");
         if (!e) return JFS_ZSTD_PARSE_EXACT;
         std::string v(e);
         for (auto &ch : v) ch = (char)tolower((unsigned char)ch);
-        return v == "fast" ? JFS_ZSTD_PARSE_FAST : JFS_ZSTD_PARSE_EXACT;
+        return v == "fast" ? JFS_ZSTD_PARSE_FAST : v == "seekable" ? JFS_ZSTD_PARSE_SEEKABLE : JFS_ZSTD_PARSE_EXACT;
     }()};
     return m;
 }
@@ -1867,7 +1879,7 @@ struct Chain {
 // Lays the call out and sizes slot 0 for it: JFS_OK or JFS_ERR_NO_MEMORY.
 int64_t chain_open(Chain &c, Lane &ln, int algo, int cipher, const std::vector<ChainSrc> &st, int ns,
                    const std::vector<ChainOut> &oo, const int32_t *seg_first, bool encode, bool out_crc, bool src_crc,
-                   bool prefix, int64_t npiece = 0) {
+                   bool prefix, int64_t npiece = 0, bool seek = false) {
     c.algo = algo;
     c.cipher = cipher;
     c.ns = ns;
@@ -1879,8 +1891,8 @@ int64_t chain_open(Chain &c, Lane &ln, int algo, int cipher, const std::vector<C
     c.off = jfs_plan::chain_offsets(st, ns, oo, c.codec, encode);
     int64_t nseg = 0;
     for (const ChainOut &o : oo) nseg += seg_first[o.idx + 1] - seg_first[o.idx];
-    c.L = ChainLayout(c.off.tin, ns, c.n, c.no, nseg, ChainFlags{c.sealed, encode, out_crc, src_crc, prefix, npiece > 0},
-                      npiece);
+    c.L = ChainLayout(c.off.tin, ns, c.n, c.no, nseg,
+                      ChainFlags{c.sealed, encode, out_crc, src_crc, prefix, npiece > 0, seek}, npiece);
     c.sl = &ln.slot[0];
     c.s1 = &ln.slot[1];
     c.ks = ln.s_k;
@@ -1956,7 +1968,8 @@ bool chain_lz4_scratch(const Chain &c, const jfs_dev_block *h_enc, bool fast) {
 
 // Queues open -> decode -> the opens' verdicts merged into the source lengths.
 // d_want (prefix modes: LZ4, and Zstd in JFS_READ_DECODE_PREFIX_ALL; else null): where each decode stops.
-int chain_decode(const Chain &c, const int32_t *d_want, int64_t max_want) {
+// d_from (Zstd with JFS_READ_SEEK on; else null): with d_want the range each source is decoded for.
+int chain_decode(const Chain &c, const int32_t *d_want, int64_t max_want, const int32_t *d_from = nullptr) {
     const jfs_dev_block *h_sdesc = c.host<jfs_dev_block>(c.L.sdesc), *d_sdesc = c.dev<jfs_dev_block>(c.L.sdesc);
     int32_t *d_srcn = c.dev<int32_t>(c.L.srcn), *d_open = c.dev<int32_t>(c.L.open);
     const int ns = c.ns;
@@ -1968,8 +1981,9 @@ int chain_decode(const Chain &c, const int32_t *d_want, int64_t max_want) {
         lk = r == JFS_OK ? 0 : -1;
     } else if (lk == 0 && c.algo == JFS_ALGO_ZSTD && ns > 0) {
         // (with a cipher the frame headers are ciphertext on the host) it plans its own scratch
-        lk = d_want ? jfs_launch_zstd_decode_prefix(d_sdesc, ns, d_srcn, d_want, c.ks)
-                    : jfs_launch_zstd_decode(d_sdesc, ns, d_srcn, nullptr, c.ks);
+        lk = d_from   ? jfs_launch_zstd_decode_range(d_sdesc, d_from, d_want, ns, d_srcn, c.ks)
+             : d_want ? jfs_launch_zstd_decode_prefix(d_sdesc, ns, d_srcn, d_want, c.ks)
+                      : jfs_launch_zstd_decode(d_sdesc, ns, d_srcn, nullptr, c.ks);
     }
     // a failed open left zeros, which may decode (for "none" they are the block): its verdict replaces the length
     if (lk == 0 && c.sealed) lk = jfs_launch_chain_merge(d_open, ns, d_srcn, c.ks);
@@ -2111,6 +2125,10 @@ int64_t compact_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *
 // (clamped to its capacity, staged behind the expected checksums in the same
 // H2D copy) unless every source is needed whole, which takes the full
 // launchers.
+// from (Zstd with JFS_READ_SEEK on, else null; `need` comes with it): per object
+// of the call, the first byte a segment asks of it.  Every source then goes
+// through the range launcher, [from, need) clamped to its capacity, also in a
+// call that needs every source whole.
 // csum (the _csum calls, else null): per read of the call, where its
 // disk-cache checksum goes (null: none).  The piece prefix of the reads that
 // want one is staged with the plan, read_csum_flat_kernel runs behind the
@@ -2120,7 +2138,7 @@ int64_t compact_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *
 int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src, const uint8_t *const *src_keys,
                  const std::vector<ChainSrc> &st, int ns, const std::vector<int> &src_map, const jfs_iov *out,
                  const std::vector<ChainOut> &oo, const int32_t *seg_first, const jfs_compact_seg *seg, int64_t *src_n,
-                 int64_t *out_n, uint32_t *crc_got, const int64_t *need, uint8_t *const *csum) {
+                 int64_t *out_n, uint32_t *crc_got, const int64_t *need, const int64_t *from, uint8_t *const *csum) {
     LaneRun scope(dev, ln, algo * 2 + DECOMPRESS, (uint64_t)st.size());
     const int n = (int)st.size(), no = (int)oo.size();
     bool any_check = false;
@@ -2133,7 +2151,8 @@ int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src
         if (ntiles > INT32_MAX) return JFS_ERR_NO_MEMORY;
     }
     tile_first[no] = (int32_t)ntiles;
-    if (need && (algo == JFS_ALGO_LZ4 || algo == JFS_ALGO_ZSTD)) want = jfs_plan::chain_want(need, st, ns, &max_want);
+    const bool seek = need && from && algo == JFS_ALGO_ZSTD && ns > 0;
+    if (need && (algo == JFS_ALGO_LZ4 || algo == JFS_ALGO_ZSTD)) want = jfs_plan::chain_want(need, st, ns, &max_want, seek);
     const bool prefix = !want.empty();
     std::vector<uint8_t> cs_want(no, 0);
     std::vector<int32_t> piece_first;
@@ -2145,12 +2164,13 @@ int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src
         if (npiece < 0) return JFS_ERR_NO_MEMORY;
     }
     Chain c;
-    const int64_t rc = chain_open(c, ln, algo, cipher, st, ns, oo, seg_first, false, false, any_check, prefix, npiece);
+    const int64_t rc = chain_open(c, ln, algo, cipher, st, ns, oo, seg_first, false, false, any_check, prefix, npiece, seek);
     if (rc != JFS_OK) return rc;
     const ChainLayout &L = c.L;
     memcpy(c.h + L.tf, tile_first.data(), (size_t)(no + 1) * 4);
     if (npiece > 0) memcpy(c.h + L.pf, piece_first.data(), (size_t)(no + 1) * 4);
     if (prefix) memcpy(c.h + L.want, want.data(), (size_t)ns * 4);
+    if (seek) memcpy(c.h + L.from, jfs_plan::chain_lo(from, st, ns).data(), (size_t)ns * 4);
     std::vector<CopyJob> jobs;
     chain_stage_sources(c, src, src_keys, st, jobs);
     for (int k = 0; any_check && k < n; k++) {
@@ -2174,7 +2194,8 @@ int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src
     if (any_check)
         lk = jfs_launch_crc32c_lens(c.dev<jfs_dev_block>(L.scd), n, d_len, c.dev<uint32_t>(L.sseed),
                                     c.dev<uint32_t>(L.scrc), ks);
-    if (lk == 0) lk = chain_decode(c, prefix ? c.dev<int32_t>(L.want) : nullptr, max_want);
+    if (lk == 0)
+        lk = chain_decode(c, prefix ? c.dev<int32_t>(L.want) : nullptr, max_want, seek ? c.dev<int32_t>(L.from) : nullptr);
     if (lk == 0 && any_check)
         lk = jfs_launch_verify_gate(c.dev<uint32_t>(L.scrc), d_len, c.dev<uint32_t>(L.exp), n, ns, d_srcn,
                                     c.dev<uint32_t>(L.got), ks);
@@ -2793,7 +2814,35 @@ int jfs_set_read_decode_mode_ext(int mode) {
     return read_decode().exchange(mode);
 }
 
+int jfs_read_seek_mode(void) { return read_seek().load(std::memory_order_relaxed); }
+
+int jfs_set_read_seek_mode(int mode) {
+    if (mode != JFS_READ_SEEK_OFF && mode != JFS_READ_SEEK_ON) return -1;
+    return read_seek().exchange(mode);
+}
+
 int jfs_zstd_parse_mode(void) { return zstd_parse_now(); }
+
+int jfs_set_zstd_parse_mode_ext(int mode) {
+    if (mode != JFS_ZSTD_PARSE_EXACT && mode != JFS_ZSTD_PARSE_FAST && mode != JFS_ZSTD_PARSE_SEEKABLE) return -1;
+    return zstd_parse().exchange(mode);
+}
+
+int64_t jfs_zstd_compress_seekable_device(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, void *stream) {
+    if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
+    stat_launch(JFS_ALGO_ZSTD, COMPRESS, nblk);
+    return jfs_launch_zstd_encode(d_blocks, nblk, d_ret, (hipStream_t)stream, JFS_ZSTD_PARSE_SEEKABLE) == 0 ? JFS_OK
+                                                                                                            : JFS_ERR_HIP;
+}
+
+int64_t jfs_zstd_decompress_range_device(const jfs_dev_block *d_blocks, const int32_t *d_lo, const int32_t *d_hi,
+                                         int nblk, int32_t *d_ret, void *stream) {
+    if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
+    if (nblk > 0 && (!d_lo || !d_hi)) return JFS_ERR_INVALID;
+    stat_launch(JFS_ALGO_ZSTD, DECOMPRESS, nblk);
+    return jfs_launch_zstd_decode_range(d_blocks, d_lo, d_hi, nblk, d_ret, (hipStream_t)stream) == 0 ? JFS_OK
+                                                                                                     : JFS_ERR_HIP;
+}
 
 int jfs_set_zstd_parse_mode(int mode) {
     if (mode != JFS_ZSTD_PARSE_EXACT && mode != JFS_ZSTD_PARSE_FAST) return -1;
@@ -3082,13 +3131,17 @@ static int64_t read_call(int algo, int cipher, int nsrc, const jfs_iov *src, con
         if (csum && csum[j] && out_n[j] == 0 && total[j] == 0) memset(csum[j], 0, 4);
     }
     // prefix modes (LZ4 in both, Zstd in prefix-all): the last byte the plan asks of every object
-    std::vector<int64_t> need;
+    std::vector<int64_t> need, from;
     const int dmode = read_decode().load(std::memory_order_relaxed);
-    if ((algo == JFS_ALGO_LZ4 && dmode != JFS_READ_DECODE_FULL) || (algo == JFS_ALGO_ZSTD && dmode == JFS_READ_DECODE_PREFIX_ALL))
+    // JFS_READ_SEEK: every Zstd source is decoded for [from, need), whatever the decode mode
+    const bool seek = algo == JFS_ALGO_ZSTD && read_seek().load(std::memory_order_relaxed) == JFS_READ_SEEK_ON;
+    if ((algo == JFS_ALGO_LZ4 && dmode != JFS_READ_DECODE_FULL) || (algo == JFS_ALGO_ZSTD && dmode == JFS_READ_DECODE_PREFIX_ALL) ||
+        seek)
         need = jfs_plan::chain_need(nsrc, nout, seg_first, seg);
+    if (seek) from = jfs_plan::chain_from(nsrc, nout, seg_first, seg);
     chain_dispatch(ds, algo, DECOMPRESS, st, oo, src_n, out_n, [&](DevCtx *dev, Lane &ln) {
         return read_run(dev, ln, algo, cipher, src, src_keys, st, ns, src_map, out, oo, seg_first, seg, src_n, out_n,
-                        crc_got, need.empty() ? nullptr : need.data(), csum);
+                        crc_got, need.empty() ? nullptr : need.data(), from.empty() ? nullptr : from.data(), csum);
     });
     chain_stat(algo, DECOMPRESS, nsrc, [&](int i) { return src[i].src_len; }, src_n, ns > 0, steady_ns() - t0);
     return JFS_OK;

@@ -109,10 +109,26 @@ inline std::vector<int64_t> chain_need(int nsrc, int nout, const int32_t *seg_fi
     return need;
 }
 
+// per object of the call, the first byte a segment asks of it (0: unused, as
+// chain_need): the lower end of the range a seekable source is decoded for
+inline std::vector<int64_t> chain_from(int nsrc, int nout, const int32_t *seg_first, const jfs_compact_seg *seg) {
+    std::vector<int64_t> from(nsrc > 0 ? nsrc : 0, -1);
+    for (int j = 0; j < nout; j++)
+        for (int k = seg_first[j]; k < seg_first[j + 1]; k++) {
+            if (seg[k].src < 0) continue;
+            int64_t &f = from[seg[k].src];
+            f = f < 0 ? (int64_t)seg[k].src_off : std::min(f, (int64_t)seg[k].src_off);
+        }
+    for (int64_t &f : from) f = std::max<int64_t>(f, 0);
+    return from;
+}
+
 // Prefix mode: want[k] = where the decode of source k stops, `need` clamped to
 // its capacity.  Empty when every source is needed whole, which takes the full
-// launchers.  *max_want = the largest entry.
-inline std::vector<int32_t> chain_want(const int64_t *need, const std::vector<ChainSrc> &st, int ns, int64_t *max_want) {
+// launchers -- unless keep_whole (the range launcher takes every call).
+// *max_want = the largest entry.
+inline std::vector<int32_t> chain_want(const int64_t *need, const std::vector<ChainSrc> &st, int ns, int64_t *max_want,
+                                       bool keep_whole = false) {
     std::vector<int32_t> want(ns);
     bool whole = true;
     *max_want = 0;
@@ -121,8 +137,15 @@ inline std::vector<int32_t> chain_want(const int64_t *need, const std::vector<Ch
         *max_want = std::max<int64_t>(*max_want, want[k]);
         whole = whole && want[k] >= st[k].cap;
     }
-    if (whole) want.clear();
+    if (whole && !keep_whole) want.clear();
     return want;
+}
+
+// Seek mode: lo[k] = where the range of source k starts, `from` clamped as want is
+inline std::vector<int32_t> chain_lo(const int64_t *from, const std::vector<ChainSrc> &st, int ns) {
+    std::vector<int32_t> lo(ns);
+    for (int k = 0; k < ns; k++) lo[k] = (int32_t)std::min<int64_t>(from[st[k].idx], st[k].cap);
+    return lo;
 }
 
 // ---------------------------------------------------------------------------
@@ -195,6 +218,7 @@ struct ChainFlags {
     bool src_crc;  // expected CRC-32C of stored objects
     bool prefix;   // per-source decode limits
     bool read_csum = false;  // disk-cache checksums of the reads (last: the initialisers above leave it off)
+    bool seek = false;       // per-source lower ends of the decoded ranges (JFS_READ_SEEK)
 };
 
 // The staged area, mirrored pinned / HBM: [stored bytes | meta | results |
@@ -217,6 +241,7 @@ struct ChainLayout {
     int64_t scd, sseed, len, exp;  // stored objects' checksums: descriptors, seeds, lengths (-1: none), expected
     int64_t want;                  // prefix mode's decode limits
     int64_t pf;                    // piece prefix of the reads' checksums, no + 1
+    int64_t from;                  // seek mode's lower ends, beside want
     int64_t srcn;                  // source lengths, ns + 1, preset
     // results, which only the device writes:
     int64_t open;        // the opens'
@@ -253,6 +278,7 @@ struct ChainLayout {
         exp = take(f.src_crc, n, 4);
         want = take(f.prefix, ns, 4);
         pf = take(f.read_csum, no + 1, 4);
+        from = take(f.seek, ns, 4);
         results = srcn = take(true, ns + 1, 4);
         h2d = o;
         open = take(f.sealed, ns, 4);

@@ -36,7 +36,8 @@ int jfs_launch_lz4_encode_seg(const jfs_dev_block *d_blocks, int nblk, const int
 int64_t jfs_lz4_fast_scratch_bytes(int nblk, const int32_t *lens);
 int jfs_launch_lz4_fast(const jfs_dev_block *d_blocks, int nblk, const int32_t *lens, int32_t *d_ret, void *scratch,
                         int64_t scratch_cap, hipStream_t stream);
-// parse_mode: JFS_ZSTD_PARSE_EXACT (libzstd's bytes) or JFS_ZSTD_PARSE_FAST (zstd_fast.hip: valid frames, not libzstd's bytes)
+// parse_mode: JFS_ZSTD_PARSE_EXACT (libzstd's bytes), JFS_ZSTD_PARSE_FAST (zstd_fast.hip: valid frames, not libzstd's
+// bytes) or JFS_ZSTD_PARSE_SEEKABLE (the fast parse, one frame per 128 KiB block and a seek table)
 int jfs_launch_zstd_encode(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, hipStream_t stream,
                            int parse_mode);
 int jfs_launch_zstd_decode(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, uint8_t *d_scratch,
@@ -55,6 +56,12 @@ void jfs_zstd_plan_host(const uint8_t *const *srcs, const int32_t *lens, const i
 // dst_cap: dst_cap); jfs_launch_zstd_decode's scratch and stream behaviour
 int jfs_launch_zstd_decode_prefix(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, const int32_t *d_want,
                                   hipStream_t stream);
+// range decode (zstd_seek.hip): input b is decoded for its output bytes
+// [d_lo[b], d_hi[b]) through its seek table, frame by frame, or as a prefix
+// decode with want = d_hi[b] when it has none; waits once on the host for the
+// number of selected frames, then jfs_launch_zstd_decode_prefix's behaviour
+int jfs_launch_zstd_decode_range(const jfs_dev_block *d_blocks, const int32_t *d_lo, const int32_t *d_hi, int nblk,
+                                 int32_t *d_ret, hipStream_t stream);
 // jfs_zstd_plan_host of such a decode; totals[5] is the largest clamped want
 void jfs_zstd_plan_host_prefix(const uint8_t *const *srcs, const int32_t *lens, const int32_t *caps,
                                const int32_t *wants, int nblk, void *info_out, uint64_t *totals);

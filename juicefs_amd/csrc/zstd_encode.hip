@@ -81,6 +81,7 @@
 #include "jfs_internal.h"
 #include "wave.cuh"
 #include "zstd_l1.h"
+#include "zstd_seek.h"
 
 namespace jfs {
 namespace zl1 {
@@ -1942,6 +1943,45 @@ struct LitDecSmem {
     uint32_t tot[256];
 };
 
+// one lane's little-endian dword at dst[o ...)
+__device__ __forceinline__ void put_le32(g_u8 *dst, int64_t o, uint32_t v) {
+    for (int i = 0; i < 4; i++) dst[o + i] = (uint8_t)(v >> (8 * i));
+}
+
+// The frame header of an n-byte input with window log wlog at dst[at ...)
+// (ZSTD_writeFrameHeader: no checksum, no dictionary, FCS); returns its bytes.
+__device__ __forceinline__ int64_t put_frame_header(g_u8 *dst, int64_t at, uint32_t n, uint32_t wlog) {
+    const bool single1 = (1u << wlog) >= n;
+    const uint32_t fcs = (n >= 256) + (n >= 65536 + 256);
+    uint64_t hv = 0xFD2FB528ull | ((uint64_t)((single1 ? 0x20 : 0) | (fcs << 6)) << 32);
+    int hn = 5;
+    if (!single1) {
+        hv |= (uint64_t)((wlog - 10) << 3) << 40;
+        hn = 6;
+    }
+    put_bytes(dst, at, hv, hn);
+    int64_t op = at + hn;
+    if (fcs == 0) {
+        if (single1) {
+            put_bytes(dst, op, n, 1);
+            op += 1;
+        }
+    } else if (fcs == 1) {
+        put_bytes(dst, op, n - 256, 2);
+        op += 2;
+    } else {
+        put_bytes(dst, op, n, 4);
+        op += 4;
+    }
+    return op - at;
+}
+
+// SEEK (JFS_ZSTD_PARSE_SEEKABLE): an input of more than one block
+// becomes one frame per block -- a header of its own in front of every block,
+// no Huffman table carried from the block before -- and a seek table behind the
+// last (zstd_seek.h).  An input of one block at most is laid out as without
+// SEEK, byte for byte.
+template <bool SEEK>
 __global__ __launch_bounds__(64) void zl1_litdec_kernel(FInfo *__restrict__ fi, const int32_t *__restrict__ flist,
                                                         BInfo *__restrict__ bi, const uint32_t *__restrict__ hist,
                                                         LitTab *__restrict__ lt, int32_t *__restrict__ ret) {
@@ -1956,8 +1996,9 @@ __global__ __launch_bounds__(64) void zl1_litdec_kernel(FInfo *__restrict__ fi, 
     const uint32_t n = (uint32_t)F.n;
     const bool single1 = (1u << F.wlog) >= n;
     const uint32_t fcs = (n >= 256) + (n >= 65536 + 256);
+    const bool seek = SEEK && F.nb > 1;  // (the frames' headers come with their blocks)
     int64_t op = 0;
-    {
+    if (!seek) {
         uint64_t hv = 0xFD2FB528ull | ((uint64_t)((single1 ? 0x20 : 0) | (fcs << 6)) << 32);
         int hn = 5;
         if (!single1) {
@@ -1993,6 +2034,12 @@ __global__ __launch_bounds__(64) void zl1_litdec_kernel(FInfo *__restrict__ fi, 
         LitTab &T = lt[g];
         const int32_t bs = B.bs, be = B.be, bsz = be - bs, flags = B.flags;
         const bool last = k == F.nb - 1;
+        if (SEEK && seek) {
+            // frame k: its own header, and no table from the frame before
+            op += put_frame_header(dst, op, (uint32_t)bsz, params_of(bsz).wlog);
+            prep = 0;
+            ptab = -1;
+        }
         int64_t cS = 0;
         int lkind = 0;  // literal section: 0 raw, 1 RLE, 2 Huffman new table, 3 Huffman previous table
         int64_t litsz = 0, clit = 0;
@@ -2093,7 +2140,9 @@ __global__ __launch_bounds__(64) void zl1_litdec_kernel(FInfo *__restrict__ fi, 
                 const int64_t c = litsz + secsz;
                 cS = c >= (int64_t)bsz - ((bsz >> 6) + 2) ? 0 : c;
             }
-            if (k > 0 && cS < 25 && (flags & F_RLE)) cS = 1;
+            // (a frame of the seekable layout never starts with an RLE block, as no libzstd frame
+            // does: old zstd releases refuse one; the block stays the compressed block it is above)
+            if (k > 0 && cS < 25 && (flags & F_RLE) && !(SEEK && seek)) cS = 1;
         }
         const bool confirmed = cS > 1;
         const bool assumed = (flags & F_ASSUMED) != 0;
@@ -2126,6 +2175,29 @@ __global__ __launch_bounds__(64) void zl1_litdec_kernel(FInfo *__restrict__ fi, 
         }
         __syncthreads();
     }
+    if (SEEK && seek) {
+        // The seek table, one entry per lane: frame k starts its header bytes in
+        // front of its block header (T.op, written above: the barrier that ends
+        // every round of the loop orders it) and ends where frame k + 1 starts.
+        namespace zs = jfs::zseek;
+        const int64_t tp = op;
+        auto fstart = [&](int32_t k) -> int64_t {
+            if (k >= F.nb) return tp;
+            const BInfo &Bk = bi[F.b0 + k];
+            const uint32_t m = (uint32_t)(Bk.be - Bk.bs);
+            return lt[F.b0 + k].op - (5 + (m < 256 ? 1 : m < 65536 + 256 ? 2 : 4));
+        };
+        for (int32_t k = l; k < F.nb; k += 64) {
+            const BInfo &Bk = bi[F.b0 + k];
+            put_le32(dst, tp + 8 + zs::ENTRY * (int64_t)k, (uint32_t)(fstart(k + 1) - fstart(k)));
+            put_le32(dst, tp + 12 + zs::ENTRY * (int64_t)k, (uint32_t)(Bk.be - Bk.bs));
+        }
+        const int64_t ft = tp + 8 + zs::ENTRY * (int64_t)F.nb;
+        put_bytes(dst, tp, (uint64_t)zs::SKIP_MAGIC | ((uint64_t)(uint32_t)(zs::ENTRY * F.nb + 9) << 32), 8);
+        put_bytes(dst, ft, (uint64_t)(uint32_t)F.nb, 5);  // the frame count; descriptor 0: no per-frame checksums
+        put_bytes(dst, ft + 5, (uint64_t)zs::SEEK_MAGIC, 4);
+        op = tp + zs::table_bytes(F.nb);
+    }
     if (l == 0) {
         ret[fidx] = op <= F.cap ? (int32_t)op : -2;
         FR.status = 0;
@@ -2138,6 +2210,8 @@ struct LitWSmem {
     uint32_t ring[256];  // Huffman stream staging (8,192 bits)
 };
 
+// SEEK: every block ends its frame (zl1_litdec_kernel<true>)
+template <bool SEEK>
 __global__ __launch_bounds__(64) void zl1_litwrite_kernel(const FInfo *__restrict__ fi, const int32_t *__restrict__ blist,
                                                           const BInfo *__restrict__ bi, const uint8_t *__restrict__ bytes,
                                                           const LitTab *__restrict__ lt) {
@@ -2155,7 +2229,7 @@ __global__ __launch_bounds__(64) void zl1_litwrite_kernel(const FInfo *__restric
     g_u8 *dst = (g_u8 *)F.dst;
     const Src S = make_src(F.src, F.n);
     const int32_t bs = B.bs, bsz = B.be - B.bs;
-    const bool last = g - F.b0 == F.nb - 1;
+    const bool last = SEEK || g - F.b0 == F.nb - 1;
     const uint8_t *lit8 = bytes + B.lit_off;
     const gc_u8 *lit = (const gc_u8 *)lit8;
     if (cS == 0) {
@@ -2295,12 +2369,16 @@ int spec_max_blocks() {
 
 // parse_mode: JFS_ZSTD_PARSE_EXACT, libzstd's level-1 bytes (everything below);
 // JFS_ZSTD_PARSE_FAST, the chunk-parallel parse of zstd_fast.hip in
-// front of the same entropy stage: one pass, no speculative rounds, no parse-again loop
+// front of the same entropy stage: one pass, no speculative rounds, no parse-again loop;
+// JFS_ZSTD_PARSE_SEEKABLE, the fast parse again, every 128 KiB block a frame of
+// its own and a seek table behind them (zl1_litdec_kernel<true>)
 extern "C" int jfs_launch_zstd_encode(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, hipStream_t stream,
                                       int parse_mode) {
     if (nblk <= 0) return 0;
-    if (parse_mode != JFS_ZSTD_PARSE_EXACT && parse_mode != JFS_ZSTD_PARSE_FAST) return -1;
-    const bool fast = parse_mode == JFS_ZSTD_PARSE_FAST;
+    if (parse_mode != JFS_ZSTD_PARSE_EXACT && parse_mode != JFS_ZSTD_PARSE_FAST && parse_mode != JFS_ZSTD_PARSE_SEEKABLE)
+        return -1;
+    const bool seekable = parse_mode == JFS_ZSTD_PARSE_SEEKABLE;
+    const bool fast = parse_mode == JFS_ZSTD_PARSE_FAST || seekable;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -1;
     // a free scratch of this device (blocking on the first only if both are taken)
@@ -2484,11 +2562,19 @@ extern "C" int jfs_launch_zstd_encode(const jfs_dev_block *d_blocks, int nblk, i
             hipLaunchKernelGGL(zl1_lithuf_kernel, dim3((unsigned)nbl), dim3(64), 0, stream, d_fi, d_bl, d_bi, d_hist,
                                d_lt);
         }
-        hipLaunchKernelGGL(zl1_litdec_kernel, dim3((unsigned)nfl), dim3(64), 0, stream, d_fi, d_list, d_bi, d_hist, d_lt,
-                           d_ret);
-        if (nbl > 0)
-            hipLaunchKernelGGL(zl1_litwrite_kernel, dim3((unsigned)nbl), dim3(64), 0, stream, d_fi, d_bl, d_bi, d_bytes,
-                               d_lt);
+        if (seekable) {
+            hipLaunchKernelGGL(zl1_litdec_kernel<true>, dim3((unsigned)nfl), dim3(64), 0, stream, d_fi, d_list, d_bi,
+                               d_hist, d_lt, d_ret);
+            if (nbl > 0)
+                hipLaunchKernelGGL(zl1_litwrite_kernel<true>, dim3((unsigned)nbl), dim3(64), 0, stream, d_fi, d_bl, d_bi,
+                                   d_bytes, d_lt);
+        } else {
+            hipLaunchKernelGGL(zl1_litdec_kernel<false>, dim3((unsigned)nfl), dim3(64), 0, stream, d_fi, d_list, d_bi,
+                               d_hist, d_lt, d_ret);
+            if (nbl > 0)
+                hipLaunchKernelGGL(zl1_litwrite_kernel<false>, dim3((unsigned)nbl), dim3(64), 0, stream, d_fi, d_bl, d_bi,
+                                   d_bytes, d_lt);
+        }
         if (hipGetLastError() != hipSuccess) return -1;
         return hipStreamSynchronize(stream) == hipSuccess ? 0 : -1;
     }
@@ -2595,10 +2681,10 @@ extern "C" int jfs_launch_zstd_encode(const jfs_dev_block *d_blocks, int nblk, i
         if (!blist.empty())
             hipLaunchKernelGGL(zl1_lithuf_kernel, dim3((unsigned)blist.size()), dim3(64), 0, stream, d_fi,
                                d_list + blist_off, d_bi, d_hist, d_lt);
-        hipLaunchKernelGGL(zl1_litdec_kernel, dim3((unsigned)todo.size()), dim3(64), 0, stream, d_fi, d_list + flist_off,
+        hipLaunchKernelGGL(zl1_litdec_kernel<false>, dim3((unsigned)todo.size()), dim3(64), 0, stream, d_fi, d_list + flist_off,
                            d_bi, d_hist, d_lt, d_ret);
         if (!blist.empty())
-            hipLaunchKernelGGL(zl1_litwrite_kernel, dim3((unsigned)blist.size()), dim3(64), 0, stream, d_fi,
+            hipLaunchKernelGGL(zl1_litwrite_kernel<false>, dim3((unsigned)blist.size()), dim3(64), 0, stream, d_fi,
                                d_list + blist_off, d_bi, d_bytes, d_lt);
         if (hipGetLastError() != hipSuccess) return -1;
         // frames whose confirmation guess was wrong go again

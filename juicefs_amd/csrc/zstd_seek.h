@@ -1,0 +1,137 @@
+// The seek table of a seekable Zstd object (the Zstandard seekable
+// format): one skippable frame behind the object's frames,
+//     u32 0x184D2A5E | u32 8 nf + 9 | nf x (u32 compressed, u32 decompressed)
+//     | u32 nf | u8 descriptor | u32 0x8F92EAB1
+// all little-endian.  The parser takes the byte fetch as a parameter
+// (lz4_walkstep.h is the model), so the range decoder's scan kernel
+// (zstd_seek.hip) and tests/zstd_seek_main.cc run the same checks.  It never
+// fetches outside [0, src_len), and anything that is not a valid table --
+// a table whose entries carry checksums included -- is "no table", never an
+// error: such an object is decoded as any other Zstd object.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define JFS_ZSEEK_HD __host__ __device__ __forceinline__
+#else
+#define JFS_ZSEEK_HD inline
+#endif
+
+namespace jfs {
+namespace zseek {
+
+constexpr uint32_t SKIP_MAGIC = 0x184D2A5Eu;
+constexpr uint32_t SEEK_MAGIC = 0x8F92EAB1u;
+constexpr int32_t FRAME_BYTES = 128 << 10;  // content of one frame of the seekable encoder
+constexpr int32_t TABLE_FIXED = 17;         // skippable header 8 + footer 9
+constexpr int32_t ENTRY = 8;
+// The most frames a table may list: what the encoder writes for its largest
+// input (0x7FFFFF00 bytes).  The table comes from stored data, and the range
+// decoder's work per object grows with the square of the selected frames
+// (zseek_expand walks on from the first one), so a table of hundreds of
+// thousands of one-byte frames is "no table" and the object is decoded as any
+// other: the walk is 16,384 entries at most.
+constexpr int32_t MAX_FRAMES = 16384;
+
+// bytes of the table of an object of nf frames
+JFS_ZSEEK_HD int64_t table_bytes(int64_t nf) { return ENTRY * nf + TABLE_FIXED; }
+
+template <class F>
+JFS_ZSEEK_HD uint32_t le32(F fetch, int32_t p) {
+    return (uint32_t)fetch(p) | ((uint32_t)fetch(p + 1) << 8) | ((uint32_t)fetch(p + 2) << 16) |
+           ((uint32_t)fetch(p + 3) << 24);
+}
+
+// The footer and the skippable header: the frame count and where the table
+// starts (= the bytes its frames must take), or false.  What the entries must
+// add up to is seek_sums_ok's.
+template <class F>
+JFS_ZSEEK_HD bool seek_footer(F fetch, int32_t src_len, int32_t *nf, int32_t *tpos) {
+    if (src_len < TABLE_FIXED + ENTRY) return false;
+    if (le32(fetch, src_len - 4) != SEEK_MAGIC) return false;
+    if (fetch(src_len - 5) != 0u) return false;  // checksum bit, reserved bits: not ours
+    const uint32_t n = le32(fetch, src_len - 9);
+    if (n < 1u || n > (uint32_t)MAX_FRAMES || (int64_t)n > ((int64_t)src_len - TABLE_FIXED) / ENTRY) return false;
+    const int32_t t = src_len - (int32_t)table_bytes(n);
+    if (le32(fetch, t) != SKIP_MAGIC) return false;
+    if (le32(fetch, t + 4) != (uint32_t)(ENTRY * n + 9u)) return false;
+    *nf = (int32_t)n;
+    *tpos = t;
+    return true;
+}
+
+// entry k of the table at tpos
+template <class F>
+JFS_ZSEEK_HD void seek_entry(F fetch, int32_t tpos, int32_t k, uint32_t *c, uint32_t *d) {
+    *c = le32(fetch, tpos + 8 + ENTRY * k);
+    *d = le32(fetch, tpos + 12 + ENTRY * k);
+}
+
+// the entries' totals: every frame has bytes (zeros = the number of entries
+// with none), the frames end where the table starts, the content fits 32 bits
+JFS_ZSEEK_HD bool seek_sums_ok(uint64_t csum, uint64_t dsum, uint32_t zeros, int32_t tpos) {
+    return zeros == 0u && csum == (uint64_t)(uint32_t)tpos && dsum <= 0xFFFFFFFFull;
+}
+
+// the range asked of an object: lo' = max(lo, 0), hi' = min(hi, dst_cap)
+JFS_ZSEEK_HD int32_t range_lo(int32_t lo) { return lo > 0 ? lo : 0; }
+JFS_ZSEEK_HD int32_t range_hi(int32_t hi, int32_t dst_cap) { return hi < dst_cap ? hi : dst_cap; }
+
+// Frame k, whose content is [d0, d0 + d) of the object: it comes before the
+// range, meets it, or comes behind it.  A frame without content meets nothing.
+JFS_ZSEEK_HD bool frame_before(uint64_t d0, uint32_t d, int32_t lo) { return d0 + d <= (uint64_t)(uint32_t)lo; }
+JFS_ZSEEK_HD bool frame_from(uint64_t d0, int32_t hi) { return d0 >= (uint64_t)(uint32_t)hi; }
+
+struct Sel {
+    int32_t table;    // 1: a valid table
+    int32_t nf;       // its frames
+    uint32_t total;   // D, the content of all frames
+    int32_t first;    // first selected frame
+    int32_t count;    // selected frames (they are consecutive); 0: the range meets none
+    uint32_t coff;    // compressed offset of frame `first`
+    uint32_t doff;    // content offset of frame `first`
+};
+
+// The whole answer for one object, serially.  lo < hi after the clamps is the
+// caller's to check; an empty range selects nothing.  With D > dst_cap the
+// selection is computed all the same: the caller answers -2 first.
+template <class F>
+JFS_ZSEEK_HD Sel seek_select(F fetch, int32_t src_len, int32_t dst_cap, int32_t lo, int32_t hi) {
+    Sel s;
+    s.table = 0; s.nf = 0; s.total = 0; s.first = 0; s.count = 0; s.coff = 0; s.doff = 0;
+    int32_t nf = 0, tpos = 0;
+    if (!seek_footer(fetch, src_len, &nf, &tpos)) return s;
+    const int32_t l = range_lo(lo), h = range_hi(hi, dst_cap);
+    uint64_t cs = 0, ds = 0;
+    uint32_t zeros = 0;
+    int32_t before = 0, count = 0;
+    uint64_t coff = 0, doff = 0;
+    for (int32_t k = 0; k < nf; k++) {
+        uint32_t c, d;
+        seek_entry(fetch, tpos, k, &c, &d);
+        zeros += c == 0u;
+        if (frame_before(ds, d, l)) {
+            before = k + 1;
+            coff = cs + c;
+            doff = ds + d;
+        } else if (!frame_from(ds, h)) {
+            count = k + 1 - before;
+        }
+        cs += c;
+        ds += d;
+    }
+    if (!seek_sums_ok(cs, ds, zeros, tpos)) return s;
+    s.table = 1;
+    s.nf = nf;
+    s.total = (uint32_t)ds;
+    if (h > l && count > 0) {
+        s.first = before;
+        s.count = count;
+        s.coff = (uint32_t)coff;
+        s.doff = (uint32_t)doff;
+    }
+    return s;
+}
+
+}  // namespace zseek
+}  // namespace jfs

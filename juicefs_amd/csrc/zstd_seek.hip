@@ -1,0 +1,278 @@
+// Range decode of seekable Zstd objects (the contract is
+// jfs_zstd_decompress_range_device's in the header).  The seek table
+// (zstd_seek.h) is read on the device: zseek_scan finds, per input, the frames
+// a byte range touches; zseek_offsets gives every input its slice of one
+// expanded list; zseek_expand writes that list, one independent decoder input
+// per selected frame; the prefix launcher of zstd_decode_prefix.hip decodes it
+// as it decodes any batch; zseek_fold turns the frames' results into the
+// inputs'.  An input without a valid table is one entry of the list, itself.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <mutex>
+
+#include "jfs_internal.h"
+#include "wave.cuh"
+#include "zstd_seek.h"
+
+namespace jfs {
+namespace zseek {
+
+enum : int32_t {
+    M_PASS = 0,   // no table (or an early answer of the decoder's): the input itself, want = hi
+    M_TABLE = 1,  // the selected frames
+    M_EMPTY = 2,  // hi' <= lo': 0
+    M_BIG = 3,    // a table whose content exceeds dst_cap: -2
+};
+
+// per input, zseek_scan's answer
+struct In {
+    int32_t mode;
+    int32_t answer;  // M_TABLE: min(D, hi')
+    int32_t nf;
+    int32_t first, count;  // selected frames
+    uint32_t coff, doff;   // where frame `first` starts: compressed, content
+    int32_t slot0;         // zseek_offsets: the input's first entry of the expanded list
+};
+
+__device__ __forceinline__ int32_t slots_of(const In &z) { return z.mode == M_TABLE && z.count > 0 ? z.count : 1; }
+
+struct Fetch {
+    const gc_u8 *s;
+    __device__ __forceinline__ uint32_t operator()(int32_t p) const { return s[p]; }
+};
+
+__device__ __forceinline__ uint64_t shfl_up64(uint64_t v, int o) {
+    const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, o, 64), hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), o, 64);
+    return (uint64_t)hi << 32 | lo;
+}
+__device__ __forceinline__ uint64_t shfl64(uint64_t v, int l) {
+    return (uint64_t)lane_read((uint32_t)(v >> 32), l) << 32 | lane_read((uint32_t)v, l);
+}
+__device__ __forceinline__ uint64_t wave_scan_incl64(uint64_t v) {
+    const int l = lane_id();
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint64_t y = shfl_up64(v, o);
+        if (l >= o) v += y;
+    }
+    return v;
+}
+
+// One wave per input: 64 table entries a round, the two running sums by a wave
+// scan.  The frames in front of the range are a prefix of the table and those
+// behind it a suffix, so a round's ballots place the selection.
+__global__ __launch_bounds__(64) void zseek_scan(const jfs_dev_block *__restrict__ blocks, const int32_t *__restrict__ lo,
+                                                 const int32_t *__restrict__ hi, int nblk, In *__restrict__ out) {
+    const int i = blockIdx.x, lane = lane_id();
+    if (i >= nblk) return;
+    const jfs_dev_block b = blocks[i];
+    In z;
+    z.mode = M_PASS; z.answer = 0; z.nf = 0; z.first = 0; z.count = 0; z.coff = 0; z.doff = 0; z.slot0 = 0;
+    const int32_t l = range_lo(lo[i]), h = range_hi(hi[i], b.dst_cap);
+    const Fetch f{(const gc_u8 *)b.src};
+    int32_t nf = 0, tpos = 0;
+    if (b.src == nullptr || b.src_len <= 0 || b.dst_cap <= 0) {
+        // the decoder's own early answers
+    } else if (h <= l) {
+        z.mode = M_EMPTY;
+    } else if (seek_footer(f, b.src_len, &nf, &tpos)) {
+        uint64_t cs = 0, ds = 0;  // the sums in front of this round
+        int32_t before = 0, end = 0;
+        uint64_t coff = 0, doff = 0;
+        bool zero = false;
+        for (int32_t k0 = 0; k0 < nf; k0 += 64) {
+            const int32_t k = k0 + lane;
+            const bool has = k < nf;
+            uint32_t c = 0, d = 0;
+            if (has) seek_entry(f, tpos, k, &c, &d);
+            const uint64_t ic = wave_scan_incl64(c), id = wave_scan_incl64(d);
+            const uint64_t d0 = ds + id - d;
+            const bool bef = has && frame_before(d0, d, l);
+            const bool sel = has && !bef && !frame_from(d0, h);
+            zero = zero || __ballot(has && c == 0u) != 0ull;
+            const int nbef = __popcll(__ballot(bef));
+            if (nbef > 0) {
+                before = k0 + nbef;
+                coff = cs + shfl64(ic, nbef - 1);
+                doff = ds + shfl64(id, nbef - 1);
+            }
+            const uint64_t m = __ballot(sel);
+            if (m) end = k0 + 64 - __builtin_clzll(m);
+            cs += shfl64(ic, 63);
+            ds += shfl64(id, 63);
+        }
+        if (seek_sums_ok(cs, ds, zero ? 1u : 0u, tpos)) {
+            if (ds > (uint64_t)(uint32_t)b.dst_cap) {
+                z.mode = M_BIG;
+            } else {
+                z.mode = M_TABLE;
+                z.nf = nf;
+                z.answer = (int32_t)(ds < (uint64_t)(uint32_t)h ? ds : (uint64_t)(uint32_t)h);
+                if (end > before) {
+                    z.first = before;
+                    z.count = end - before;
+                    z.coff = (uint32_t)coff;
+                    z.doff = (uint32_t)doff;
+                }
+            }
+        }
+    }
+    if (lane == 0) out[i] = z;
+}
+
+// slot0 of every input and the length of the expanded list (one wave)
+__global__ __launch_bounds__(64) void zseek_offsets(In *__restrict__ in, int nblk, uint64_t *__restrict__ total) {
+    const int lane = lane_id();
+    uint64_t base = 0;
+    for (int i0 = 0; i0 < nblk; i0 += 64) {
+        const int i = i0 + lane;
+        const uint32_t n = i < nblk ? (uint32_t)slots_of(in[i]) : 0u;
+        uint32_t sum = 0;
+        const uint32_t ex = wave_scan_excl(n, &sum);
+        // (an input takes MAX_FRAMES slots at most, so a round's 32-bit sum cannot wrap; a list
+        // beyond int32 is refused on the host: the value only has to stay in range)
+        if (i < nblk) in[i].slot0 = (int32_t)(base + ex < 0x7FFFFFFFull ? base + ex : 0x7FFFFFFFull);
+        base += sum;
+    }
+    if (lane == 0) *total = base;
+}
+
+// One thread per entry of the expanded list: its input by binary search over
+// slot0, its frame by walking the table on from the first selected one.
+__global__ __launch_bounds__(64) void zseek_expand(const jfs_dev_block *__restrict__ blocks, const int32_t *__restrict__ hi,
+                                                   int nblk, const In *__restrict__ in, int32_t total,
+                                                   jfs_dev_block *__restrict__ xdesc, int32_t *__restrict__ xwant) {
+    const int32_t e = (int32_t)(blockIdx.x * 64u + threadIdx.x);
+    if (e >= total) return;
+    int a = 0, z = nblk - 1;  // the last input with slot0 <= e
+    while (a < z) {
+        const int m = (a + z + 1) >> 1;
+        if (in[m].slot0 <= e) a = m;
+        else z = m - 1;
+    }
+    const In s = in[a];
+    const jfs_dev_block b = blocks[a];
+    jfs_dev_block x{b.src, b.dst, 0, 0};  // nothing to decode: an empty input
+    int32_t want = 0;
+    if (s.mode == M_PASS) {
+        x = b;
+        want = hi[a];
+    } else if (s.mode == M_TABLE && s.count > 0) {
+        const Fetch f{(const gc_u8 *)b.src};
+        const int32_t tpos = b.src_len - (int32_t)table_bytes(s.nf), j = e - s.slot0;
+        uint32_t coff = s.coff, doff = s.doff, c = 0, d = 0;
+        for (int32_t k = s.first; k < s.first + j; k++) {
+            seek_entry(f, tpos, k, &c, &d);
+            coff += c;
+            doff += d;
+        }
+        seek_entry(f, tpos, s.first + j, &c, &d);
+        if (d > 0u) {  // (a frame without content inside the selection has nothing to write)
+            x = jfs_dev_block{b.src + coff, b.dst + doff, (int32_t)c, (int32_t)d};
+            want = (int32_t)d;
+        }
+    }
+    xdesc[e] = x;
+    xwant[e] = want;
+}
+
+// One wave per input: its result from its entries' results.
+__global__ __launch_bounds__(64) void zseek_fold(const In *__restrict__ in, int nblk, const jfs_dev_block *__restrict__ xdesc,
+                                                 const int32_t *__restrict__ xret, int32_t *__restrict__ ret) {
+    const int i = blockIdx.x, lane = lane_id();
+    if (i >= nblk) return;
+    const In s = in[i];
+    int32_t r;
+    if (s.mode == M_PASS) {
+        r = xret[s.slot0];
+    } else if (s.mode == M_EMPTY) {
+        r = 0;
+    } else if (s.mode == M_BIG) {
+        r = -2;
+    } else {
+        bool bad = false;
+        for (int32_t j = lane; j < s.count; j += 64) {
+            const int32_t d = xdesc[s.slot0 + j].dst_cap;
+            bad = bad || (d > 0 && xret[s.slot0 + j] != d);
+        }
+        r = __ballot(bad) ? -1 : s.answer;
+    }
+    if (lane == 0) ret[i] = r;
+}
+
+namespace {
+struct Scratch {
+    std::mutex mu;
+    In *d_in = nullptr;
+    size_t in_cap = 0;
+    uint8_t *d_x = nullptr;  // per entry: descriptor, want, result
+    size_t x_cap = 0;
+    uint64_t *d_total = nullptr, *h_total = nullptr;
+    hipEvent_t ev_total = nullptr, ev_done = nullptr;
+};
+Scratch g_scr[16];
+
+template <class T>
+bool grow(T **p, size_t *cap, size_t want) {
+    if (*cap >= want) return true;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    size_t n = 1024;
+    while (n < want) n <<= 1;
+    if (hipMalloc((void **)p, n * sizeof(T)) != hipSuccess) return false;
+    *cap = n;
+    return true;
+}
+constexpr size_t X_ENTRY = sizeof(jfs_dev_block) + 8;
+}  // namespace
+
+}  // namespace zseek
+}  // namespace jfs
+
+// scan -> offsets -> (one host wait for the list's length, as the decoder waits
+// for its header scan) -> expand -> prefix decode of the list -> fold
+extern "C" int jfs_launch_zstd_decode_range(const jfs_dev_block *d_blocks, const int32_t *d_lo, const int32_t *d_hi,
+                                            int nblk, int32_t *d_ret, hipStream_t stream) {
+    using namespace jfs::zseek;
+    if (nblk <= 0) return 0;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -1;
+    Scratch &z = g_scr[dev];
+    std::lock_guard<std::mutex> lk(z.mu);
+    if (!z.d_total) {
+        if (hipMalloc((void **)&z.d_total, sizeof(uint64_t)) != hipSuccess) return -1;
+        if (hipHostMalloc((void **)&z.h_total, sizeof(uint64_t), hipHostMallocDefault) != hipSuccess) return -1;
+        if (hipEventCreateWithFlags(&z.ev_total, hipEventDisableTiming) != hipSuccess) return -1;
+        if (hipEventCreateWithFlags(&z.ev_done, hipEventDisableTiming) != hipSuccess) return -1;
+    }
+    if ((size_t)nblk > z.in_cap) {
+        // earlier launches (any stream) may still read the old scratch
+        if (hipEventSynchronize(z.ev_done) != hipSuccess) return -1;
+        if (!grow(&z.d_in, &z.in_cap, (size_t)nblk)) return -1;
+    }
+    // launches that share the scratch run in call order across streams
+    if (hipStreamWaitEvent(stream, z.ev_done, 0) != hipSuccess) return -1;
+    hipLaunchKernelGGL(zseek_scan, dim3((unsigned)nblk), dim3(64), 0, stream, d_blocks, d_lo, d_hi, nblk, z.d_in);
+    hipLaunchKernelGGL(zseek_offsets, dim3(1), dim3(64), 0, stream, z.d_in, nblk, z.d_total);
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (hipMemcpyAsync(z.h_total, z.d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, stream) != hipSuccess) return -1;
+    if (hipEventRecord(z.ev_total, stream) != hipSuccess) return -1;
+    if (hipEventSynchronize(z.ev_total) != hipSuccess) return -1;
+    const uint64_t total = *z.h_total;
+    if (total < (uint64_t)nblk || total > 0x7FFFFFF0ull / X_ENTRY) return -1;
+    // every earlier launch on the scratch is done: ev_done was waited for on
+    // `stream` ahead of ev_total
+    if (!grow(&z.d_x, &z.x_cap, (size_t)total * X_ENTRY)) return -1;
+    jfs_dev_block *xdesc = (jfs_dev_block *)z.d_x;
+    int32_t *xwant = (int32_t *)(xdesc + total), *xret = xwant + total;
+    hipLaunchKernelGGL(zseek_expand, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, stream, d_blocks, d_hi, nblk,
+                       (const In *)z.d_in, (int32_t)total, xdesc, xwant);
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (jfs_launch_zstd_decode_prefix(xdesc, (int)total, xret, xwant, stream) != 0) return -1;
+    hipLaunchKernelGGL(zseek_fold, dim3((unsigned)nblk), dim3(64), 0, stream, (const In *)z.d_in, nblk,
+                       (const jfs_dev_block *)xdesc, (const int32_t *)xret, d_ret);
+    if (hipGetLastError() != hipSuccess) return -1;
+    return hipEventRecord(z.ev_done, stream) == hipSuccess ? 0 : -1;
+}

@@ -175,6 +175,26 @@ def zstd_compress_fast(desc: torch.Tensor, ret: torch.Tensor, stream=None):
            "jfs_zstd_compress_fast_device")
 
 
+def zstd_compress_seekable(desc: torch.Tensor, ret: torch.Tensor, stream=None):
+    """jfs_zstd_compress_seekable_device: the fast parse, one frame per 128 KiB
+    block and a seek table behind them (inputs of one block at most: the fast
+    call's frame).  Ordinary Zstd objects to every reader; host-synchronous."""
+    n = desc.numel() // DESC_DTYPE.itemsize
+    _check(L.load().jfs_zstd_compress_seekable_device(desc.data_ptr(), n, ret.data_ptr(), _stream_ptr(stream)),
+           "jfs_zstd_compress_seekable_device")
+
+
+def zstd_decompress_range(desc: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor, ret: torch.Tensor, stream=None):
+    """jfs_zstd_decompress_range_device: input i is decoded for its output bytes
+    [lo[i], hi[i]) (int32 device tensors, one entry per descriptor) -- only the
+    frames the range touches when the object has a seek table, a prefix decode
+    with want = hi[i] when it has none."""
+    n = desc.numel() // DESC_DTYPE.itemsize
+    assert lo.dtype == torch.int32 and hi.dtype == torch.int32 and lo.numel() >= n and hi.numel() >= n
+    _check(L.load().jfs_zstd_decompress_range_device(desc.data_ptr(), lo.data_ptr(), hi.data_ptr(), n, ret.data_ptr(),
+                                                     _stream_ptr(stream)), "jfs_zstd_decompress_range_device")
+
+
 def crc32c(desc: torch.Tensor, crc: torch.Tensor | None = None, ret: torch.Tensor | None = None,
            seg_bytes: int = 0, stream=None):
     """CRC-32C per descriptor (jfs_crc32c_device): whole-block values into
