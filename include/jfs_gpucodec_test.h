@@ -23,8 +23,9 @@ int64_t jfs_test_spread_locking(int ndev, int iters, int timeout_ms);
 
 /* Test only. Overrides the number of pointer-jumping rounds that the
  * small-batch decoders launch (0 = the computed count); each value is
- * clamped to [0, JUMP_ROUNDS] / [0, SJ_ROUNDS]. Applies to the full and the
- * prefix launchers. Returns 0. Process-global, not thread-safe. */
+ * clamped to [0, 12] (origin_map.h MAX_ROUNDS). One value per codec, which
+ * its full and prefix launchers read. Returns 0. Process-global, not
+ * thread-safe. */
 int jfs_test_set_split_jump_rounds(int lz4_rounds, int zstd_rounds);
 
 #ifdef __cplusplus

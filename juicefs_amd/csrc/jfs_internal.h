@@ -100,10 +100,6 @@ int jfs_launch_lz4_split(const jfs_dev_block *d_desc, int nb, int32_t *d_ret, vo
 int jfs_launch_lz4_split_prefix(const jfs_dev_block *d_desc, int nb, int32_t *d_ret, const int32_t *d_want,
                                 void *d_scratch, int64_t nseg_all, int64_t max_cap, int64_t norg_all, int64_t max_want,
                                 hipStream_t st);
-// test hook jfs_test_set_split_jump_rounds (lz4_split.hip): the Zstd launchers'
-// overrides, one per translation unit (zstd_decode.hip, zstd_decode_prefix.hip)
-void jfs_zstd_split_test_jump_rounds(int rounds);
-void jfs_zstd_prefix_split_test_jump_rounds(int rounds);
 // ret value of a fused chain's second step when its first step failed
 #define JFS_CHAIN_FAILED (-2147483647 - 1)
 // compaction gather (compact.hip): verdicts into d_ret and the copy; merge != 0:

@@ -21,13 +21,11 @@
 //   count    output bytes of each segment's true tokens;
 //   scan     exclusive prefix sum per block -> output offset of each segment;
 //   emit     each lane walks its true tokens again, checks liblz4's
-//            acceptance conditions (below) and writes the block's ORIGIN map:
-//            org[p] = -(input position + 1) for a literal byte, else the output
-//            position it copies (op - off + i mod off, so overlapped matches
-//            point before the match);
-//   jump     pointer jumping over org (in place; every pointer only moves to
-//            an ancestor) until every entry is a literal: O(log chain) rounds;
-//   gather   dst[p] = src[-org[p] - 1].
+//            acceptance conditions (below) and writes the block's ORIGIN map
+//            (origin_map.h: the entries, the jump and gather rules and the
+//            round count); a literal's index is its input position;
+//   jump     pointer jumping over the map until every entry is a literal;
+//   gather   the output bytes, from the settled map.
 // Any block that this formulation does not cover EXACTLY -- a fix-up or jump
 // that did not converge in its rounds, or a token that fails one of the
 // conditions below -- is flagged and re-run by the exact one-workgroup kernel
@@ -53,6 +51,7 @@
 #include <stdint.h>
 
 #include "jfs_internal.h"
+#include "origin_map.h"
 #include "wave.cuh"
 
 namespace jfs {
@@ -60,9 +59,7 @@ namespace lz4s {
 
 constexpr int SEG = JFS_LZ4_SPLIT_SEG;  // compressed bytes per segment (one lane)
 constexpr int FIX_ROUNDS = 6;
-constexpr int JUMP_ROUNDS = 12;
-constexpr int HOPS = 6;  // pointer hops per entry per jump round
-constexpr int T = 256;   // threads per workgroup
+constexpr int T = om::THREADS;  // threads per workgroup
 
 struct SBlock {
     const uint8_t *src;
@@ -78,7 +75,7 @@ struct BStat {
     int32_t bad, last_ok, total, todo;  // bad: 1 = outside the proven cases, 2 = the stream ends in a match
     int32_t unsettled;  // the gather met an entry that is not a literal yet
     int32_t fix[FIX_ROUNDS];
-    int32_t jmp[JUMP_ROUNDS];
+    int32_t jmp[om::MAX_ROUNDS];
 };
 
 struct Scratch {
@@ -446,7 +443,7 @@ __global__ __launch_bounds__(T) void emit_kernel(int nb, int nseg_all, Scratch s
             if (l == 0) st.bad = ends_in_match(t, n) ? 2 : 1;
             return;
         }
-        const uint32_t v0 = (uint32_t)(-(t.lenip) - 1);  // literal entry i = v0 - i
+        const uint32_t v0 = om::lit_entry(t.lenip);  // literal entry i = v0 - i
         // (PREFIX: the entries below want; want - op <= 0 leaves none)
         const int32_t ll = PREFIX ? min(t.ll, want - op) : t.ll;
         for (int32_t i = l; i < ll; i += 64) org[op + i] = v0 - (uint32_t)i;
@@ -499,58 +496,21 @@ __global__ __launch_bounds__(T) void emit_thread_kernel(int nb, int nseg_all, Sc
             st.bad = ends_in_match(t, n) ? 2 : 1;
             return;
         }
-        // origin entries, 16-byte stores where the run is 4-aligned (the
-        // area starts 16-byte aligned: org_off is a multiple of 4 entries)
-        {
-            const uint32_t v0 = (uint32_t)(-(t.lenip) - 1);  // entry i = v0 - i
-            const int32_t ll = PREFIX ? min(t.ll, want - op) : t.ll;  // (the entries below want)
-            int32_t i = 0;
-            for (; i < ll && ((op + i) & 3); i++) org[op + i] = v0 - (uint32_t)i;
-            for (; i + 4 <= ll; i += 4) {
-                const uint32_t v = v0 - (uint32_t)i;
-                *(g_u4 *)(org + op + i) = make_uint4(v, v - 1u, v - 2u, v - 3u);
-            }
-            for (; i < ll; i++) org[op + i] = v0 - (uint32_t)i;
-        }
+        // (PREFIX: the entries below want; want - op <= 0 leaves none)
+        om::put_lits(org, op, PREFIX ? min(t.ll, want - op) : t.ll, om::lit_entry(t.lenip));
         op += t.ll;
         if (t.last) {
             st.last_ok = 1;
             return;
         }
-        {
-            const int32_t base = op - t.off;
-            const uint32_t off = (uint32_t)t.off;
-            const int32_t ml = PREFIX ? min(t.ml, want - op) : t.ml;
-            uint32_t j = 0;  // entry i = base + (i mod off)
-            int32_t i = 0;
-            for (; i < ml && ((op + i) & 3); i++) {
-                org[op + i] = (uint32_t)(base + j);
-                j = j + 1 == off ? 0u : j + 1;
-            }
-            for (; i + 4 <= ml; i += 4) {
-                uint32_t e[4];
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    e[q] = (uint32_t)(base + j);
-                    j = j + 1 == off ? 0u : j + 1;
-                }
-                *(g_u4 *)(org + op + i) = make_uint4(e[0], e[1], e[2], e[3]);
-            }
-            for (; i < ml; i++) {
-                org[op + i] = (uint32_t)(base + j);
-                j = j + 1 == off ? 0u : j + 1;
-            }
-        }
+        om::put_match(org, op, PREFIX ? min(t.ml, want - op) : t.ml, (uint32_t)t.off);
         op += t.ml;
         x = t.next;
         if (cut && op >= want) return;
     }
 }
 
-// grid (x: JX workgroups per block, y: block); each thread strides over its
-// block's entries, 4 at a time (a fixed, small grid: the rounds after the
-// first mostly find their block settled, and dispatching a workgroup per
-// 1,024 entries for them cost more than the hops).
+// grid (x: workgroups per block, y: block)
 __global__ __launch_bounds__(T) void jump_kernel(Scratch sc, int round) {
     const int b = blockIdx.y;
     BStat &st = sc.st[b];
@@ -559,36 +519,9 @@ __global__ __launch_bounds__(T) void jump_kernel(Scratch sc, int round) {
     const SBlock B = sc.blk[b];
     const int64_t total = min(st.total, B.want);  // (the entries the emit wrote; the full decode: st.total)
     g_u32 *org = (g_u32 *)(sc.org + B.org_off);
-    bool any = false;
-    for (int64_t p = ((int64_t)blockIdx.x * T + threadIdx.x) * 4; p < total; p += (int64_t)gridDim.x * T * 4) {
-        const int lim = total - p < 4 ? (int)(total - p) : 4;
-        uint4 v = *(const g_u4 *)(org + p);
-        const uint32_t e0[4] = {v.x, v.y, v.z, v.w};
-        int32_t o[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) o[i] = i < lim ? (int32_t)e0[i] : -1;
-        // the four entries' hops interleaved: four independent loads in flight
-        for (int h = 0; h < HOPS; h++) {
-            if (o[0] < 0 && o[1] < 0 && o[2] < 0 && o[3] < 0) break;
-            int32_t nx[4];
-#pragma unroll
-            for (int i = 0; i < 4; i++) nx[i] = o[i] >= 0 ? (int32_t)org[o[i]] : o[i];
-#pragma unroll
-            for (int i = 0; i < 4; i++) o[i] = nx[i];
-        }
-        uint32_t e[4];
-        bool changed = false;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            e[i] = i < lim ? (uint32_t)o[i] : e0[i];
-            changed |= e[i] != e0[i];
-        }
-        if (changed) {
-            *(g_u4 *)(org + p) = make_uint4(e[0], e[1], e[2], e[3]);
-            any = true;
-        }
-    }
-    if (any) st.jmp[round] = 1;
+    if (om::jump_walk(org, total, ((int64_t)blockIdx.x * T + threadIdx.x) * 4, (int64_t)gridDim.x * T * 4,
+                      [org](int32_t o) -> uint32_t { return org[o]; }))
+        st.jmp[round] = 1;
 }
 
 // blocks decoded by this path / handed to the exact kernel (diagnostics)
@@ -625,34 +558,29 @@ __global__ __launch_bounds__(T) void gather_kernel(Scratch sc) {
     const int64_t total = min(st.total, B.want);  // no byte at or above it is written
     if (p >= total) return;
     const gc_u32 *org = (const gc_u32 *)(sc.org + B.org_off);
-    const gc_u8 *s = (const gc_u8 *)B.src;
-    g_u8 *d = (g_u8 *)B.dst;
-    const uint4 v = *(const gc_u4 *)(org + p);
-    const uint32_t e[4] = {v.x, v.y, v.z, v.w};
-    bool lit = true;
-#pragma unroll
-    for (int i = 0; i < 4; i++) lit &= p + i >= total || (int32_t)e[i] < 0;
-    if (!lit) {
-        st.unsettled = 1;
-        return;
-    }
-    if (p + 4 <= total && (((uintptr_t)(d + p)) & 3u) == 0) {
-        uint32_t w = 0;
-#pragma unroll
-        for (int i = 0; i < 4; i++) w |= (uint32_t)s[-(int64_t)(int32_t)e[i] - 1] << (8 * i);
-        *(g_u32 *)(d + p) = w;
-    } else {
-        for (int i = 0; i < 4 && p + i < total; i++) d[p + i] = s[-(int64_t)(int32_t)e[i] - 1];
-    }
+    if (!om::gather_quad(org, (const gc_u8 *)B.src, (g_u8 *)B.dst, p, total)) st.unsettled = 1;
 }
 
 }  // namespace lz4s
 }  // namespace jfs
 
 using namespace jfs::lz4s;
+namespace om = jfs::om;
 
-// Scratch layout, shared by the planner on the host and the launcher.
-static int64_t a256(int64_t x) { return (x + 255) & ~255ll; }
+// Scratch layout: carves the areas from d_scratch (null: only the size
+// counts) and returns the bytes it takes, for the host's size query and the launcher.
+static int64_t layout(void *d_scratch, int64_t nb, int64_t nseg_all, int64_t norg_all, Scratch &sc, int32_t *&todo) {
+    om::Carve c(d_scratch);
+    c.take(sc.blk, nb * (int64_t)sizeof(SBlock));
+    c.take(sc.st, nb * (int64_t)sizeof(BStat));
+    c.take(sc.spec_exit, nseg_all * 4);
+    c.take(sc.entry, nseg_all * 4);
+    c.take(sc.cnt, nseg_all * 4);
+    c.take(sc.bits, nseg_all * (SEG / 8));
+    c.take(todo, nb * 4);
+    c.take(sc.org, norg_all * 4);
+    return c.bytes;
+}
 
 extern "C" int64_t jfs_lz4_split_scratch_bytes(int nb, const int32_t *src_len, const int32_t *cap) {
     int64_t seg = 0, org = 0;
@@ -661,13 +589,10 @@ extern "C" int64_t jfs_lz4_split_scratch_bytes(int nb, const int32_t *src_len, c
         seg += (n + SEG - 1) / SEG;
         org += (c + 3) & ~3ll;
     }
-    return a256(nb * (int64_t)sizeof(SBlock)) + a256(nb * (int64_t)sizeof(BStat)) + 3 * a256(seg * 4) +
-           a256(seg * (SEG / 8)) + a256(org * 4) + a256(nb * 4) + 256;
+    Scratch sc;
+    int32_t *todo;
+    return layout(nullptr, nb, seg, org, sc, todo);
 }
-
-// Test only (jfs_test_set_split_jump_rounds): the pointer-jumping rounds to
-// launch instead of the computed count; 0 = the computed count.
-static int g_test_jump_rounds = 0;
 
 // nseg_all / max_cap: Σ segments and the largest dst_cap (grid sizes); the
 // host computes both from the same (src_len, cap) it sized the scratch with.
@@ -679,25 +604,10 @@ static int launch_split(const jfs_dev_block *d_desc, int nb, int32_t *d_ret, con
                         int64_t nseg_all, int64_t max_cap, int64_t norg_all, int64_t max_want, hipStream_t st) {
     if (nb <= 0) return 0;
     max_want = std::max<int64_t>(0, std::min(max_want, max_cap));
-    uint8_t *p = (uint8_t *)(((uintptr_t)d_scratch + 255) & ~(uintptr_t)255);
     Scratch sc;
-    sc.blk = (SBlock *)p;
-    p += a256(nb * (int64_t)sizeof(SBlock));
-    sc.st = (BStat *)p;
-    p += a256(nb * (int64_t)sizeof(BStat));
-    sc.spec_exit = (int32_t *)p;
-    p += a256(nseg_all * 4);
-    sc.entry = (int32_t *)p;
-    p += a256(nseg_all * 4);
-    sc.cnt = (int32_t *)p;
-    p += a256(nseg_all * 4);
-    sc.bits = (uint32_t *)p;
-    p += a256(nseg_all * (SEG / 8));
-    int32_t *todo = (int32_t *)p;
-    p += a256(nb * 4);
-    sc.org = (int32_t *)p;
+    int32_t *todo;
+    layout(d_scratch, nb, nseg_all, norg_all, sc, todo);
     const int gs = (int)((nseg_all + T - 1) / T);
-    const dim3 gp((unsigned)((max_want / 4 + T) / T), (unsigned)nb);
     hipLaunchKernelGGL(plan_kernel, dim3(1), dim3(T), 0, st, d_desc, d_want, nb, sc, nseg_all, max_cap, norg_all, max_want);
     if (nseg_all > 0) {
         hipLaunchKernelGGL(spec_kernel, dim3(gs), dim3(T), 0, st, nb, (int)nseg_all, sc);
@@ -713,20 +623,10 @@ static int launch_split(const jfs_dev_block *d_desc, int nb, int32_t *d_ret, con
         else
             hipLaunchKernelGGL(emit_thread_kernel<PREFIX>, dim3((unsigned)gs), dim3(T), 0, st, nb, (int)nseg_all, sc);
     }
-    // jump grid: about 2,048 workgroups in all (every entry of a 4 MiB block
-    // is covered after a few strides), at most one per 1,024 entries
-    const unsigned jx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((max_want / 4 + T) / T, (2048 + nb - 1) / nb));
-    // Rounds: after round r every entry points >= HOPS^r steps up its chain (or
-    // to a literal), and a chain is at most one step per token (a step from a
-    // token's match lands in an earlier token's output or in its own
-    // literals), i.e. <= max_want / 4 + 1 steps: HOPS^jr above that settles
-    // every well-formed block (8 rounds for 4 MiB; each idle launch cost ~6 us
-    // of a lone decode).  The gather checks every entry regardless.
-    int jr = 1;
-    for (double reach = HOPS; reach <= (double)max_want / 4 + 1 && jr < JUMP_ROUNDS; reach *= HOPS) jr++;
-    if (g_test_jump_rounds > 0) jr = g_test_jump_rounds;
+    const unsigned jx = om::jump_groups(max_want, nb);
+    const int jr = om::launch_rounds(max_want, 4);
     for (int r = 0; r < jr; r++) hipLaunchKernelGGL(jump_kernel, dim3(jx, (unsigned)nb), dim3(T), 0, st, sc, r);
-    hipLaunchKernelGGL(gather_kernel, gp, dim3(T), 0, st, sc);
+    hipLaunchKernelGGL(gather_kernel, dim3(om::quad_groups(max_want), (unsigned)nb), dim3(T), 0, st, sc);
     hipLaunchKernelGGL(verdict_kernel, dim3((nb + 63) / 64), dim3(64), 0, st, nb, sc, d_ret, todo);
     if (hipGetLastError() != hipSuccess) return -1;
     // the exact one-workgroup kernel for the flagged blocks (the others exit at once)
@@ -746,12 +646,10 @@ extern "C" int jfs_launch_lz4_split_prefix(const jfs_dev_block *d_desc, int nb, 
     return launch_split<true>(d_desc, nb, d_ret, d_want, d_scratch, nseg_all, max_cap, norg_all, max_want, st);
 }
 
-// Test hook (include/jfs_gpucodec_test.h): each translation unit that sizes a
-// jump loop keeps its own override.
+// Test hook (include/jfs_gpucodec_test.h)
 extern "C" int jfs_test_set_split_jump_rounds(int lz4_rounds, int zstd_rounds) {
-    g_test_jump_rounds = std::max(0, std::min(lz4_rounds, JUMP_ROUNDS));
-    jfs_zstd_split_test_jump_rounds(zstd_rounds);
-    jfs_zstd_prefix_split_test_jump_rounds(zstd_rounds);
+    om::test_rounds[0] = std::max(0, std::min(lz4_rounds, om::MAX_ROUNDS));
+    om::test_rounds[1] = std::max(0, std::min(zstd_rounds, om::MAX_ROUNDS));
     return 0;
 }
 

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "jfs_internal.h"
+#include "origin_map.h"
 #include "wave.cuh"
 #include "zstd_walk.h"
 
@@ -2390,8 +2391,6 @@ int zsplit_max() {
     return v;
 }
 
-int64_t a256(int64_t x) { return (x + 255) & ~255ll; }
-
 // The small-batch path's scratch grows with the blocks (one record each) and
 // the output capacity (one origin entry per byte): inputs made of very many
 // tiny blocks, or huge capacities, take the one-wave path instead.
@@ -2399,30 +2398,29 @@ bool split_ok(int nblk, const uint64_t *tot) {
     return nblk <= zsplit_max() && tot[3] <= (uint64_t)nblk * 512 + 4096 && tot[4] <= (1ull << 30);
 }
 
-// tot: the plan totals (zplan need[] / jfs_zstd_plan_host): [3] blocks,
-// [4] origin entries, [5] largest dst_cap
-int64_t split_bytes(int nblk, const uint64_t *tot) {
+// Scratch layout: carves the areas from d_split (null: only the size counts)
+// and returns the bytes it takes.  tot: the plan totals (zplan need[] /
+// jfs_zstd_plan_host): [3] blocks, [4] origin entries, [5] largest dst_cap
+int64_t split_layout(void *d_split, int nblk, const uint64_t *tot, jfs::JFS_ZNS::SScr &sc) {
     using namespace jfs::JFS_ZNS;
-    return a256((int64_t)nblk * (int64_t)sizeof(SIn)) + a256((int64_t)tot[3] * (int64_t)sizeof(SBlk)) +
-           a256((int64_t)nblk * 4) + a256((int64_t)tot[4] * 4) + 256;
+    jfs::om::Carve c(d_split);
+    c.take(sc.in, (int64_t)nblk * (int64_t)sizeof(SIn));
+    c.take(sc.blk, (int64_t)tot[3] * (int64_t)sizeof(SBlk));
+    c.take(sc.todo, (int64_t)nblk * 4);
+    c.take(sc.org, (int64_t)tot[4] * 4);
+    return c.bytes;
 }
-
-// Test only (jfs_test_set_split_jump_rounds): the pointer-jumping rounds to
-// launch instead of the computed count; 0 = the computed count.
-int g_test_jump_rounds = 0;
+int64_t split_bytes(int nblk, const uint64_t *tot) {
+    jfs::JFS_ZNS::SScr sc;
+    return split_layout(nullptr, nblk, tot, sc);
+}
 
 int launch_split(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, jfs::zstdd::ZInfo *d_info, uint8_t *d_lit,
                  uint4 *d_items, void *d_split, const uint64_t *tot, hipStream_t st) {
     using namespace jfs::JFS_ZNS;
-    uint8_t *p = (uint8_t *)(((uintptr_t)d_split + 255) & ~(uintptr_t)255);
+    namespace om = jfs::om;
     SScr sc;
-    sc.in = (SIn *)p;
-    p += a256((int64_t)nblk * (int64_t)sizeof(SIn));
-    sc.blk = (SBlk *)p;
-    p += a256((int64_t)tot[3] * (int64_t)sizeof(SBlk));
-    sc.todo = (int32_t *)p;
-    p += a256((int64_t)nblk * 4);
-    sc.org = (int32_t *)p;
+    split_layout(d_split, nblk, tot, sc);
     const int64_t nbk = (int64_t)tot[3], max_cap = (int64_t)tot[5];
     hipLaunchKernelGGL(zsplan_kernel, dim3(1), dim3(64), 0, st, d_info, nblk, sc);
     hipLaunchKernelGGL(zswalk_kernel, dim3(nblk), dim3(64), 0, st, d_blocks, nblk, d_info, d_items, sc,
@@ -2434,19 +2432,11 @@ int launch_split(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, jfs::z
     if (nbk > 0)
         hipLaunchKernelGGL(zsemit_kernel, dim3((unsigned)nbk, ZSE_PARTS), dim3(ST), 0, st, nblk, (const ZInfo *)d_info,
                            (const uint4 *)d_items, sc);
-    const unsigned jx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((max_cap / 4 + ST) / ST, (2048 + nblk - 1) / nblk));
-    // Rounds: after round r every entry points >= SJ_HOPS^r steps up its chain
-    // (or to a literal), and a step from a match byte lands in an earlier
-    // sequence's output (overlaps point before their match), so a chain has
-    // at most one step per sequence, <= max_cap / 3 + 1 (matches are >= 3
-    // bytes): SJ_HOPS^jr above that settles every well-formed input (8 rounds
-    // for 4 MiB).  The gather checks every entry regardless.
-    int jr = 1;
-    for (double reach = SJ_HOPS; reach <= (double)max_cap / 3 + 1 && jr < SJ_ROUNDS; reach *= SJ_HOPS) jr++;
-    if (g_test_jump_rounds > 0) jr = g_test_jump_rounds;
+    const unsigned jx = om::jump_groups(max_cap, nblk);
+    const int jr = om::launch_rounds(max_cap, 3);
     for (int r = 0; r < jr; r++) hipLaunchKernelGGL(zsjump_kernel, dim3(jx, (unsigned)nblk), dim3(ST), 0, st, sc, r);
-    hipLaunchKernelGGL(zsgather_kernel, dim3((unsigned)((max_cap / 4 + ST) / ST), (unsigned)nblk), dim3(ST), 0, st,
-                       d_blocks, (const ZInfo *)d_info, (const uint8_t *)d_lit, sc);
+    hipLaunchKernelGGL(zsgather_kernel, dim3(om::quad_groups(max_cap), (unsigned)nblk), dim3(ST), 0, st, d_blocks,
+                       (const ZInfo *)d_info, (const uint8_t *)d_lit, sc);
     hipLaunchKernelGGL(zsverd_kernel, dim3((nblk + 63) / 64), dim3(64), 0, st, nblk, sc, d_ret);
     hipLaunchKernelGGL(zexec_kernel, dim3(nblk), dim3(64), 0, st, d_blocks, nblk, (const ZInfo *)d_info,
                        (const uint8_t *)d_lit, (const uint4 *)d_items, d_ret, (const int32_t *)sc.todo);
@@ -2471,14 +2461,8 @@ int split_counts_add(uint64_t *out, int reset) {
 
 #ifdef JFS_ZSTD_DECODE_PREFIX_TU
 extern "C" int jfs_zstd_prefix_split_counts_add(uint64_t *out, int reset) { return split_counts_add(out, reset); }
-extern "C" void jfs_zstd_prefix_split_test_jump_rounds(int rounds) {
-    g_test_jump_rounds = std::max(0, std::min(rounds, (int)jfs::JFS_ZNS::SJ_ROUNDS));
-}
 #else
 extern "C" int jfs_zstd_prefix_split_counts_add(uint64_t *out, int reset);
-extern "C" void jfs_zstd_split_test_jump_rounds(int rounds) {
-    g_test_jump_rounds = std::max(0, std::min(rounds, (int)jfs::JFS_ZNS::SJ_ROUNDS));
-}
 extern "C" int jfs_zstd_split_ok(int nblk, const uint64_t *tot) { return split_ok(nblk, tot) ? 1 : 0; }
 extern "C" int64_t jfs_zstd_split_bytes(int nblk, const uint64_t *tot) { return split_bytes(nblk, tot); }
 

@@ -21,22 +21,20 @@
 //             the blocks' output offsets; an input outside the proven cases
 //             (not exactly one frame, a checksum, any error item, a size or
 //             literal-count check) is marked for the exact replay;
-//   zsemit    one workgroup per block writes the ORIGIN of each output byte:
-//             -(literal index + 1), or the output position it copies
-//             (overlapping matches point before the match);
-//   zsjump    pointer jumping (in place; each pointer only moves to an
-//             ancestor), rounds enough for the longest possible chain;
-//   zsgather  dst[p] = literal[-org[p] - 1]; an entry that is not a literal
-//             marks its input;
+//   zsemit    one workgroup per block writes the ORIGIN of each output byte
+//             (origin_map.h: the entries, the jump and gather rules and the
+//             round count); a literal's index is its place in the input's
+//             literal area;
+//   zsjump    pointer jumping over the map;
+//   zsgather  the output bytes; an entry that is not a literal marks its
+//             input;
 //   zsverd    the marked inputs go to the exact replay;
 //   zexec     the exact replay, for the marked inputs only: it reads the same
 //             items and literals, so results and error codes are the exact
 //             path's on every input.
 // ===========================================================================
-constexpr int SJ_ROUNDS = 12;  // pointer-jumping rounds
-constexpr int SJ_HOPS = 6;     // hops per entry per round
-constexpr int ST = 256;        // threads per workgroup (emit / jump / gather)
-constexpr int SCHUNK = 2048;   // sequence bitstream chunk staged per refill
+constexpr int ST = om::THREADS;  // threads per workgroup (emit / jump / gather)
+constexpr int SCHUNK = 2048;     // sequence bitstream chunk staged per refill
 constexpr int SRING = 4 * SCHUNK;
 enum { SB_STORE = 1, SB_FIRST = 2, SB_SEQ = 4, SB_LIT = 8 };
 
@@ -65,7 +63,7 @@ struct SIn {                 // one input
     int32_t unsettled, pad;  // the gather met an entry that is not a literal yet
     uint64_t fcs;
     int64_t total;
-    int32_t jmp[SJ_ROUNDS];
+    int32_t jmp[om::MAX_ROUNDS];
 };
 
 struct SScr {
@@ -84,7 +82,7 @@ __global__ void zsplan_kernel(const ZInfo *__restrict__ info, int nblk, SScr sc)
         x.org_off = oo;
         x.nb = 0; x.ok = 0; x.has_fcs = 0; x.todo = 1; x.unsettled = 0;
         x.fcs = 0; x.total = 0;
-        for (int r = 0; r < SJ_ROUNDS; r++) x.jmp[r] = 0;
+        for (int r = 0; r < om::MAX_ROUNDS; r++) x.jmp[r] = 0;
         sc.todo[i] = 1;
         bo += info[i].n_blk;
         oo += ((int64_t)(info[i].cap > 0 ? info[i].cap : 0) + 3) & ~3ll;
@@ -693,17 +691,6 @@ __global__ __launch_bounds__(64) void zsfix_kernel(const jfs_dev_block *__restri
     }
 }
 
-// origin entries [p, p + n) = v0, v0 - 1, ... (literal indices, encoded negative)
-__device__ __forceinline__ void org_lits(g_u32 *org, int64_t p, int64_t n, uint32_t v0) {
-    int64_t i = 0;
-    for (; i < n && ((p + i) & 3); i++) org[p + i] = v0 - (uint32_t)i;
-    for (; i + 4 <= n; i += 4) {
-        const uint32_t v = v0 - (uint32_t)i;
-        *(g_u4 *)(org + p + i) = make_uint4(v, v - 1u, v - 2u, v - 3u);
-    }
-    for (; i < n; i++) org[p + i] = v0 - (uint32_t)i;
-}
-
 // grid (x: block record, y: ZSE_PARTS ranges of the block's sequences): a
 // range's workgroup first sums the items before it (a coalesced pass: its
 // start in the output and in the literals), then scans its own and writes
@@ -725,7 +712,7 @@ __global__ __launch_bounds__(ST) void zsemit_kernel(int nblk, const ZInfo *__res
     if (ZPFX && o0 >= si.total) return;  // prefix decode: a block behind `want` (si.total <= want) is never read
     if (d.btype != 2) {
         for (int64_t i = part * ST + t; i < d.bsize; i += ST * ZSE_PARTS)
-            org[o0 + i] = (uint32_t)(-(int64_t)(d.lpos + i) - 1);
+            org[o0 + i] = om::lit_entry((int64_t)(d.lpos + i));
         return;
     }
     const gc_u4 *it = (const gc_u4 *)items_all + info[bi].item_off + d.slot + 2;
@@ -775,31 +762,12 @@ __global__ __launch_bounds__(ST) void zsemit_kernel(int nblk, const ZInfo *__res
     for (int32_t q = q0; q < q1 && !bad; q++) {
         const uint4 v = it[q];
         const uint32_t ll = v.x, ml = v.y, off = rep_res(v.z, e0, e1, e2);
-        org_lits(org, pos, ll, (uint32_t)(-(int64_t)lp - 1));
+        om::put_lits<int64_t>(org, pos, ll, om::lit_entry((int64_t)lp));
         pos += ll;
         lp += ll;
         if (ml) {
             if ((int64_t)off > pos) { bad = true; break; }  // before the frame start
-            const int64_t base = pos - off;
-            uint32_t j = 0;
-            int64_t i = 0;
-            for (; i < ml && ((pos + i) & 3); i++) {
-                org[pos + i] = (uint32_t)(base + j);
-                j = j + 1 == off ? 0u : j + 1;
-            }
-            for (; i + 4 <= ml; i += 4) {
-                uint32_t e[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    e[u] = (uint32_t)(base + j);
-                    j = j + 1 == off ? 0u : j + 1;
-                }
-                *(g_u4 *)(org + pos + i) = make_uint4(e[0], e[1], e[2], e[3]);
-            }
-            for (; i < ml; i++) {
-                org[pos + i] = (uint32_t)(base + j);
-                j = j + 1 == off ? 0u : j + 1;
-            }
+            om::put_match<int64_t>(org, pos, ml, off);
             pos += ml;
         }
     }
@@ -807,51 +775,23 @@ __global__ __launch_bounds__(ST) void zsemit_kernel(int nblk, const ZInfo *__res
     const int64_t rest = (int64_t)d.regen - (int64_t)d.sll;
     const int64_t tail = o0 + (int64_t)d.regen + (int64_t)d.sml - rest;
     if (part == ZSE_PARTS - 1)
-        for (int64_t i = t; i < rest; i += ST) org[tail + i] = (uint32_t)(-(int64_t)(d.lpos + d.sll + i) - 1);
+        for (int64_t i = t; i < rest; i += ST) org[tail + i] = om::lit_entry((int64_t)(d.lpos + d.sll + i));
     if (bad) {
         si.todo = 1;
         sc.todo[bi] = 1;
     }
 }
 
-// grid (x: workgroups per input, y: input); every pointer only moves to an
-// ancestor, so concurrent updates are safe
+// grid (x: workgroups per input, y: input)
 __global__ __launch_bounds__(ST) void zsjump_kernel(SScr sc, int round) {
     const int bi = blockIdx.y;
     SIn &si = sc.in[bi];
     if (si.todo) return;
     if (round > 0 && !si.jmp[round - 1]) return;
-    const int64_t total = si.total;
     g_u32 *org = (g_u32 *)(sc.org + si.org_off);
-    bool any = false;
-    for (int64_t p = ((int64_t)blockIdx.x * ST + threadIdx.x) * 4; p < total; p += (int64_t)gridDim.x * ST * 4) {
-        const int lim = total - p < 4 ? (int)(total - p) : 4;
-        const uint4 v = *(const g_u4 *)(org + p);
-        const uint32_t e0[4] = {v.x, v.y, v.z, v.w};
-        int32_t o[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) o[i] = i < lim ? (int32_t)e0[i] : -1;
-        for (int h = 0; h < SJ_HOPS; h++) {
-            if (o[0] < 0 && o[1] < 0 && o[2] < 0 && o[3] < 0) break;
-            int32_t nx[4];
-#pragma unroll
-            for (int i = 0; i < 4; i++) nx[i] = o[i] >= 0 ? (int32_t)org[o[i]] : o[i];
-#pragma unroll
-            for (int i = 0; i < 4; i++) o[i] = nx[i];
-        }
-        uint32_t e[4];
-        bool changed = false;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            e[i] = i < lim ? (uint32_t)o[i] : e0[i];
-            changed |= e[i] != e0[i];
-        }
-        if (changed) {
-            *(g_u4 *)(org + p) = make_uint4(e[0], e[1], e[2], e[3]);
-            any = true;
-        }
-    }
-    if (any) si.jmp[round] = 1;
+    if (om::jump_walk(org, si.total, ((int64_t)blockIdx.x * ST + threadIdx.x) * 4, (int64_t)gridDim.x * ST * 4,
+                      [org](int32_t o) -> uint32_t { return org[o]; }))
+        si.jmp[round] = 1;
 }
 
 // inputs (small-batch path) decoded by the origin map / handed to zexec
@@ -879,22 +819,6 @@ __global__ __launch_bounds__(ST) void zsgather_kernel(const jfs_dev_block *__res
     if (p >= total) return;
     const gc_u32 *org = (const gc_u32 *)(sc.org + si.org_off);
     const gc_u8 *lit = (const gc_u8 *)litbuf + info[bi].lit_off;
-    g_u8 *dst = (g_u8 *)blocks[bi].dst;
-    const uint4 v = *(const gc_u4 *)(org + p);
-    const uint32_t e[4] = {v.x, v.y, v.z, v.w};
-    bool settled = true;
-#pragma unroll
-    for (int i = 0; i < 4; i++) settled &= p + i >= total || (int32_t)e[i] < 0;
-    if (!settled) {  // (runs before the verdict: the exact replay rewrites the input)
-        sc.in[bi].unsettled = 1;
-        return;
-    }
-    if (p + 4 <= total && (((uintptr_t)(dst + p)) & 3u) == 0) {
-        uint32_t w = 0;
-#pragma unroll
-        for (int i = 0; i < 4; i++) w |= (uint32_t)lit[-(int64_t)(int32_t)e[i] - 1] << (8 * i);
-        *(g_u32 *)(dst + p) = w;
-    } else {
-        for (int i = 0; i < 4 && p + i < total; i++) dst[p + i] = lit[-(int64_t)(int32_t)e[i] - 1];
-    }
+    // (runs before the verdict: the exact replay rewrites a marked input)
+    if (!om::gather_quad(org, lit, (g_u8 *)blocks[bi].dst, p, total)) sc.in[bi].unsettled = 1;
 }

@@ -13,7 +13,7 @@ SEG = 256        # JFS_LZ4_SPLIT_SEG (jfs_internal.h): compressed bytes per segm
 T = 256          # lz4_split.hip T: segments per fix-up workgroup
 FIX_ROUNDS = 6   # lz4_split.hip FIX_ROUNDS: fix_kernel launches per decode
 SPAN = SEG * T   # compressed bytes one fix-up workgroup covers (64 KiB)
-HOPS = 6         # lz4_split.hip HOPS = zstd_split.inc SJ_HOPS: pointer hops per entry per jump round
+HOPS = 6         # origin_map.h HOPS: pointer hops per entry per jump round
 ZBLOCK = 128 << 10  # Zstd Block_Maximum_Size
 
 
@@ -196,9 +196,10 @@ NWG_EDGE, NWG_OVER = 6, 7
 
 
 def jump_rounds(size, unit, max_rounds=12):
-    """The launchers' round count for `size` output bytes: the smallest jr with
-    HOPS^jr > size / unit + 1 (unit 4: lz4_split.hip, a chain step per token;
-    unit 3: zstd_decode.hip, a step per sequence), at most JUMP_ROUNDS = SJ_ROUNDS = 12."""
+    """The launchers' round count for `size` output bytes, origin_map.h
+    rounds(): the smallest jr with HOPS^jr > size / unit + 1 (unit 4: LZ4, a
+    chain step per token; unit 3: Zstd, a step per sequence), at most
+    MAX_ROUNDS = 12.  tests/test_origin_map.py holds this mirror to the header."""
     jr, reach = 1, HOPS
     while reach <= size / unit + 1 and jr < max_rounds:
         jr, reach = jr + 1, reach * HOPS

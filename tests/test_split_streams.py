@@ -25,13 +25,16 @@ def test_constants_restate_the_sources():
     hdr = open(os.path.join(root, "jfs_internal.h")).read()
     src = open(os.path.join(root, "lz4_split.hip")).read()
     zs = open(os.path.join(root, "zstd_split.inc")).read()
+    om = open(os.path.join(root, "origin_map.h")).read()
     assert int(re.search(r"#define JFS_LZ4_SPLIT_SEG (\d+)", hdr).group(1)) == S.SEG
     assert int(re.search(r"constexpr int FIX_ROUNDS = (\d+);", src).group(1)) == S.FIX_ROUNDS
-    assert int(re.search(r"constexpr int T = (\d+);", src).group(1)) == S.T
-    assert int(re.search(r"constexpr int HOPS = (\d+);", src).group(1)) == S.HOPS
-    assert int(re.search(r"constexpr int SJ_HOPS = (\d+);", zs).group(1)) == S.HOPS
-    assert int(re.search(r"constexpr int JUMP_ROUNDS = (\d+);", src).group(1)) == 12
-    assert int(re.search(r"constexpr int SJ_ROUNDS = (\d+);", zs).group(1)) == 12
+    # the origin-map constants live in origin_map.h alone; both codecs take them from there
+    assert int(re.search(r"constexpr int THREADS = (\d+);", om).group(1)) == S.T
+    assert re.search(r"constexpr int T = om::THREADS;", src) and re.search(r"constexpr int ST = om::THREADS;", zs)
+    assert int(re.search(r"constexpr int HOPS = (\d+);", om).group(1)) == S.HOPS
+    assert int(re.search(r"constexpr int MAX_ROUNDS = (\d+);", om).group(1)) == 12
+    assert "jmp[om::MAX_ROUNDS]" in src and "jmp[om::MAX_ROUNDS]" in zs
+    assert not re.search(r"constexpr int (HOPS|SJ_HOPS|JUMP_ROUNDS|SJ_ROUNDS)\b", src + zs)
 
 
 def test_chain_streams_decode(oracle):
