@@ -44,7 +44,10 @@ constexpr int CW = 64 * P;             // compressed window bytes handled per pa
 constexpr int CWIN = CW + 80;          // LDS staging incl. lookahead (multiple of 16)
 constexpr int R = 4096;                // output ring bytes (power of two)
 constexpr int RMASK = R - 1;
-constexpr int SEG = 128;               // segment-walk parser: bytes per lane
+#ifndef JFS_LZ4_WALK_SEG
+#define JFS_LZ4_WALK_SEG 256
+#endif
+constexpr int SEG = JFS_LZ4_WALK_SEG;  // segment-walk parser: bytes per lane (128 or 256)
 constexpr int TMAX = CW / 3 + 2;       // max tokens in a window (interior token >= 3 bytes)
 // Table capacity per window.  Windows with more tokens (only runs of 3..5-byte
 // tokens) end at token TCAP and the next window starts there; the cap keeps the
@@ -972,10 +975,12 @@ __device__ __forceinline__ uint32_t copy_tokens(Smem &s, Ctx &c, uint32_t T, int
 // true entry (the previous segment's exit) until nothing changes.  The chain
 // positions stay in the lanes' registers (SEG bits each) while the windows of
 // the span are staged and tabled.  A long segment amortizes the pre-roll and
-// the fix-up over ~SEG/5.6 tokens per lane; the window exit-table parser spent
-// ~29 VALU per byte offset.
+// the fix-up over ~SEG/5.6 tokens per lane (the fix-up's join distance does
+// not depend on SEG: 256 against 128 measured in DESIGN.md 3i); the window
+// exit-table parser spent ~29 VALU per byte offset.
 // ---------------------------------------------------------------------------
-static_assert(SEG == 128, "segment bit sets are two u64 per lane");
+static_assert(SEG == 128 || SEG == 256, "a lane's segment bit set: two or four u64 (BitSet, lz4_walkstep.h)");
+using SegBits = BitSet<SEG>;
 constexpr int SW = 64 * SEG;
 constexpr int SPRE = 32;         // speculative pre-roll before each segment (16 / 48 measured no better)
 constexpr int SEG_BUDGET = 64;   // at most this many walk steps of the next span per window
@@ -999,16 +1004,15 @@ __device__ __noinline__ uint32_t g_next_exact(const Ctx &c, int32_t p) {
 // `budget` walk steps (one HBM load round each) and returns true once the
 // chain is final, so the parser wave can walk the next span a few steps per
 // window while the copier works (the walk is bound by load latency).
-// Result: vt0/vt1 = true chain positions of this lane's segment, ex = its
+// Result: vt = true chain positions of this lane's segment, ex = its
 // true exit (first position >= its end, or STOP | p).
 struct SegWalk {
     int32_t base, plo, phi;
     int32_t q;            // walk position of a moving lane
     uint32_t cur;         // entry the current result assumes
     uint32_t sx, ex;      // speculative / true exit
-    uint64_t vs0, vs1;    // speculative chain positions
-    uint64_t vt0, vt1;    // true chain positions
-    uint64_t vp0, vp1;    // positions of a fix-up walk
+    SegBits vs;           // speculative chain positions
+    SegBits vt;           // true chain positions (of a lane in a fix-up walk: the walk's so far)
     bool mv;              // this lane is walking
     uint32_t pe2;         // the byte fetched for a step's owed e2 test (lz4_walkstep.h)
     bool pend;            // whether one is owed (the step: sx / ex while the lane moves)
@@ -1023,7 +1027,8 @@ struct SegWalk {
         phi = plo + SEG;
         cur = l == 0 ? (uint32_t)b : (uint32_t)(plo - SPRE);
         q = (int32_t)cur;
-        vs0 = vs1 = vt0 = vt1 = vp0 = vp1 = 0;
+        vs.clear();
+        vt.clear();
         sx = ex = 0;
         mv = true;
         pe2 = 0;
@@ -1043,13 +1048,12 @@ struct SegWalk {
             for (; budget > 0 && __ballot(mv); --budget) {
                 PCOUNT(11, 1);
                 int kind = WS_STEPPED;
-                if (mv) kind = ws_spec_iter(*this, fetch, exact, c.n);
+                if (mv) kind = ws_spec_iter(*this, vs, fetch, exact, c.n);
                 PWALK(kind);
                 if (++steps > SEG + SPRE) { c.bug = 6; phase = 2; return true; }
             }
             if (budget == 0) return false;
-            vt0 = vs0;
-            vt1 = vs1;
+            vt = vs;
             ex = sx;
             phase = 1;
             round = true;
@@ -1068,25 +1072,24 @@ struct SegWalk {
                     cur = In;
                     const uint32_t d = In - (uint32_t)plo;
                     if ((In & STOP) || (int32_t)In >= phi) {
-                        vt0 = vt1 = 0;
+                        vt.clear();
                         ex = In;
-                    } else if (tbit2(vs0, vs1, d)) {
-                        vt0 = vs0 & from_lo(d);
-                        vt1 = vs1 & from_hi(d);
+                    } else if (vs.test(d)) {
+                        vt = vs.and_from(d);
                         ex = sx;
                     } else {
+                        vt.clear();  // the walk records into vt
                         mv = true;
                     }
                 }
                 q = (int32_t)In;
-                vp0 = vp1 = 0;
                 steps = 0;
                 round = false;
             }
             for (; budget > 0 && __ballot(mv); --budget) {
                 PCOUNT(13, 1);
                 int kind = WS_STEPPED;
-                if (mv) kind = ws_fix_iter(*this, fetch, exact, c.n);
+                if (mv) kind = ws_fix_iter(*this, vs, vt, fetch, exact, c.n);
                 PWALK(kind);
                 if (++steps > SEG + 1) { c.bug = 7; phase = 2; return true; }
             }
@@ -1096,22 +1099,24 @@ struct SegWalk {
     }
 };
 
-// Dword k (0..4*64-1) of the span's bit set; lane k/4 holds it as dword k%4 of
-// (vt0, vt1).  Out-of-span dwords read as 0.
-__device__ __forceinline__ uint32_t span_dword(uint64_t vt0, uint64_t vt1, int32_t k) {
-    const int src = (k >> 2) & 63;
-    const uint32_t d0 = (uint32_t)__shfl((int)(uint32_t)vt0, src, 64);
-    const uint32_t d1 = (uint32_t)__shfl((int)(uint32_t)(vt0 >> 32), src, 64);
-    const uint32_t d2 = (uint32_t)__shfl((int)(uint32_t)vt1, src, 64);
-    const uint32_t d3 = (uint32_t)__shfl((int)(uint32_t)(vt1 >> 32), src, 64);
-    const uint32_t j = (uint32_t)k & 3u;
-    const uint32_t v = j == 0 ? d0 : j == 1 ? d1 : j == 2 ? d2 : d3;
-    return (k >= 0 && k < 4 * 64) ? v : 0u;
+// Dword k (0 .. 64 * SEG / 32 - 1) of the span's bit set; lane k / (SEG / 32)
+// holds it as dword k % (SEG / 32) of its set.  Out-of-span dwords read as 0.
+__device__ __forceinline__ uint32_t span_dword(const SegBits &v, int32_t k) {
+    constexpr int DW = SEG / 32;
+    const int src = (k >> (DW == 4 ? 2 : 3)) & 63;
+    const uint32_t j = (uint32_t)k & (uint32_t)(DW - 1);
+    uint32_t r = 0;
+    ws_each<DW>([&](auto i) {
+        const uint32_t di = (uint32_t)(v.w[i.v >> 1] >> (32 * (i.v & 1)));
+        const uint32_t got = (uint32_t)__shfl((int)di, src, 64);
+        r = j == (uint32_t)i.v ? got : r;
+    });
+    return (k >= 0 && k < DW * 64) ? r : 0u;
 }
 
 // The chain of one span (seg_chain), kept by the parser wave across windows.
 struct Span {
-    uint64_t v0, v1;  // this lane's segment bits
+    SegBits v;        // this lane's segment bits
     int32_t base;     // span start (a true chain position)
     uint32_t exit;    // first chain position >= base + SW, or STOP | p
 };
@@ -1132,7 +1137,7 @@ __device__ __forceinline__ void parse_window_seg(Smem &s, Ctx &c, int32_t wbase,
     // lane l: positions [cbase + 32 l, + 32) = span bits [o, o + 32)
     const int32_t o = cbase - sp.base + 32 * l;  // >= -15
     const int32_t K = o >> 5;
-    const uint32_t lo = span_dword(sp.v0, sp.v1, K), hi = span_dword(sp.v0, sp.v1, K + 1);
+    const uint32_t lo = span_dword(sp.v, K), hi = span_dword(sp.v, K + 1);
     uint32_t field = __builtin_amdgcn_alignbit(hi, lo, (uint32_t)o & 31u);
     const int32_t plo = cbase + 32 * l;
     const int32_t a = wbase - plo, b = wend - plo;  // keep bits [a, b)
@@ -1167,12 +1172,10 @@ __device__ __forceinline__ void parse_window_seg(Smem &s, Ctx &c, int32_t wbase,
     } else {
         // first chain position >= wend inside the span, else the span's exit
         const int32_t d = wend - sp.base - l * SEG;
-        const uint32_t dd = d < 0 ? 0u : (uint32_t)d;
-        const uint64_t m0 = d >= SEG ? 0ull : sp.v0 & from_lo(dd), m1 = d >= SEG ? 0ull : sp.v1 & from_hi(dd);
-        const uint64_t any = __ballot((m0 | m1) != 0ull);
+        const uint32_t bit = sp.v.first_from(d < 0 ? 0u : (uint32_t)d);  // SEG: none
+        const uint64_t any = __ballot(bit < (uint32_t)SEG);
         if (any) {
             const int f = (int)__builtin_ctzll(any);
-            const uint32_t bit = m0 ? (uint32_t)__builtin_ctzll(m0) : 64u + (uint32_t)__builtin_ctzll(m1 | (1ull << 63));
             *efin_out = (uint32_t)sp.base + (uint32_t)(f * SEG) + readlane(bit, f);
         } else {
             *efin_out = sp.exit;
@@ -1200,7 +1203,7 @@ __device__ __forceinline__ void parser_wave(Smem &s, Ctx &c PROF_ARG) {
     int32_t pip = 0;
     bool pstop = false;
     Span sp;
-    sp.v0 = sp.v1 = 0;
+    sp.v.clear();
     sp.base = 0;
     sp.exit = 0;
     bool spv = false;  // sp describes the chain from sp.base
@@ -1228,8 +1231,7 @@ __device__ __forceinline__ void parser_wave(Smem &s, Ctx &c PROF_ARG) {
                     PSTAMP(1);
                     PFIRST(const uint64_t its = pr.acc[11] + pr.acc[13] - it0; pr.acc[22] += 1; pr.acc[23] += its;
                            pr.acc[24] += pr.last; pr.acc[25] += its == 0);
-                    sp.v0 = wk.vt0;
-                    sp.v1 = wk.vt1;
+                    sp.v = wk.vt;
                     sp.base = pip;
                     sp.exit = readlane(wk.ex, 63);
                     spv = true;
@@ -1284,7 +1286,11 @@ __device__ __forceinline__ void parser_wave(Smem &s, Ctx &c PROF_ARG) {
 // whole long token) beyond `want` may be written, never past cap.
 template <bool PREFIX>
 __device__ __forceinline__ void copier_wave(Smem &s, Ctx &c, int32_t *retp, int32_t want PROF_ARG) {
-    __builtin_amdgcn_s_setprio(1);  // the copier is the critical wave of the pair (2 / 3: no better)
+    // Since the walk step waits for one load round the parser is the critical
+    // wave of the pair; the copier keeps the priority it was
+    // tuned with (2 / 3: no better; the parser raised to it for a span
+    // boundary's blocking advance: DESIGN.md 3i).
+    __builtin_amdgcn_s_setprio(1);
     Ser st;
     st.ip = 0;
     st.op = 0;

@@ -1,7 +1,9 @@
 // The step rule of the LZ4 decode kernel's segment-walk parser (SegWalk in
-// lz4_decode.hip) with the byte fetch as a parameter.  Host and device:
-// tests/test_lz4_walkstep.py drives tests/walkstep_main.cc, which runs these
-// walks and a plain ws_next_exact walk over the same bytes.
+// lz4_decode.hip) with the byte fetch as a parameter, and the lanes' bit sets
+// (BitSet<SEG>).  Host and device: tests/test_lz4_walkstep.py drives
+// tests/walkstep_main.cc, tests/test_lz4_walk_seg.py tests/walkseg_main.cc
+// (SEG = 128 and 256), which run these walks and a plain ws_next_exact walk
+// over the same bytes.
 //
 // A step at p needs the token byte and the byte after it (one load round);
 // from them follow the literal length and q, the position of the first
@@ -93,23 +95,77 @@ JFS_WALKSTEP_HD WsRound ws_round(F fetch, int32_t n, int32_t p, uint32_t &pe2) {
     return r;
 }
 
-// 128-bit sets as two u64 (bit d = position plo + d)
-JFS_WALKSTEP_HD bool tbit2(uint64_t a0, uint64_t a1, uint32_t d) {
-    return (((d < 64u ? a0 : a1) >> (d & 63u)) & 1ull) != 0;
+// f(WsIdx<0>), f(WsIdx<1>) ... f(WsIdx<K - 1>): a loop whose index is a constant
+// in every call, so that a word of a bit set is only ever named by a constant
+// index and the set stays in registers.
+template <int I>
+struct WsIdx {
+    static constexpr int v = I;
+};
+template <int K, int I = 0, class Fn>
+JFS_WALKSTEP_HD void ws_each(Fn f) {
+    if constexpr (I < K) {
+        f(WsIdx<I>());
+        ws_each<K, I + 1>(f);
+    }
 }
-JFS_WALKSTEP_HD void sbit2(uint64_t &a0, uint64_t &a1, uint32_t d) {
-    const uint64_t m = 1ull << (d & 63u);
-    a0 |= d < 64u ? m : 0ull;
-    a1 |= d < 64u ? 0ull : m;
-}
-// bit d of the set := on
-JFS_WALKSTEP_HD void pbit2(uint64_t &a0, uint64_t &a1, uint32_t d, bool on) {
-    const uint64_t m = 1ull << (d & 63u);
-    uint64_t &a = d < 64u ? a0 : a1;
-    a = on ? a | m : a & ~m;
-}
-JFS_WALKSTEP_HD uint64_t from_lo(uint32_t d) { return d < 64u ? (~0ull << (d & 63u)) : 0ull; }
-JFS_WALKSTEP_HD uint64_t from_hi(uint32_t d) { return d < 64u ? ~0ull : (~0ull << (d & 63u)); }
+
+// SEG-bit sets as SEG / 64 u64 words (bit d = position plo + d); a bit index
+// picks its word by compares.
+template <int N>
+struct BitSet {
+    static_assert(N > 0 && N % 64 == 0, "whole u64 words");
+    static constexpr int W = N / 64;
+    uint64_t w[W];
+
+    JFS_WALKSTEP_HD void clear() {
+        ws_each<W>([&](auto i) { w[i.v] = 0ull; });
+    }
+    // d >= N reads the last word (callers discard the result)
+    JFS_WALKSTEP_HD bool test(uint32_t d) const {
+        uint64_t a = w[0];
+        ws_each<W>([&](auto i) { a = i.v > 0 && d >= 64u * (uint32_t)i.v ? w[i.v] : a; });
+        return ((a >> (d & 63u)) & 1ull) != 0;
+    }
+    // bit d of the set := on (d < N)
+    JFS_WALKSTEP_HD void put(uint32_t d, bool on) {
+        const uint64_t m = 1ull << (d & 63u);
+        ws_each<W>([&](auto i) {
+            const uint64_t v = on ? w[i.v] | m : w[i.v] & ~m;
+            w[i.v] = (d >> 6) == (uint32_t)i.v ? v : w[i.v];
+        });
+    }
+    // the bits >= d (none for d >= N)
+    static JFS_WALKSTEP_HD BitSet from(uint32_t d) {
+        BitSet r;
+        const uint64_t part = ~0ull << (d & 63u);
+        ws_each<W>([&](auto i) { r.w[i.v] = (d >> 6) < (uint32_t)i.v ? ~0ull : (d >> 6) == (uint32_t)i.v ? part : 0ull; });
+        return r;
+    }
+    JFS_WALKSTEP_HD BitSet and_from(uint32_t d) const {
+        BitSet r = from(d);
+        ws_each<W>([&](auto i) { r.w[i.v] &= w[i.v]; });
+        return r;
+    }
+    JFS_WALKSTEP_HD void or_in(const BitSet &o) {
+        ws_each<W>([&](auto i) { w[i.v] |= o.w[i.v]; });
+    }
+    JFS_WALKSTEP_HD bool any() const {
+        uint64_t a = 0ull;
+        ws_each<W>([&](auto i) { a |= w[i.v]; });
+        return a != 0ull;
+    }
+    // the first set bit >= d, or N
+    JFS_WALKSTEP_HD uint32_t first_from(uint32_t d) const {
+        const BitSet m = and_from(d);
+        uint32_t r = (uint32_t)N;
+        ws_each<W>([&](auto i) {  // from the last word down
+            constexpr int k = W - 1 - i.v;
+            r = m.w[k] ? 64u * (uint32_t)k + (uint32_t)__builtin_ctzll(m.w[k] | (1ull << 63)) : r;
+        });
+        return r;
+    }
+};
 
 // What one iteration of a lane did (for the event counts of the profiling build).
 enum { WS_STEPPED = 0, WS_REDONE = 1, WS_ARRIVED = 2 };
@@ -129,13 +185,13 @@ JFS_WALKSTEP_HD uint32_t ws_take(W &w, uint32_t &pp, const WsRound &r, F fetch, 
 }
 
 // One iteration of a speculative walk (phase 0 of SegWalk::advance) for a
-// moving lane.  W: q, plo, phi, sx, vs0, vs1, mv and the deferred state pe2
-// (the byte of the owed e2 test), pend; the step that owes the test is kept in
-// sx, which means nothing else while the lane moves.  A lane that owes a test
-// keeps moving, past phi as well, until the test is made: sx is the exit once
-// a settled step leaves.
-template <class W, class F, class X>
-JFS_WALKSTEP_HD int ws_spec_iter(W &w, F fetch, X exact, int32_t n) {
+// moving lane.  W: q, plo, phi, sx, mv and the deferred state pe2 (the byte of
+// the owed e2 test), pend; vs: the lane's speculative chain positions; the step
+// that owes the test is kept in sx, which means nothing else while the lane
+// moves.  A lane that owes a test keeps moving, past phi as well, until the
+// test is made: sx is the exit once a settled step leaves.
+template <int N, class W, class F, class X>
+JFS_WALKSTEP_HD int ws_spec_iter(W &w, BitSet<N> &vs, F fetch, X exact, int32_t n) {
     const WsRound r = ws_round(fetch, n, w.q, w.pe2);
     // the step at pp is the exact rule's: the bytes at q are dropped
     const bool redo = w.pend && w.pe2 == 255u;
@@ -147,7 +203,7 @@ JFS_WALKSTEP_HD int ws_spec_iter(W &w, F fetch, X exact, int32_t n) {
     else x = ws_take(w, w.sx, r, fetch, n, &ex);
     if (ex) x = exact(at);
     const bool stop = (x & WS_STOP) != 0;
-    if (!arr && at >= w.plo) pbit2(w.vs0, w.vs1, (uint32_t)(at - w.plo), !stop);
+    if (!arr && at >= w.plo) vs.put((uint32_t)(at - w.plo), !stop);
     const bool out = stop || (!w.pend && (int32_t)x >= w.phi);
     w.sx = out ? x : w.sx;
     w.mv = !out;
@@ -157,32 +213,66 @@ JFS_WALKSTEP_HD int ws_spec_iter(W &w, F fetch, X exact, int32_t n) {
 
 // One iteration of a fix-up walk (phase 1) for a moving lane: the walk ends
 // where it joins the speculative chain vs, stops or leaves the segment.  W as
-// above and vp0, vp1, vt0, vt1, ex; here ex keeps the step that owes the test
-// while the lane moves (sx is the speculative exit a joining walk takes).
-template <class W, class F, class X>
-JFS_WALKSTEP_HD int ws_fix_iter(W &w, F fetch, X exact, int32_t n) {
+// above and ex; here ex keeps the step that owes the test while the lane moves
+// (sx is the speculative exit a joining walk takes).  vt, the lane's true
+// chain positions, takes the walk's positions directly: the caller clears it
+// when the walk starts (nothing reads a walking lane's vt), a join ORs the
+// speculative chain's suffix in.
+template <int N, class W, class F, class X>
+JFS_WALKSTEP_HD int ws_fix_iter(W &w, const BitSet<N> &vs, BitSet<N> &vt, F fetch, X exact, int32_t n) {
     const WsRound r = ws_round(fetch, n, w.q, w.pe2);
     const bool redo = w.pend && w.pe2 == 255u;
     const bool arr = w.pend && !redo && w.q >= w.phi;
     const int32_t at = redo ? (int32_t)w.ex : w.q;
     const uint32_t d = (uint32_t)(at - w.plo);
-    const bool join = !redo && !arr && tbit2(w.vs0, w.vs1, d);
+    const bool join = !redo && !arr && vs.test(d);
     uint32_t x = (uint32_t)w.q;
     bool ex = redo;
     if (redo || arr || join) w.pend = false;
     else x = ws_take(w, w.ex, r, fetch, n, &ex);
     if (ex) x = exact(at);
     const bool stop = (x & WS_STOP) != 0;
-    if (!arr && !join) pbit2(w.vp0, w.vp1, d, !stop);
+    if (!arr && !join) vt.put(d, !stop);
+    if (join) vt.or_in(vs.and_from(d));
     const bool out = join || stop || (!w.pend && (int32_t)x >= w.phi);
-    if (out) {
-        w.vt0 = w.vp0 | (join ? w.vs0 & from_lo(d) : 0ull);
-        w.vt1 = w.vp1 | (join ? w.vs1 & from_hi(d) : 0ull);
-        w.ex = join ? w.sx : x;
-    }
+    if (out) w.ex = join ? w.sx : x;
     w.mv = !out;
     w.q = (int32_t)x;
     return redo ? WS_REDONE : arr ? WS_ARRIVED : WS_STEPPED;
+}
+
+// The two-word form of a 128-bit set and of the two iterations, for a W that
+// keeps its sets as vs0, vs1 / vt0, vt1 (tests/walkstep_main.cc).
+JFS_WALKSTEP_HD BitSet<128> ws_set2(uint64_t a0, uint64_t a1) {
+    BitSet<128> s;
+    s.w[0] = a0;
+    s.w[1] = a1;
+    return s;
+}
+JFS_WALKSTEP_HD bool tbit2(uint64_t a0, uint64_t a1, uint32_t d) { return ws_set2(a0, a1).test(d); }
+JFS_WALKSTEP_HD void sbit2(uint64_t &a0, uint64_t &a1, uint32_t d) {
+    BitSet<128> s = ws_set2(a0, a1);
+    s.put(d, true);
+    a0 = s.w[0];
+    a1 = s.w[1];
+}
+JFS_WALKSTEP_HD uint64_t from_lo(uint32_t d) { return BitSet<128>::from(d).w[0]; }
+JFS_WALKSTEP_HD uint64_t from_hi(uint32_t d) { return BitSet<128>::from(d).w[1]; }
+template <class W, class F, class X>
+JFS_WALKSTEP_HD int ws_spec_iter(W &w, F fetch, X exact, int32_t n) {
+    BitSet<128> vs = ws_set2(w.vs0, w.vs1);
+    const int kind = ws_spec_iter(w, vs, fetch, exact, n);
+    w.vs0 = vs.w[0];
+    w.vs1 = vs.w[1];
+    return kind;
+}
+template <class W, class F, class X>
+JFS_WALKSTEP_HD int ws_fix_iter(W &w, F fetch, X exact, int32_t n) {
+    BitSet<128> vt = ws_set2(w.vt0, w.vt1);
+    const int kind = ws_fix_iter(w, ws_set2(w.vs0, w.vs1), vt, fetch, exact, n);
+    w.vt0 = vt.w[0];
+    w.vt1 = vt.w[1];
+    return kind;
 }
 
 }  // namespace lz4d
