@@ -381,6 +381,116 @@ int64_t jfs_zstd_compress_seekable_device(const jfs_dev_block *d_blocks, int nbl
 int64_t jfs_zstd_decompress_range_device(const jfs_dev_block *d_blocks, const int32_t *d_lo, const int32_t *d_hi,
                                          int nblk, int32_t *d_ret, void *stream);
 
+/* XXH64 of device-resident pieces (the per-frame checksum of the Zstandard
+ * seekable format is its low 32 bits).
+ * d_hash[i] = XXH64(src[0, src_len), seed 0).  src_len == 0 gives
+ * 0xEF46DB3751D8E999 (src may be NULL).  d_ret (may be NULL): 0, or -1 for a bad
+ * descriptor (src_len < 0, NULL src with src_len > 0; d_hash[i] is then 0).
+ * dst / dst_cap are ignored.  Reads no byte outside src[0, src_len); src may
+ * have any alignment.  Asynchronous on `stream`. */
+int64_t jfs_xxh64_device(const jfs_dev_block *d_blocks, int nblk, uint64_t *d_hash, int32_t *d_ret, void *stream);
+
+/* Checksummed seekable Zstd encode: the contract and calling rules of
+ * jfs_zstd_compress_seekable_device.  src_len <= 131072 gives that call's
+ * bytes, with no table (one frame needs no seek, and the object CRC covers
+ * it).  A longer input gives the same nb frames, byte for byte, and then the
+ * table with per-frame checksums of the Zstandard seekable format:
+ *     u32 0x184D2A5E | u32 12 nb + 9 | nb x (u32 compressed size of the frame,
+ *     u32 decompressed size, u32 low 32 bits of XXH64 (seed 0) of the frame's
+ *     content) | u32 nb | u8 0x80 | u32 0x8F92EAB1
+ * so ret is the seekable call's ret + 4 nb, exactly; the worst case n + 25 nb
+ * + 17 stays within jfs_compress_bound(ZSTD, n).  jfs_zstd_decompress_range_device
+ * and the JFS_READ_SEEK reads take such a table for no table and decode the
+ * object as any other; jfs_zstd_decompress_frames_device reads it.  Does not
+ * consult jfs_zstd_parse_mode or jfs_zstd_seek_csum_mode. */
+int64_t jfs_zstd_compress_seekable_csum_device(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, void *stream);
+
+/* Planning a ranged GET of a seekable object (host only; needs no device).
+ * tail = the last tail_len bytes of an object of object_len bytes (object_len
+ * <= 0x7FFFFFFF); [lo, hi) = the content range wanted.  A valid table is the
+ * one jfs_zstd_decompress_range_device describes, with descriptor byte 0x00
+ * (entries of 8 bytes) or 0x80 (entries of 12 bytes, the third word a
+ * checksum), read as a table that stands alone: its bytes run from the
+ * skippable magic through the footer.  The 9-byte footer is enough to answer
+ * JFS_SEEK_PLAN_MORE with the table's position; a footer that is not one, or a
+ * table that fails any check, answers JFS_SEEK_PLAN_NONE.  The selection is the
+ * range call's with lo' = max(lo, 0) and hi' = min(hi, D).  Returns JFS_OK and
+ * fills *out, or JFS_ERR_INVALID (NULL, negative sizes, tail_len > object_len,
+ * object_len > 0x7FFFFFFF). */
+#define JFS_SEEK_PLAN_OK 0   /* fetch [get_off, get_off + get_len) of the object */
+#define JFS_SEEK_PLAN_MORE 1 /* the table is longer than `tail`: fetch [table_off, table_off + table_len) and call again */
+#define JFS_SEEK_PLAN_NONE 2 /* no valid table: fetch the whole object, use the ordinary calls */
+typedef struct jfs_seek_plan {
+    int32_t status, checksums;    /* checksums: 1 for a 12-byte table */
+    int32_t nf, first, count;     /* frames; the selected ones (count 0: the range meets none, get_len 0) */
+    int32_t reserved;
+    int64_t table_off, table_len; /* where the table lies in the object */
+    int64_t get_off, get_len;     /* the selected frames' bytes */
+    int64_t content;              /* D */
+    int64_t first_off;            /* content offset of frame `first` */
+} jfs_seek_plan;
+int64_t jfs_zstd_seek_plan(const uint8_t *tail, int64_t tail_len, int64_t object_len, int64_t lo, int64_t hi,
+                           jfs_seek_plan *out);
+
+/* Decoding a fragment of a seekable object, verified: input i holds the
+ * object's table and the bytes [frag_off, frag_off + frag_len) of the object
+ * (what jfs_zstd_seek_plan says to fetch), and is decoded for its content bytes
+ * [d_lo[i], d_hi[i]).  Let lo' = max(lo, 0), hi' = min(hi, dst_cap).  ret[i],
+ * in this order of precedence:
+ *   NULL table, frag or dst, or a negative size: -1.
+ *   The table is not valid (as for jfs_zstd_seek_plan; there is no whole object
+ *     to fall back on): -1.
+ *   dst_cap == 0 or hi' <= lo': 0, nothing written.
+ *   D > dst_cap: -2.
+ *   A selected frame whose bytes do not lie inside the fragment: -3.
+ *   Otherwise the selected frames are decoded exactly as
+ *     jfs_zstd_decompress_range_device decodes them, each into dst[D_k, D_k+1).
+ *     A frame that does not return its table size: -1.  Else, with a 12-byte
+ *     table, a frame whose content's XXH64 low word differs from its entry: -4
+ *     (only this call returns it).  Else min(D, hi').
+ * Nothing outside dst[flo, fhi) is written.  With frag the whole object,
+ * frag_off = 0 and table pointing into it, this is the verified range decode of
+ * a resident object.  Stream behaviour and scratch are the range call's (one
+ * host wait for the number of selected frames; the per-device lock is held
+ * across the waits). */
+typedef struct jfs_seek_frag {
+    const uint8_t *table; int32_t table_len; int32_t object_len; /* the stand-alone table, device memory */
+    const uint8_t *frag;  int32_t frag_off;  int32_t frag_len;   /* bytes [frag_off, frag_off + frag_len) of the object */
+    uint8_t *dst;         int32_t dst_cap;   int32_t reserved;   /* dst[k] = content byte k, as for the range call */
+} jfs_seek_frag;
+int64_t jfs_zstd_decompress_frames_device(const jfs_seek_frag *d_frags, const int32_t *d_lo, const int32_t *d_hi,
+                                          int nblk, int32_t *d_ret, void *stream);
+
+/* The same from host buffers: what a loadRange adapter calls after
+ * jfs_zstd_seek_plan and the ranged GET.  Read i holds the object's table and
+ * the fragment [frag_off, frag_off + frag_len) of the object, and asks for the
+ * content bytes [lo, hi).  Let lo' = max(lo, 0), hi' = min(hi, block_size).
+ * out_n[i] = the bytes written to dst, min(D, hi') - lo' (0 when that is not
+ * positive), which are content [lo', min(D, hi')); or JFS_ERR_CORRUPT (the
+ * table is not valid, a frame does not decode to its table size, or a selected
+ * frame lies outside the fragment: the device call's -1 and -3),
+ * JFS_ERR_SHORT_BUFFER (D > block_size, the device call's -2; or dst_cap below
+ * the bytes to write), JFS_ERR_CHECKSUM (-4).  Nothing is written to dst for a
+ * failed read.  Only tables and fragments cross the link upwards (a table that
+ * several reads share, by pointer and length, once) and only the requested
+ * bytes come down; the decoded blocks of block_size bytes are device scratch.
+ * Returns JFS_ERR_INVALID before anything else (n < 0, NULL arrays, a NULL
+ * table, a NULL frag with frag_len > 0, a NULL dst with dst_cap > 0, a negative
+ * size, or table_len, object_len, frag_off, frag_len or block_size beyond
+ * int32), then JFS_ERR_NO_DEVICE, else JFS_OK with every out_n[i] set.  One
+ * device of device_mask runs the call, the caller's current device is
+ * unchanged on return, a read whose staging or scratch cannot be allocated
+ * reports JFS_ERR_NO_MEMORY, a HIP failure JFS_ERR_HIP; jfs_stats counts the
+ * call under (Zstd, decompress), bytes_in = table + fragment. */
+typedef struct jfs_range_read {
+    const uint8_t *table; int64_t table_len; int64_t object_len;
+    const uint8_t *frag;  int64_t frag_off;  int64_t frag_len;
+    int64_t lo, hi;       /* content range asked for */
+    int64_t block_size;   /* capacity of the decoded block (device scratch; never crosses the link) */
+    uint8_t *dst; int64_t dst_cap; /* receives content [lo', min(D, hi')); needs hi' - lo' bytes at most */
+} jfs_range_read;
+int64_t jfs_zstd_load_range_batch(int n, const jfs_range_read *r, int64_t *out_n, uint32_t device_mask);
+
 /* CRC-32C (Castagnoli) of device-resident blocks.
  * d_blocks[i].src / src_len: the data.  d_crc[i] (if d_crc != NULL) receives
  * crc32.Update(0, crc32c, data), the object checksum of
@@ -772,6 +882,21 @@ int jfs_set_zstd_parse_mode(int mode);
  * introduced with and keeps answering -1 for any other value;
  * jfs_set_zstd_parse_mode_ext is the same call for all three modes. */
 int jfs_set_zstd_parse_mode_ext(int mode);
+/* Checksum switch of the seekable mode.  JFS_ZSTD_SEEK_CSUM_OFF (default):
+ * nothing changes.  JFS_ZSTD_SEEK_CSUM_ON: while the Zstd parse mode is
+ * JFS_ZSTD_PARSE_SEEKABLE, every host-buffer compress call (jfs_compress, the
+ * batch calls and their _crc and _mixed forms, jfs_compress_seal_batch, the
+ * encode step of the compaction calls) writes the objects of
+ * jfs_zstd_compress_seekable_csum_device; in any other parse mode the switch
+ * has no effect.  The initial value is read once from JFS_ZSTD_SEEK_CSUM =
+ * "off" | "on" (case-insensitive; anything else, or unset: off).
+ * jfs_set_zstd_seek_csum_mode returns the previous value, or -1 for an unknown
+ * one (which changes nothing); it is atomic and applies to calls that start
+ * afterwards. */
+#define JFS_ZSTD_SEEK_CSUM_OFF 0
+#define JFS_ZSTD_SEEK_CSUM_ON 1
+int jfs_zstd_seek_csum_mode(void);
+int jfs_set_zstd_seek_csum_mode(int mode);
 
 /* Per-codec counters (the data behind cachedStore's object_request_data_bytes
  * and block-size metrics, cached_store.go:931-974).  Index algo * 2 + dir,

@@ -51,6 +51,9 @@ EXPORTS = [
     "jfs_test_set_split_jump_rounds",
     "jfs_zstd_compress_seekable_device", "jfs_zstd_decompress_range_device", "jfs_set_zstd_parse_mode_ext",
     "jfs_read_seek_mode", "jfs_set_read_seek_mode",
+    "jfs_xxh64_device", "jfs_zstd_compress_seekable_csum_device", "jfs_zstd_seek_csum_mode",
+    "jfs_set_zstd_seek_csum_mode", "jfs_zstd_seek_plan", "jfs_zstd_decompress_frames_device",
+    "jfs_zstd_load_range_batch",
 ]
 # the hook include/jfs_gpucodec_lz4_fast_test.h declares (the fast LZ4 encoder's host twin)
 LZ4_FAST_TEST_EXPORTS = ["jfs_test_lz4_fast_host"]
@@ -61,6 +64,8 @@ MODE_OFF, MODE_AUTO, MODE_FORCE = 0, 1, 2
 LZ4_PARSE_EXACT, LZ4_PARSE_FAST = 0, 1
 ZSTD_PARSE_EXACT, ZSTD_PARSE_FAST, ZSTD_PARSE_SEEKABLE = 0, 1, 2
 READ_SEEK_OFF, READ_SEEK_ON = 0, 1
+ZSTD_SEEK_CSUM_OFF, ZSTD_SEEK_CSUM_ON = 0, 1
+SEEK_PLAN_OK, SEEK_PLAN_MORE, SEEK_PLAN_NONE = 0, 1, 2
 READ_DECODE_FULL, READ_DECODE_PREFIX, READ_DECODE_PREFIX_ALL = 0, 1, 2
 CIPHER_AES256GCM, CIPHER_CHACHA20POLY1305, CIPHER_SM4GCM = 0, 1, 2
 STATS_N = 6  # index algo * 2 + dir (0 compress, 1 decompress)
@@ -89,6 +94,24 @@ class JfsSealParam(ctypes.Structure):
 class JfsDevBlock(ctypes.Structure):
     _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p),
                 ("src_len", ctypes.c_int32), ("dst_cap", ctypes.c_int32)]
+
+
+class JfsSeekFrag(ctypes.Structure):
+    _fields_ = [("table", ctypes.c_void_p), ("table_len", ctypes.c_int32), ("object_len", ctypes.c_int32),
+                ("frag", ctypes.c_void_p), ("frag_off", ctypes.c_int32), ("frag_len", ctypes.c_int32),
+                ("dst", ctypes.c_void_p), ("dst_cap", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class JfsRangeRead(ctypes.Structure):
+    _fields_ = [("table", ctypes.c_void_p), ("table_len", ctypes.c_int64), ("object_len", ctypes.c_int64),
+                ("frag", ctypes.c_void_p), ("frag_off", ctypes.c_int64), ("frag_len", ctypes.c_int64),
+                ("lo", ctypes.c_int64), ("hi", ctypes.c_int64), ("block_size", ctypes.c_int64),
+                ("dst", ctypes.c_void_p), ("dst_cap", ctypes.c_int64)]
+
+
+class JfsSeekPlan(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("status", "checksums", "nf", "first", "count", "reserved")] + [
+        (n, ctypes.c_int64) for n in ("table_off", "table_len", "get_off", "get_len", "content", "first_off")]
 
 
 class JfsCompactSeg(ctypes.Structure):
@@ -144,6 +167,20 @@ def load() -> ctypes.CDLL:
     lib.jfs_read_seek_mode.restype = ctypes.c_int
     lib.jfs_set_read_seek_mode.argtypes = [ctypes.c_int]
     lib.jfs_set_read_seek_mode.restype = ctypes.c_int
+    lib.jfs_xxh64_device.argtypes = [vp, ctypes.c_int, vp, vp, vp]
+    lib.jfs_xxh64_device.restype = i64
+    lib.jfs_zstd_compress_seekable_csum_device.argtypes = [vp, ctypes.c_int, vp, vp]
+    lib.jfs_zstd_compress_seekable_csum_device.restype = i64
+    lib.jfs_zstd_decompress_frames_device.argtypes = [vp, vp, vp, ctypes.c_int, vp, vp]
+    lib.jfs_zstd_decompress_frames_device.restype = i64
+    lib.jfs_zstd_seek_plan.argtypes = [vp, i64, i64, i64, i64, ctypes.POINTER(JfsSeekPlan)]
+    lib.jfs_zstd_seek_plan.restype = i64
+    lib.jfs_zstd_load_range_batch.argtypes = [ctypes.c_int, ctypes.POINTER(JfsRangeRead), ctypes.POINTER(i64), u32]
+    lib.jfs_zstd_load_range_batch.restype = i64
+    lib.jfs_zstd_seek_csum_mode.argtypes = []
+    lib.jfs_zstd_seek_csum_mode.restype = ctypes.c_int
+    lib.jfs_set_zstd_seek_csum_mode.argtypes = [ctypes.c_int]
+    lib.jfs_set_zstd_seek_csum_mode.restype = ctypes.c_int
     lib.jfs_set_zstd_parse_mode_ext.argtypes = [ctypes.c_int]
     lib.jfs_set_zstd_parse_mode_ext.restype = ctypes.c_int
     lib.jfs_read_decode_mode.argtypes = []

@@ -218,6 +218,35 @@ class ZStandard(Compressor):
     def __init__(self, level: int = ZSTD_LEVEL):
         self.level = level
 
+    def LoadRangeBatch(self, reads, device_mask: int = 0):
+        """jfs_zstd_load_range_batch: reads = [(dst, table, object_len, frag,
+        frag_off, lo, hi, block_size)], the table and the fragment of a seekable
+        object as seek_plan says to fetch them; dst receives the content bytes
+        [max(lo, 0), min(D, hi, block_size)).  Returns [(n, err)] per read; only
+        tables and fragments go to the GPU and only those bytes come back."""
+        n = len(reads)
+        arr = (L.JfsRangeRead * max(n, 1))()
+        keep = []
+        for i, (dst, table, object_len, frag, frag_off, lo, hi, block_size) in enumerate(reads):
+            dp, dn, k0 = _addr(dst, True)
+            tp, tn, k1 = _addr(table, False)
+            fp, fn, k2 = _addr(frag, False)
+            keep.append((k0, k1, k2))
+            arr[i] = L.JfsRangeRead(tp, tn, object_len, fp, frag_off, fn, lo, hi, block_size, dp, dn)
+        out = (ctypes.c_int64 * max(n, 1))()
+        rc = L.load().jfs_zstd_load_range_batch(n, arr, out, device_mask)
+        if rc != 0:
+            raise _err(rc, 0, 0, "LoadRangeBatch")
+        res = []
+        for i in range(n):
+            if out[i] >= 0:
+                res.append((int(out[i]), None))
+            elif out[i] == L.JFS_ERR_CHECKSUM:
+                res.append((0, CompressError("zstd: a frame's content does not match its seek-table checksum", out[i])))
+            else:
+                res.append((0, _err(out[i], len(reads[i][0]), reads[i][6] - max(reads[i][5], 0), "LoadRangeBatch")))
+        return res
+
 
 class LZ4(Compressor):
     """compress.go:105-125"""
@@ -334,6 +363,43 @@ def set_read_seek_mode(mode: str) -> str:
         raise ValueError(f"read seek mode {mode!r}: expected 'off' or 'on'")
     prev = L.load().jfs_set_read_seek_mode(_READ_SEEK[mode])
     return next(k for k, v in _READ_SEEK.items() if v == prev)
+
+
+_SEEK_CSUM = {"off": L.ZSTD_SEEK_CSUM_OFF, "on": L.ZSTD_SEEK_CSUM_ON}
+_PLAN_STATUS = {L.SEEK_PLAN_OK: "ok", L.SEEK_PLAN_MORE: "more", L.SEEK_PLAN_NONE: "none"}
+
+
+def zstd_seek_csum_mode() -> str:
+    """The checksum switch of the seekable parse mode (jfs_zstd_seek_csum_mode):
+    "off", or "on" -- while the Zstd parse mode is "seekable" the compress calls
+    write seek tables with a checksum per frame."""
+    m = L.load().jfs_zstd_seek_csum_mode()
+    return next(k for k, v in _SEEK_CSUM.items() if v == m)
+
+
+def set_zstd_seek_csum_mode(mode: str) -> str:
+    """Set it (process-wide, for calls that start afterwards) and return the
+    previous value's name."""
+    if mode not in _SEEK_CSUM:
+        raise ValueError(f"zstd seek checksum mode {mode!r}: expected 'off' or 'on'")
+    prev = L.load().jfs_set_zstd_seek_csum_mode(_SEEK_CSUM[mode])
+    return next(k for k, v in _SEEK_CSUM.items() if v == prev)
+
+
+def seek_plan(tail: bytes, object_len: int, lo: int, hi: int) -> dict:
+    """jfs_zstd_seek_plan: from the last len(tail) bytes of a stored object, what
+    to fetch for its content bytes [lo, hi).  Returns the plan's fields, with
+    status "ok" (fetch [get_off, get_off + get_len)), "more" (fetch the table at
+    [table_off, table_off + table_len) and ask again) or "none" (no table: fetch
+    the object).  Needs no device."""
+    p = L.JfsSeekPlan()
+    buf = (ctypes.c_char * max(1, len(tail))).from_buffer_copy(bytes(tail) or b"\0")
+    rc = L.load().jfs_zstd_seek_plan(ctypes.cast(buf, ctypes.c_void_p), len(tail), object_len, lo, hi, ctypes.byref(p))
+    if rc != 0:
+        raise ValueError(f"jfs_zstd_seek_plan: {rc}")
+    d = {n: getattr(p, n) for n, _ in L.JfsSeekPlan._fields_ if n != "reserved"}
+    d["status"] = _PLAN_STATUS[p.status]
+    return d
 
 
 def zstd_fast_seqs(src, device_ptr: int | None = None):

@@ -36,6 +36,7 @@
 #include "blockgen.h"
 #include "chain_plan.h"
 #include "jfs_internal.h"
+#include "zstd_seek.h"
 
 #define JFS_VERSION "jfs-gpucodec 0.1.0 (gfx950)"
 
@@ -338,6 +339,27 @@ std::atomic<int> &zstd_parse() {
     return m;
 }
 inline int zstd_parse_now() { return zstd_parse().load(std::memory_order_relaxed); }
+
+// JFS_ZSTD_SEEK_CSUM (include/jfs_gpucodec.h): off (default) | on
+std::atomic<int> &zstd_seek_csum() {
+    static std::atomic<int> m{[] {
+        const char *e = getenv("JFS_ZSTD_SEEK_CSUM");
+        if (!e) return JFS_ZSTD_SEEK_CSUM_OFF;
+        std::string v(e);
+        for (auto &ch : v) ch = (char)tolower((unsigned char)ch);
+        return v == "on" ? JFS_ZSTD_SEEK_CSUM_ON : JFS_ZSTD_SEEK_CSUM_OFF;
+    }()};
+    return m;
+}
+// What a host-buffer compress call encodes with: the parse mode, or this value
+// (no parse mode of the public switch) for seekable objects with checksums.
+constexpr int ZSTD_ENCODE_SEEK_CSUM = 3;
+inline int zstd_encode_now() {
+    const int p = zstd_parse_now();
+    return p == JFS_ZSTD_PARSE_SEEKABLE && zstd_seek_csum().load(std::memory_order_relaxed) == JFS_ZSTD_SEEK_CSUM_ON
+               ? ZSTD_ENCODE_SEEK_CSUM
+               : p;
+}
 
 // JFS_GPU_DEVICES: "all" (default), a comma list of ordinals, or a 0x mask
 uint64_t device_select_mask() {
@@ -746,7 +768,9 @@ int launch_kernel(int algo, int dir, const jfs_dev_block *d_desc, int nblk, int3
     if (algo == JFS_ALGO_LZ4 && dir == DECOMPRESS) return jfs_launch_lz4_decode(d_desc, nblk, d_ret, st);
     if (algo == JFS_ALGO_LZ4 && dir == COMPRESS) return jfs_launch_lz4_encode(d_desc, nblk, d_ret, st);
     if (algo == JFS_ALGO_ZSTD && dir == DECOMPRESS) return jfs_launch_zstd_decode(d_desc, nblk, d_ret, nullptr, st);
-    if (algo == JFS_ALGO_ZSTD && dir == COMPRESS) return jfs_launch_zstd_encode(d_desc, nblk, d_ret, st, zparse);
+    if (algo == JFS_ALGO_ZSTD && dir == COMPRESS)
+        return zparse == ZSTD_ENCODE_SEEK_CSUM ? jfs_launch_zstd_encode_seek_csum(d_desc, nblk, d_ret, st)
+                                               : jfs_launch_zstd_encode(d_desc, nblk, d_ret, st, zparse);
     return -1;
 }
 
@@ -901,7 +925,7 @@ struct BatchRun {
         : dev(dev), ln(ln), other(dev->lane[(&ln - dev->lane + 1) % NLANE]), algo(algo), dir(dir), iov(iov), out(out),
           ae(ae), crc_out(crc_out), csum_out(dir == DECOMPRESS ? csum : nullptr),
           zplan(algo == JFS_ALGO_ZSTD && dir == DECOMPRESS && !ae), zib(zplan ? (int64_t)jfs_zstd_info_bytes() : 0),
-          lz4_fast(lz4_fast_mode()), zparse(zstd_parse_now()), blk(nblk) {
+          lz4_fast(lz4_fast_mode()), zparse(zstd_encode_now()), blk(nblk) {
         for (int i = 0; i < nblk; i++) blk[i] = {iov[i].src_len, ae ? iov[i].dst_cap : staged_cap(algo, dir, iov[i])};
         const int64_t limit =
             (algo == JFS_ALGO_LZ4 || algo == JFS_ALGO_ZSTD) && dir == COMPRESS && !ae ? chunk_limit_lz4c()
@@ -2069,7 +2093,7 @@ int64_t compact_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *
     if (lk == 0) lk = gather(0);
     if (lk == 0 && codec && no > 0) {
         lk = c.lz4 ? (launch_lz4_encode(*c.s1, h_enc, d_enc, no, d_ret, ks, fast) == JFS_OK ? 0 : -1)
-                   : launch_kernel(algo, COMPRESS, d_enc, no, d_ret, ks, zstd_parse_now());
+                   : launch_kernel(algo, COMPRESS, d_enc, no, d_ret, ks, zstd_encode_now());
         // the encoder ran on every block: a failed gather's verdict replaces its result
         if (lk == 0) lk = gather(1);
     }
@@ -2844,6 +2868,78 @@ int64_t jfs_zstd_decompress_range_device(const jfs_dev_block *d_blocks, const in
                                                                                                      : JFS_ERR_HIP;
 }
 
+int jfs_zstd_seek_csum_mode(void) { return zstd_seek_csum().load(std::memory_order_relaxed); }
+
+int jfs_set_zstd_seek_csum_mode(int mode) {
+    if (mode != JFS_ZSTD_SEEK_CSUM_OFF && mode != JFS_ZSTD_SEEK_CSUM_ON) return -1;
+    return zstd_seek_csum().exchange(mode);
+}
+
+int64_t jfs_xxh64_device(const jfs_dev_block *d_blocks, int nblk, uint64_t *d_hash, int32_t *d_ret, void *stream) {
+    if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
+    if (nblk < 0 || (nblk > 0 && (!d_blocks || !d_hash))) return JFS_ERR_INVALID;
+    return jfs_launch_xxh64(d_blocks, nblk, d_hash, d_ret, (hipStream_t)stream) == 0 ? JFS_OK : JFS_ERR_HIP;
+}
+
+int64_t jfs_zstd_compress_seekable_csum_device(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, void *stream) {
+    if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
+    // (the descriptors are copied back to the host from the pointer given)
+    if (nblk < 0 || (nblk > 0 && (!d_blocks || !d_ret))) return JFS_ERR_INVALID;
+    stat_launch(JFS_ALGO_ZSTD, COMPRESS, nblk);
+    return jfs_launch_zstd_encode_seek_csum(d_blocks, nblk, d_ret, (hipStream_t)stream) == 0 ? JFS_OK : JFS_ERR_HIP;
+}
+
+int64_t jfs_zstd_decompress_frames_device(const jfs_seek_frag *d_frags, const int32_t *d_lo, const int32_t *d_hi,
+                                          int nblk, int32_t *d_ret, void *stream) {
+    if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
+    if (nblk > 0 && (!d_frags || !d_lo || !d_hi || !d_ret)) return JFS_ERR_INVALID;
+    stat_launch(JFS_ALGO_ZSTD, DECOMPRESS, nblk);
+    return jfs_launch_zstd_decode_frames(d_frags, d_lo, d_hi, nblk, d_ret, (hipStream_t)stream) == 0 ? JFS_OK
+                                                                                                     : JFS_ERR_HIP;
+}
+
+int64_t jfs_zstd_seek_plan(const uint8_t *tail, int64_t tail_len, int64_t object_len, int64_t lo, int64_t hi,
+                           jfs_seek_plan *out) {
+    namespace zs = jfs::zseek;
+    if (!out || tail_len < 0 || object_len < 0 || tail_len > object_len || object_len > 0x7FFFFFFFll ||
+        (!tail && tail_len > 0))
+        return JFS_ERR_INVALID;
+    memset(out, 0, sizeof(*out));
+    out->status = JFS_SEEK_PLAN_NONE;
+    if (tail_len < 9) return JFS_OK;
+    // the footer: the frame count and the entry size place the table
+    const uint8_t *f = tail + tail_len - 9;
+    const auto ffetch = [f](int32_t p) { return (uint32_t)f[p]; };
+    if (zs::le32(ffetch, 5) != zs::SEEK_MAGIC || (f[4] != 0u && f[4] != zs::DESC_CSUM)) return JFS_OK;
+    const uint32_t n = zs::le32(ffetch, 0);
+    const int64_t entry = f[4] ? zs::ENTRY_CSUM : zs::ENTRY;
+    if (n < 1u || n > (uint32_t)zs::MAX_FRAMES || entry * n + zs::TABLE_FIXED > object_len) return JFS_OK;
+    const int64_t table_len = entry * n + zs::TABLE_FIXED;
+    if (tail_len < table_len) {
+        out->status = JFS_SEEK_PLAN_MORE;
+        out->checksums = f[4] != 0u;
+        out->nf = (int32_t)n;
+        out->table_off = object_len - table_len;
+        out->table_len = table_len;
+        return JFS_OK;
+    }
+    const uint8_t *t = tail + tail_len - table_len;
+    const zs::TableSel s = zs::table_select([t](int32_t p) { return (uint32_t)t[p]; }, table_len, object_len, -1, lo, hi);
+    if (!s.table) return JFS_OK;
+    out->status = JFS_SEEK_PLAN_OK;
+    out->checksums = s.checksums;
+    out->nf = s.nf;
+    out->first = s.first;
+    out->count = s.count;
+    out->table_off = object_len - table_len;
+    out->table_len = table_len;
+    out->get_off = (int64_t)s.coff;
+    out->get_len = (int64_t)(s.cend - s.coff);
+    out->content = (int64_t)s.total;
+    out->first_off = (int64_t)s.doff;
+    return JFS_OK;
+}
+
 int jfs_set_zstd_parse_mode(int mode) {
     if (mode != JFS_ZSTD_PARSE_EXACT && mode != JFS_ZSTD_PARSE_FAST) return -1;
     return zstd_parse().exchange(mode);
@@ -3178,6 +3274,120 @@ int64_t jfs_read_open_batch_csum(int algo, int cipher, int nsrc, const jfs_iov *
     if (cipher < 0 || (nout > 0 && !csum)) return JFS_ERR_INVALID;
     return read_call(algo, cipher, nsrc, src, src_keys, src_crc, nout, out, seg_first, seg, src_n, out_n, crc_got,
                      device_mask, csum);
+}
+
+// Ranged reads from host buffers: the host answers what the table
+// alone decides; the rest run on one lane, on the read calls' staging -- slot
+// 0's pinned and device buffers for what crosses the link (descriptors, tables,
+// fragments up in one copy; results and the requested bytes down in one), its
+// scratch for the decoded blocks.
+int64_t jfs_zstd_load_range_batch(int n, const jfs_range_read *r, int64_t *out_n, uint32_t device_mask) {
+    namespace zs = jfs::zseek;
+    if (n < 0 || (n > 0 && (!r || !out_n))) return JFS_ERR_INVALID;
+    for (int i = 0; i < n; i++) {
+        const jfs_range_read &v = r[i];
+        if (!v.table || v.table_len < 0 || v.object_len < 0 || v.frag_off < 0 || v.frag_len < 0 || v.block_size < 0 ||
+            v.dst_cap < 0 || v.table_len > INT32_MAX || v.object_len > INT32_MAX || v.frag_off > INT32_MAX ||
+            v.frag_len > INT32_MAX || v.block_size > INT32_MAX || (!v.frag && v.frag_len > 0) || (!v.dst && v.dst_cap > 0))
+            return JFS_ERR_INVALID;
+    }
+    const std::vector<DevCtx *> ds = devices_in(device_mask);
+    if (ds.empty()) return JFS_ERR_NO_DEVICE;
+    const int64_t t0 = steady_ns();
+    struct Job {
+        int idx;
+        int32_t lo, hi, len, expect;
+        int64_t tab, frag, out, blk;  // offsets: staged table and fragment, packed output, decoded block
+    };
+    const auto up16 = [](int64_t x) { return (x + 15) & ~15ll; };
+    std::vector<Job> jobs;
+    std::vector<ChainOut> oo;
+    std::vector<std::pair<std::pair<const uint8_t *, int64_t>, int64_t>> tabs;  // a table several reads share goes up once
+    int64_t data = 0, outs = 0, blks = 0;
+    int32_t max_len = 0;
+    for (int i = 0; i < n; i++) {
+        const jfs_range_read &v = r[i];
+        const uint8_t *t = v.table;
+        const zs::TableSel s =
+            zs::table_select([t](int32_t p) { return (uint32_t)t[p]; }, v.table_len, v.object_len, v.block_size, v.lo, v.hi);
+        const int64_t lo = std::max<int64_t>(v.lo, 0), hi = std::min(v.hi, v.block_size);
+        const int64_t top = std::min<int64_t>((int64_t)s.total, hi), len = top > lo ? top - lo : 0;
+        if (!s.table) out_n[i] = JFS_ERR_CORRUPT;
+        else if (v.block_size == 0 || hi <= lo) out_n[i] = 0;
+        else if ((int64_t)s.total > v.block_size || v.dst_cap < len) out_n[i] = JFS_ERR_SHORT_BUFFER;
+        else if (len == 0) out_n[i] = 0;  // the range lies behind the content
+        else {
+            Job j{i, (int32_t)lo, (int32_t)hi, (int32_t)len, (int32_t)top, -1, 0, outs, blks};
+            for (const auto &e : tabs)
+                if (e.first.first == v.table && e.first.second == v.table_len) j.tab = e.second;
+            if (j.tab < 0) {
+                j.tab = data;
+                tabs.push_back({{v.table, v.table_len}, data});
+                data += up16(v.table_len);
+            }
+            j.frag = data;
+            data += up16(v.frag_len);
+            outs += up16(len);
+            blks += (v.block_size + 255) & ~255ll;
+            max_len = std::max(max_len, (int32_t)len);
+            jobs.push_back(j);
+            oo.push_back({i, len, len, 0, 0});
+        }
+    }
+    const int m = (int)jobs.size();
+    const int64_t o_lo = up16((int64_t)sizeof(jfs_seek_frag) * m), o_hi = o_lo + up16(4ll * m), o_pack = o_hi + up16(4ll * m),
+                  o_data = o_pack + up16((int64_t)sizeof(jfs_range_pack) * m), o_ret = o_data + data,
+                  o_out = o_ret + up16(4ll * m), end = o_out + outs;
+    chain_dispatch(ds, JFS_ALGO_ZSTD, DECOMPRESS, std::vector<ChainSrc>(), oo, out_n, out_n, [&](DevCtx *dev, Lane &ln) {
+        LaneRun scope(dev, ln, JFS_ALGO_ZSTD * 2 + DECOMPRESS, (uint64_t)m);
+        Slot &sl = ln.slot[0];
+        if (!sl.ensure(end) || !sl.ensure_split(std::max<int64_t>(blks, 16))) return (int64_t)JFS_ERR_NO_MEMORY;
+        jfs_seek_frag *h_frag = (jfs_seek_frag *)sl.h;
+        int32_t *h_lo = (int32_t *)(sl.h + o_lo), *h_hi = (int32_t *)(sl.h + o_hi);
+        jfs_range_pack *h_pack = (jfs_range_pack *)(sl.h + o_pack);
+        std::vector<CopyJob> cp;
+        for (const auto &e : tabs) cp.push_back({sl.h + o_data + e.second, e.first.first, e.first.second});
+        for (int k = 0; k < m; k++) {
+            const Job &j = jobs[k];
+            const jfs_range_read &v = r[j.idx];
+            if (v.frag_len > 0) cp.push_back({sl.h + o_data + j.frag, v.frag, v.frag_len});
+            // (an empty fragment still needs a pointer: its place in the staging)
+            h_frag[k] = jfs_seek_frag{sl.d + o_data + j.tab,  (int32_t)v.table_len, (int32_t)v.object_len,
+                                      sl.d + o_data + j.frag, (int32_t)v.frag_off,  (int32_t)v.frag_len,
+                                      sl.sp + j.blk,          (int32_t)v.block_size, 0};
+            h_lo[k] = j.lo;
+            h_hi[k] = j.hi;
+            h_pack[k] = jfs_range_pack{sl.sp + j.blk + j.lo, sl.d + o_out + j.out, j.len, j.expect};
+        }
+        par_copy(cp);
+        hipStream_t ks = ln.s_k;
+        int32_t *d_ret = (int32_t *)(sl.d + o_ret);
+        int lk = hipMemcpyAsync(sl.d, sl.h, (size_t)o_ret, hipMemcpyHostToDevice, ks) == hipSuccess ? 0 : -1;
+        if (lk == 0)
+            lk = jfs_launch_zstd_decode_frames((const jfs_seek_frag *)sl.d, (const int32_t *)(sl.d + o_lo),
+                                               (const int32_t *)(sl.d + o_hi), m, d_ret, ks);
+        if (lk == 0) lk = jfs_launch_range_pack((const jfs_range_pack *)(sl.d + o_pack), m, max_len, d_ret, ks);
+        if (lk == 0 && hipMemcpyAsync(sl.h + o_ret, sl.d + o_ret, (size_t)(end - o_ret), hipMemcpyDeviceToHost, ks) != hipSuccess)
+            lk = -1;
+        if (hipStreamSynchronize(ks) != hipSuccess || lk != 0) return (int64_t)JFS_ERR_HIP;
+        const int32_t *h_ret = (const int32_t *)(sl.h + o_ret);
+        cp.clear();
+        for (int k = 0; k < m; k++) {
+            const Job &j = jobs[k];
+            const int32_t raw = h_ret[k];
+            if (raw == j.expect) {
+                out_n[j.idx] = j.len;
+                cp.push_back({r[j.idx].dst, sl.h + o_out + j.out, (int64_t)j.len});
+            } else {
+                out_n[j.idx] = raw == -4 ? JFS_ERR_CHECKSUM : raw == -2 ? JFS_ERR_SHORT_BUFFER : JFS_ERR_CORRUPT;
+            }
+        }
+        par_copy(cp);
+        return (int64_t)JFS_OK;
+    });
+    chain_stat(JFS_ALGO_ZSTD, DECOMPRESS, n, [&](int i) { return r[i].table_len + r[i].frag_len; }, out_n, m > 0,
+               steady_ns() - t0);
+    return JFS_OK;
 }
 
 int jfs_device_count(void) { return (int)devices().size(); }

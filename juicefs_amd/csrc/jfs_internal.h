@@ -62,6 +62,24 @@ int jfs_launch_zstd_decode_prefix(const jfs_dev_block *d_blocks, int nblk, int32
 // number of selected frames, then jfs_launch_zstd_decode_prefix's behaviour
 int jfs_launch_zstd_decode_range(const jfs_dev_block *d_blocks, const int32_t *d_lo, const int32_t *d_hi, int nblk,
                                  int32_t *d_ret, hipStream_t stream);
+// XXH64, seed 0, of d_blocks[i].src[0, src_len) (xxh64.hip); d_ret may be null
+int jfs_launch_xxh64(const jfs_dev_block *d_blocks, int nblk, uint64_t *d_hash, int32_t *d_ret, hipStream_t stream);
+// the seekable encode with per-frame checksums in its table (zstd_seek_csum.hip)
+int jfs_launch_zstd_encode_seek_csum(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, hipStream_t stream);
+// fragment decode (zstd_seek.hip): the range decode from a stand-alone table and
+// a fragment of the object's frames, every decoded frame checked against its
+// table checksum where the table has them
+int jfs_launch_zstd_decode_frames(const jfs_seek_frag *d_frags, const int32_t *d_lo, const int32_t *d_hi, int nblk,
+                                  int32_t *d_ret, hipStream_t stream);
+// jfs_zstd_load_range_batch: the bytes src[0, len) of a decoded block go to dst
+// where the fragment decode of that read answered `expect`
+struct jfs_range_pack {
+    const uint8_t *src;
+    uint8_t *dst;
+    int32_t len, expect;
+};
+int jfs_launch_range_pack(const jfs_range_pack *d_pack, int n, int32_t max_len, const int32_t *d_ret,
+                          hipStream_t stream);
 // jfs_zstd_plan_host of such a decode; totals[5] is the largest clamped want
 void jfs_zstd_plan_host_prefix(const uint8_t *const *srcs, const int32_t *lens, const int32_t *caps,
                                const int32_t *wants, int nblk, void *info_out, uint64_t *totals);

@@ -133,5 +133,103 @@ JFS_ZSEEK_HD Sel seek_select(F fetch, int32_t src_len, int32_t dst_cap, int32_t 
     return s;
 }
 
+// ---- a table that stands alone, with or without checksums ------
+// The table's own bytes, [0, table_len) from the skippable magic through the
+// footer, of an object of object_len bytes whose frames it follows.  Descriptor
+// 0x00: entries of 8 bytes as above; 0x80: entries of 12 bytes whose third word
+// is the low 32 bits of XXH64 (seed 0) of the frame's content.  Every condition
+// above holds here too; nothing outside [0, table_len) is fetched.
+constexpr int32_t ENTRY_CSUM = 12;
+constexpr uint32_t DESC_CSUM = 0x80u;
+
+// the frame count and the entry size (8 or 12), or false
+template <class F>
+JFS_ZSEEK_HD bool table_header(F fetch, int64_t table_len, int64_t object_len, int32_t *nf, int32_t *entry) {
+    if (table_len < TABLE_FIXED + ENTRY || table_len > object_len || object_len > 0x7FFFFFFFll) return false;
+    const int32_t tl = (int32_t)table_len;
+    if (le32(fetch, tl - 4) != SEEK_MAGIC) return false;
+    const uint32_t desc = fetch(tl - 5);
+    if (desc != 0u && desc != DESC_CSUM) return false;
+    const int32_t ent = desc ? ENTRY_CSUM : ENTRY;
+    const uint32_t n = le32(fetch, tl - 9);
+    if (n < 1u || n > (uint32_t)MAX_FRAMES || (int64_t)ent * n + TABLE_FIXED != table_len) return false;
+    if (le32(fetch, 0) != SKIP_MAGIC) return false;
+    if (le32(fetch, 4) != (uint32_t)ent * n + 9u) return false;
+    *nf = (int32_t)n;
+    *entry = ent;
+    return true;
+}
+
+// entry k: compressed size, decompressed size, checksum (0 without one)
+template <class F>
+JFS_ZSEEK_HD void table_entry(F fetch, int32_t entry, int32_t k, uint32_t *c, uint32_t *d, uint32_t *x) {
+    *c = le32(fetch, 8 + entry * k);
+    *d = le32(fetch, 12 + entry * k);
+    *x = entry == ENTRY_CSUM ? le32(fetch, 16 + entry * k) : 0u;
+}
+
+struct TableSel {
+    int32_t table;      // 1: a valid table
+    int32_t checksums;  // 1: entries of 12 bytes
+    int32_t nf;
+    int32_t first, count;  // the selected frames; count 0: the range meets none
+    uint64_t total;        // D
+    uint64_t coff, cend;   // the selected frames' bytes in the object
+    uint64_t doff, dend;   // and their content
+};
+
+// The whole answer for one stand-alone table, serially: seek_select's rule with
+// lo' = max(lo, 0) and hi' = min(hi, cap), where cap < 0 stands for D.
+template <class F>
+JFS_ZSEEK_HD TableSel table_select(F fetch, int64_t table_len, int64_t object_len, int64_t cap, int64_t lo, int64_t hi) {
+    TableSel s;
+    s.table = 0; s.checksums = 0; s.nf = 0; s.first = 0; s.count = 0;
+    s.total = 0; s.coff = 0; s.cend = 0; s.doff = 0; s.dend = 0;
+    int32_t nf = 0, entry = 0;
+    if (!table_header(fetch, table_len, object_len, &nf, &entry)) return s;
+    uint64_t cs = 0, ds = 0;
+    uint32_t zeros = 0;
+    for (int32_t k = 0; k < nf; k++) {
+        uint32_t c, d, x;
+        table_entry(fetch, entry, k, &c, &d, &x);
+        zeros += c == 0u;
+        cs += c;
+        ds += d;
+    }
+    if (zeros != 0u || cs != (uint64_t)(object_len - table_len) || ds > 0xFFFFFFFFull) return s;
+    s.table = 1;
+    s.checksums = entry == ENTRY_CSUM;
+    s.nf = nf;
+    s.total = ds;
+    const uint64_t l = lo > 0 ? (uint64_t)lo : 0u;
+    const int64_t top = cap < 0 ? (int64_t)ds : cap;
+    const int64_t h = hi < top ? hi : top;
+    if (h <= 0 || (uint64_t)h <= l) return s;
+    uint64_t c0 = 0, d0 = 0;
+    int32_t first = 0, count = 0;
+    for (int32_t k = 0; k < nf; k++) {
+        uint32_t c, d, x;
+        table_entry(fetch, entry, k, &c, &d, &x);
+        if (d0 + d <= l) {  // in front of the range
+            first = k + 1;
+            s.coff = c0 + c;
+            s.doff = d0 + d;
+        } else if (d0 < (uint64_t)h) {
+            count = k + 1 - first;
+            s.cend = c0 + c;
+            s.dend = d0 + d;
+        }
+        c0 += c;
+        d0 += d;
+    }
+    if (count > 0) {
+        s.first = first;
+        s.count = count;
+    } else {
+        s.coff = s.cend = s.doff = s.dend = 0;
+    }
+    return s;
+}
+
 }  // namespace zseek
 }  // namespace jfs

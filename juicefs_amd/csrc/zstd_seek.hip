@@ -201,6 +201,180 @@ __global__ __launch_bounds__(64) void zseek_fold(const In *__restrict__ in, int 
     if (lane == 0) ret[i] = r;
 }
 
+// ---- fragments (jfs_zstd_decompress_frames_device) --------------
+// The same four steps over a table that stands alone (zstd_seek.h, second
+// part) and a fragment of the object's frames: sibling kernels, so the range
+// call keeps its own.  zseek_offsets serves both.
+enum : int32_t {
+    M_BAD = 4,   // a bad descriptor or no valid table: -1
+    M_FRAG = 5,  // a selected frame lies outside the fragment: -3
+};
+
+__global__ __launch_bounds__(64) void zframes_scan(const jfs_seek_frag *__restrict__ frags, const int32_t *__restrict__ lo,
+                                                   const int32_t *__restrict__ hi, int nblk, In *__restrict__ out) {
+    const int i = blockIdx.x, lane = lane_id();
+    if (i >= nblk) return;
+    const jfs_seek_frag b = frags[i];
+    In z;
+    z.mode = M_BAD; z.answer = 0; z.nf = 0; z.first = 0; z.count = 0; z.coff = 0; z.doff = 0; z.slot0 = 0;
+    const int32_t l = range_lo(lo[i]), h = range_hi(hi[i], b.dst_cap);
+    const Fetch f{(const gc_u8 *)b.table};
+    int32_t nf = 0, entry = 0;
+    if (b.table == nullptr || b.frag == nullptr || b.dst == nullptr || b.table_len < 0 || b.object_len < 0 ||
+        b.frag_off < 0 || b.frag_len < 0 || b.dst_cap < 0) {
+        // -1
+    } else if (table_header(f, b.table_len, b.object_len, &nf, &entry)) {
+        uint64_t cs = 0, ds = 0;  // the sums in front of this round
+        int32_t before = 0, end = 0;
+        uint64_t coff = 0, doff = 0, cend = 0;
+        bool zero = false;
+        for (int32_t k0 = 0; k0 < nf; k0 += 64) {
+            const int32_t k = k0 + lane;
+            const bool has = k < nf;
+            uint32_t c = 0, d = 0, x = 0;
+            if (has) table_entry(f, entry, k, &c, &d, &x);
+            const uint64_t ic = wave_scan_incl64(c), id = wave_scan_incl64(d);
+            const uint64_t d0 = ds + id - d;
+            const bool bef = has && frame_before(d0, d, l);
+            const bool sel = has && !bef && !frame_from(d0, h);
+            zero = zero || __ballot(has && c == 0u) != 0ull;
+            const int nbef = __popcll(__ballot(bef));
+            if (nbef > 0) {
+                before = k0 + nbef;
+                coff = cs + shfl64(ic, nbef - 1);
+                doff = ds + shfl64(id, nbef - 1);
+            }
+            const uint64_t m = __ballot(sel);
+            if (m) {
+                end = k0 + 64 - __builtin_clzll(m);
+                cend = cs + shfl64(ic, 63 - __builtin_clzll(m));
+            }
+            cs += shfl64(ic, 63);
+            ds += shfl64(id, 63);
+        }
+        if (zero || cs != (uint64_t)(uint32_t)(b.object_len - b.table_len) || ds > 0xFFFFFFFFull) {
+            // -1
+        } else if (b.dst_cap == 0 || h <= l) {
+            z.mode = M_EMPTY;
+        } else if (ds > (uint64_t)(uint32_t)b.dst_cap) {
+            z.mode = M_BIG;
+        } else {
+            z.mode = M_TABLE;
+            z.nf = nf;
+            z.answer = (int32_t)(ds < (uint64_t)(uint32_t)h ? ds : (uint64_t)(uint32_t)h);
+            if (end > before) {
+                if (coff < (uint64_t)(uint32_t)b.frag_off || cend > (uint64_t)(uint32_t)b.frag_off + (uint32_t)b.frag_len) {
+                    z.mode = M_FRAG;
+                } else {
+                    z.first = before;
+                    z.count = end - before;
+                    z.coff = (uint32_t)coff;
+                    z.doff = (uint32_t)doff;
+                }
+            }
+        }
+    }
+    if (lane == 0) out[i] = z;
+}
+
+// As zseek_expand; entry e also gets the piece XXH64 is taken of (its decoded
+// content; nothing for a table without checksums) and the word to expect.
+__global__ __launch_bounds__(64) void zframes_expand(const jfs_seek_frag *__restrict__ frags, int nblk,
+                                                     const In *__restrict__ in, int32_t total,
+                                                     jfs_dev_block *__restrict__ xdesc, int32_t *__restrict__ xwant,
+                                                     jfs_dev_block *__restrict__ hdesc, uint32_t *__restrict__ expect) {
+    const int32_t e = (int32_t)(blockIdx.x * 64u + threadIdx.x);
+    if (e >= total) return;
+    int a = 0, z = nblk - 1;  // the last input with slot0 <= e
+    while (a < z) {
+        const int m = (a + z + 1) >> 1;
+        if (in[m].slot0 <= e) a = m;
+        else z = m - 1;
+    }
+    const In s = in[a];
+    const jfs_seek_frag b = frags[a];
+    jfs_dev_block x{b.frag, b.dst, 0, 0};  // nothing to decode: an empty input
+    jfs_dev_block hd{nullptr, nullptr, 0, 0};
+    int32_t want = 0;
+    uint32_t sum = 0;
+    if (s.mode == M_TABLE && s.count > 0) {
+        const Fetch f{(const gc_u8 *)b.table};
+        const int32_t entry = f(b.table_len - 5) ? ENTRY_CSUM : ENTRY, j = e - s.slot0;
+        uint32_t coff = s.coff, doff = s.doff, c = 0, d = 0;
+        for (int32_t k = s.first; k < s.first + j; k++) {
+            table_entry(f, entry, k, &c, &d, &sum);
+            coff += c;
+            doff += d;
+        }
+        table_entry(f, entry, s.first + j, &c, &d, &sum);
+        if (d > 0u) {  // (a frame without content inside the selection has nothing to write)
+            x = jfs_dev_block{b.frag + (coff - (uint32_t)b.frag_off), b.dst + doff, (int32_t)c, (int32_t)d};
+            want = (int32_t)d;
+        }
+        if (entry == ENTRY_CSUM) hd = jfs_dev_block{b.dst + doff, nullptr, (int32_t)d, 0};
+    }
+    xdesc[e] = x;
+    xwant[e] = want;
+    hdesc[e] = hd;
+    expect[e] = sum;
+}
+
+// As zseek_fold, with the two new answers and the checksum verdict: -1 (a frame
+// that did not return its table size) wins over -4 (a frame whose content's
+// XXH64 low word is not its entry's).
+__global__ __launch_bounds__(64) void zframes_fold(const In *__restrict__ in, int nblk, const jfs_dev_block *__restrict__ xdesc,
+                                                   const int32_t *__restrict__ xret, const jfs_dev_block *__restrict__ hdesc,
+                                                   const uint64_t *__restrict__ hash, const uint32_t *__restrict__ expect,
+                                                   int32_t *__restrict__ ret) {
+    const int i = blockIdx.x, lane = lane_id();
+    if (i >= nblk) return;
+    const In s = in[i];
+    int32_t r;
+    if (s.mode == M_BAD) {
+        r = -1;
+    } else if (s.mode == M_EMPTY) {
+        r = 0;
+    } else if (s.mode == M_BIG) {
+        r = -2;
+    } else if (s.mode == M_FRAG) {
+        r = -3;
+    } else {
+        bool bad = false, differ = false;
+        for (int32_t j = lane; j < s.count; j += 64) {
+            const int32_t d = xdesc[s.slot0 + j].dst_cap;
+            bad = bad || (d > 0 && xret[s.slot0 + j] != d);
+            differ = differ || (hdesc[s.slot0 + j].src != nullptr && (uint32_t)hash[s.slot0 + j] != expect[s.slot0 + j]);
+        }
+        r = __ballot(bad) ? -1 : __ballot(differ) ? -4 : s.answer;
+    }
+    if (lane == 0) ret[i] = r;
+}
+
+// jfs_zstd_load_range_batch: read i's requested bytes, block[lo, lo + len) of
+// its decoded block, go to its place in the area that crosses the link -- only
+// where the decode answered the length the host expects (anything else is a
+// failed read: nothing of it comes down).  grid (tiles of 16 KiB, reads).
+constexpr int32_t PACK_TILE = 16 << 10;
+__global__ __launch_bounds__(256) void zframes_pack(const jfs_range_pack *__restrict__ pk, int n,
+                                                    const int32_t *__restrict__ ret) {
+    const int i = blockIdx.y;
+    if (i >= n) return;
+    const jfs_range_pack p = pk[i];
+    if (p.len <= 0 || ret[i] != p.expect) return;
+    const int64_t t0 = (int64_t)blockIdx.x * PACK_TILE;
+    if (t0 >= p.len) return;
+    const int32_t m = (int32_t)(p.len - t0 < PACK_TILE ? p.len - t0 : PACK_TILE);
+    gc_u8 *s = (gc_u8 *)p.src + t0;
+    g_u8 *d = (g_u8 *)p.dst + t0;
+    if ((((uintptr_t)s | (uintptr_t)d) & 15u) == 0) {
+        const int32_t q = m >> 4;
+        for (int32_t k = threadIdx.x; k < q; k += 256) ((g_u4 *)d)[k] = ((gc_u4 *)s)[k];
+        for (int32_t k = (q << 4) + threadIdx.x; k < m; k += 256) d[k] = s[k];
+    } else {
+        for (int32_t k = threadIdx.x; k < m; k += 256) d[k] = s[k];
+    }
+}
+
 namespace {
 struct Scratch {
     std::mutex mu;
@@ -208,6 +382,8 @@ struct Scratch {
     size_t in_cap = 0;
     uint8_t *d_x = nullptr;  // per entry: descriptor, want, result
     size_t x_cap = 0;
+    uint8_t *d_h = nullptr;  // per entry of a fragment decode: hash descriptor, hash, expected word
+    size_t h_cap = 0;
     uint64_t *d_total = nullptr, *h_total = nullptr;
     hipEvent_t ev_total = nullptr, ev_done = nullptr;
 };
@@ -226,6 +402,7 @@ bool grow(T **p, size_t *cap, size_t want) {
     return true;
 }
 constexpr size_t X_ENTRY = sizeof(jfs_dev_block) + 8;
+constexpr size_t H_ENTRY = sizeof(jfs_dev_block) + 8 + 8;  // (the expected word's 4 bytes, padded)
 }  // namespace
 
 }  // namespace zseek
@@ -275,4 +452,63 @@ extern "C" int jfs_launch_zstd_decode_range(const jfs_dev_block *d_blocks, const
                        (const jfs_dev_block *)xdesc, (const int32_t *)xret, d_ret);
     if (hipGetLastError() != hipSuccess) return -1;
     return hipEventRecord(z.ev_done, stream) == hipSuccess ? 0 : -1;
+}
+
+// The same sequence for fragments: scan -> offsets -> (the host wait) -> expand
+// -> prefix decode of the list -> XXH64 of the decoded pieces -> fold
+extern "C" int jfs_launch_zstd_decode_frames(const jfs_seek_frag *d_frags, const int32_t *d_lo, const int32_t *d_hi,
+                                             int nblk, int32_t *d_ret, hipStream_t stream) {
+    using namespace jfs::zseek;
+    if (nblk <= 0) return 0;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -1;
+    Scratch &z = g_scr[dev];
+    std::lock_guard<std::mutex> lk(z.mu);
+    if (!z.d_total) {
+        if (hipMalloc((void **)&z.d_total, sizeof(uint64_t)) != hipSuccess) return -1;
+        if (hipHostMalloc((void **)&z.h_total, sizeof(uint64_t), hipHostMallocDefault) != hipSuccess) return -1;
+        if (hipEventCreateWithFlags(&z.ev_total, hipEventDisableTiming) != hipSuccess) return -1;
+        if (hipEventCreateWithFlags(&z.ev_done, hipEventDisableTiming) != hipSuccess) return -1;
+    }
+    if ((size_t)nblk > z.in_cap) {
+        if (hipEventSynchronize(z.ev_done) != hipSuccess) return -1;
+        if (!grow(&z.d_in, &z.in_cap, (size_t)nblk)) return -1;
+    }
+    if (hipStreamWaitEvent(stream, z.ev_done, 0) != hipSuccess) return -1;
+    hipLaunchKernelGGL(zframes_scan, dim3((unsigned)nblk), dim3(64), 0, stream, d_frags, d_lo, d_hi, nblk, z.d_in);
+    hipLaunchKernelGGL(zseek_offsets, dim3(1), dim3(64), 0, stream, z.d_in, nblk, z.d_total);
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (hipMemcpyAsync(z.h_total, z.d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, stream) != hipSuccess) return -1;
+    if (hipEventRecord(z.ev_total, stream) != hipSuccess) return -1;
+    if (hipEventSynchronize(z.ev_total) != hipSuccess) return -1;
+    const uint64_t total = *z.h_total;
+    if (total < (uint64_t)nblk || total > 0x7FFFFFF0ull / H_ENTRY) return -1;
+    if (!grow(&z.d_x, &z.x_cap, (size_t)total * X_ENTRY)) return -1;
+    if (!grow(&z.d_h, &z.h_cap, (size_t)total * H_ENTRY)) return -1;
+    jfs_dev_block *xdesc = (jfs_dev_block *)z.d_x, *hdesc = (jfs_dev_block *)z.d_h;
+    int32_t *xwant = (int32_t *)(xdesc + total), *xret = xwant + total;
+    uint64_t *hash = (uint64_t *)(hdesc + total);
+    uint32_t *expect = (uint32_t *)(hash + total);
+    hipLaunchKernelGGL(zframes_expand, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, stream, d_frags, nblk,
+                       (const In *)z.d_in, (int32_t)total, xdesc, xwant, hdesc, expect);
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (jfs_launch_zstd_decode_prefix(xdesc, (int)total, xret, xwant, stream) != 0) return -1;
+    if (jfs_launch_xxh64(hdesc, (int)total, hash, nullptr, stream) != 0) return -1;
+    hipLaunchKernelGGL(zframes_fold, dim3((unsigned)nblk), dim3(64), 0, stream, (const In *)z.d_in, nblk,
+                       (const jfs_dev_block *)xdesc, (const int32_t *)xret, (const jfs_dev_block *)hdesc,
+                       (const uint64_t *)hash, (const uint32_t *)expect, d_ret);
+    if (hipGetLastError() != hipSuccess) return -1;
+    return hipEventRecord(z.ev_done, stream) == hipSuccess ? 0 : -1;
+}
+
+extern "C" int jfs_launch_range_pack(const jfs_range_pack *d_pack, int n, int32_t max_len, const int32_t *d_ret,
+                                     hipStream_t stream) {
+    using namespace jfs::zseek;
+    if (n <= 0 || max_len <= 0) return 0;
+    for (int a = 0; a < n; a += 65535) {  // (the grid's y extent)
+        const int m = n - a < 65535 ? n - a : 65535;
+        hipLaunchKernelGGL(zframes_pack, dim3((unsigned)((max_len + PACK_TILE - 1) / PACK_TILE), (unsigned)m), dim3(256),
+                           0, stream, d_pack + a, m, d_ret + a);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }

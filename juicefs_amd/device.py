@@ -195,6 +195,63 @@ def zstd_decompress_range(desc: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor
                                                      _stream_ptr(stream)), "jfs_zstd_decompress_range_device")
 
 
+def xxh64(desc: torch.Tensor, hash: torch.Tensor, ret: torch.Tensor | None = None, stream=None):
+    """jfs_xxh64_device: hash[i] (an int64 device tensor holding the uint64
+    bits) = XXH64, seed 0, of descriptor i's src[0, src_len); ret[i] (int32,
+    optional) = 0, or -1 for a bad descriptor."""
+    n = desc.numel() // DESC_DTYPE.itemsize
+    assert hash.dtype == torch.int64 and hash.numel() >= n
+    _check(L.load().jfs_xxh64_device(desc.data_ptr(), n, hash.data_ptr(), ret.data_ptr() if ret is not None else None,
+                                     _stream_ptr(stream)), "jfs_xxh64_device")
+
+
+def zstd_compress_seekable_csum(desc: torch.Tensor, ret: torch.Tensor, stream=None):
+    """jfs_zstd_compress_seekable_csum_device: zstd_compress_seekable's frames,
+    then a table of 12-byte entries whose third word is the low half of XXH64
+    of the frame's content.  Host-synchronous."""
+    n = desc.numel() // DESC_DTYPE.itemsize
+    _check(L.load().jfs_zstd_compress_seekable_csum_device(desc.data_ptr(), n, ret.data_ptr(), _stream_ptr(stream)),
+           "jfs_zstd_compress_seekable_csum_device")
+
+
+FRAG_DTYPE = np.dtype([("table", "<u8"), ("table_len", "<i4"), ("object_len", "<i4"),
+                       ("frag", "<u8"), ("frag_off", "<i4"), ("frag_len", "<i4"),
+                       ("dst", "<u8"), ("dst_cap", "<i4"), ("reserved", "<i4")])
+assert FRAG_DTYPE.itemsize == ctypes.sizeof(L.JfsSeekFrag)
+
+
+def make_frag_desc(buf: torch.Tensor, table_offs, table_lens, object_lens, frag_offs_in_buf, frag_offs, frag_lens,
+                   dst: torch.Tensor, dst_offs, dst_caps) -> torch.Tensor:
+    """Build a device tensor of jfs_seek_frag descriptors (48 bytes each): the
+    tables and fragments lie in `buf` at table_offs / frag_offs_in_buf; frag_offs
+    are the fragments' positions in their objects.  An offset of None gives a
+    NULL pointer."""
+    n = len(table_offs)
+    a = np.zeros(n, dtype=FRAG_DTYPE)
+
+    def ptrs(t, offs):
+        return np.asarray([0 if o is None else t.data_ptr() + o for o in offs], dtype=np.uint64)
+    a["table"] = ptrs(buf, table_offs)
+    a["frag"] = ptrs(buf, frag_offs_in_buf)
+    a["dst"] = ptrs(dst, dst_offs)
+    a["table_len"] = np.asarray(table_lens, dtype=np.int32)
+    a["object_len"] = np.asarray(object_lens, dtype=np.int32)
+    a["frag_off"] = np.asarray(frag_offs, dtype=np.int32)
+    a["frag_len"] = np.asarray(frag_lens, dtype=np.int32)
+    a["dst_cap"] = np.asarray(dst_caps, dtype=np.int32)
+    return torch.from_numpy(a.view(np.uint8).copy()).to(buf.device)
+
+
+def zstd_decompress_frames(desc: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor, ret: torch.Tensor, stream=None):
+    """jfs_zstd_decompress_frames_device: input i (make_frag_desc) is decoded for
+    its content bytes [lo[i], hi[i]) from its table and a fragment of its
+    frames; with a checksummed table every decoded frame is verified (-4)."""
+    n = desc.numel() // FRAG_DTYPE.itemsize
+    assert lo.dtype == torch.int32 and hi.dtype == torch.int32 and lo.numel() >= n and hi.numel() >= n
+    _check(L.load().jfs_zstd_decompress_frames_device(desc.data_ptr(), lo.data_ptr(), hi.data_ptr(), n, ret.data_ptr(),
+                                                      _stream_ptr(stream)), "jfs_zstd_decompress_frames_device")
+
+
 def crc32c(desc: torch.Tensor, crc: torch.Tensor | None = None, ret: torch.Tensor | None = None,
            seg_bytes: int = 0, stream=None):
     """CRC-32C per descriptor (jfs_crc32c_device): whole-block values into
