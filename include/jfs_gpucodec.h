@@ -315,12 +315,29 @@ int jfs_lz4_eseg_counts(uint64_t *out, int reset);
 int64_t jfs_zstd_decompress_device(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, void *stream);
 /* Batches of at most JFS_ZSTD_SPLIT_MAX inputs (default 128; also the batch
  * ABI's staged chunks and jfs_decompress) decode one workgroup per Zstd block
- * with an origin-map replay; an input outside that path's proven cases (not
- * exactly one frame, a checksum, any error) is replayed by the exact one-wave
- * kernel -- same results either way.  Diagnostics: out[0] = inputs the
+ * with an origin-map replay; an input outside that path's proven cases (no
+ * frame or more frames than jfs_get_zstd_split_frames, a frame with a content
+ * checksum, any error) is replayed by the exact one-wave kernel -- same
+ * results either way.  Diagnostics: out[0] = inputs the
  * small-batch path replayed itself, out[1] = inputs it handed over; on the
  * current device since the last reset.  Synchronous; 0 on success. */
 int jfs_zstd_split_counts(uint64_t *out, int reset);
+/* The most frames an input may hold for the small-batch path to replay it
+ * itself: concatenated frames from any writer, seekable objects (one frame per
+ * 128 KiB; no seek table is read or trusted), skippable frames anywhere.
+ * Default JFS_ZSTD_SPLIT_FRAMES_MAX (the seek table's frame limit); 1 hands
+ * every multi-frame input to the one-wave kernel, as before the limit existed.
+ * The initial value is read once from JFS_ZSTD_SPLIT_FRAMES (a decimal in
+ * [1, 16384]; anything else is the default).  Process-wide; a launch takes the
+ * value of the moment it is enqueued.  jfs_set_zstd_split_frames returns the
+ * previous value, or -1 for a value outside [1, 16384] (nothing changes). */
+#define JFS_ZSTD_SPLIT_FRAMES_MAX 16384
+int jfs_get_zstd_split_frames(void);
+int jfs_set_zstd_split_frames(int max_frames);
+/* Of jfs_zstd_split_counts' out[0]: out[0] = the inputs of two frames or more,
+ * out[1] = the frames they held; on the current device since the last reset.
+ * Synchronous; 0 on success. */
+int jfs_zstd_split_frame_counts(uint64_t out[2], int reset);
 /* Zstd frame per block; ret[i] = frame size, or -2 when dst_cap < CompressBound(src_len).
  * Synchronous with respect to `stream` (it uses per-device scratch). */
 int64_t jfs_zstd_compress_device(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, void *stream);

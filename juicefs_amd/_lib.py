@@ -54,6 +54,7 @@ EXPORTS = [
     "jfs_xxh64_device", "jfs_zstd_compress_seekable_csum_device", "jfs_zstd_seek_csum_mode",
     "jfs_set_zstd_seek_csum_mode", "jfs_zstd_seek_plan", "jfs_zstd_decompress_frames_device",
     "jfs_zstd_load_range_batch",
+    "jfs_get_zstd_split_frames", "jfs_set_zstd_split_frames", "jfs_zstd_split_frame_counts",
 ]
 # the hook include/jfs_gpucodec_lz4_fast_test.h declares (the fast LZ4 encoder's host twin)
 LZ4_FAST_TEST_EXPORTS = ["jfs_test_lz4_fast_host"]
@@ -64,6 +65,7 @@ MODE_OFF, MODE_AUTO, MODE_FORCE = 0, 1, 2
 LZ4_PARSE_EXACT, LZ4_PARSE_FAST = 0, 1
 ZSTD_PARSE_EXACT, ZSTD_PARSE_FAST, ZSTD_PARSE_SEEKABLE = 0, 1, 2
 READ_SEEK_OFF, READ_SEEK_ON = 0, 1
+ZSTD_SPLIT_FRAMES_MAX = 16384
 ZSTD_SEEK_CSUM_OFF, ZSTD_SEEK_CSUM_ON = 0, 1
 SEEK_PLAN_OK, SEEK_PLAN_MORE, SEEK_PLAN_NONE = 0, 1, 2
 READ_DECODE_FULL, READ_DECODE_PREFIX, READ_DECODE_PREFIX_ALL = 0, 1, 2
@@ -193,6 +195,12 @@ def load() -> ctypes.CDLL:
     lib.jfs_lz4_split_counts.restype = ctypes.c_int
     lib.jfs_zstd_split_counts.argtypes = [vp, ctypes.c_int]
     lib.jfs_zstd_split_counts.restype = ctypes.c_int
+    lib.jfs_zstd_split_frame_counts.argtypes = [vp, ctypes.c_int]
+    lib.jfs_zstd_split_frame_counts.restype = ctypes.c_int
+    lib.jfs_get_zstd_split_frames.argtypes = []
+    lib.jfs_get_zstd_split_frames.restype = ctypes.c_int
+    lib.jfs_set_zstd_split_frames.argtypes = [ctypes.c_int]
+    lib.jfs_set_zstd_split_frames.restype = ctypes.c_int
     lib.jfs_test_set_split_jump_rounds.argtypes = [ctypes.c_int, ctypes.c_int]
     lib.jfs_test_set_split_jump_rounds.restype = ctypes.c_int
     lib.jfs_lz4_compress_device_small.argtypes = [vp, vp, ctypes.c_int, vp, vp]

@@ -365,6 +365,20 @@ def set_read_seek_mode(mode: str) -> str:
     return next(k for k, v in _READ_SEEK.items() if v == prev)
 
 
+def zstd_split_frames() -> int:
+    """The most frames a Zstd input may hold for the small-batch decode path to
+    replay it block-parallel (jfs_get_zstd_split_frames; default 16384)."""
+    return L.load().jfs_get_zstd_split_frames()
+
+
+def set_zstd_split_frames(n: int) -> int:
+    """Set it (process-wide, for launches enqueued afterwards) and return the
+    previous value; 1 hands every multi-frame input to the one-wave replay."""
+    if not isinstance(n, int) or isinstance(n, bool) or not 1 <= n <= L.ZSTD_SPLIT_FRAMES_MAX:
+        raise ValueError(f"zstd split frames {n!r}: expected an int in [1, {L.ZSTD_SPLIT_FRAMES_MAX}]")
+    return L.load().jfs_set_zstd_split_frames(n)
+
+
 _SEEK_CSUM = {"off": L.ZSTD_SEEK_CSUM_OFF, "on": L.ZSTD_SEEK_CSUM_ON}
 _PLAN_STATUS = {L.SEEK_PLAN_OK: "ok", L.SEEK_PLAN_MORE: "more", L.SEEK_PLAN_NONE: "none"}
 

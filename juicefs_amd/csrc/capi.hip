@@ -327,6 +327,19 @@ std::atomic<int> &read_seek() {
     return m;
 }
 
+// JFS_ZSTD_SPLIT_FRAMES (include/jfs_gpucodec.h): 1 .. 16384 (default 16384);
+// anything else in the environment leaves the default
+std::atomic<int> &zstd_split_frames() {
+    static std::atomic<int> m{[] {
+        const char *e = getenv("JFS_ZSTD_SPLIT_FRAMES");
+        if (!e) return JFS_ZSTD_SPLIT_FRAMES_MAX;
+        char *end = nullptr;
+        const long v = strtol(e, &end, 10);
+        return end != e && *end == 0 && v >= 1 && v <= JFS_ZSTD_SPLIT_FRAMES_MAX ? (int)v : JFS_ZSTD_SPLIT_FRAMES_MAX;
+    }()};
+    return m;
+}
+
 // JFS_ZSTD_PARSE (include/jfs_gpucodec.h): exact (default) | fast | seekable
 std::atomic<int> &zstd_parse() {
     static std::atomic<int> m{[] {
@@ -2843,6 +2856,13 @@ int jfs_read_seek_mode(void) { return read_seek().load(std::memory_order_relaxed
 int jfs_set_read_seek_mode(int mode) {
     if (mode != JFS_READ_SEEK_OFF && mode != JFS_READ_SEEK_ON) return -1;
     return read_seek().exchange(mode);
+}
+
+int jfs_get_zstd_split_frames(void) { return zstd_split_frames().load(std::memory_order_relaxed); }
+
+int jfs_set_zstd_split_frames(int max_frames) {
+    if (max_frames < 1 || max_frames > JFS_ZSTD_SPLIT_FRAMES_MAX) return -1;
+    return zstd_split_frames().exchange(max_frames);
 }
 
 int jfs_zstd_parse_mode(void) { return zstd_parse_now(); }

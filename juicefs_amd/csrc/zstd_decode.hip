@@ -2424,7 +2424,7 @@ int launch_split(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, jfs::z
     const int64_t nbk = (int64_t)tot[3], max_cap = (int64_t)tot[5];
     hipLaunchKernelGGL(zsplan_kernel, dim3(1), dim3(64), 0, st, d_info, nblk, sc);
     hipLaunchKernelGGL(zswalk_kernel, dim3(nblk), dim3(64), 0, st, d_blocks, nblk, d_info, d_items, sc,
-                       g_strict_reserved);
+                       g_strict_reserved, jfs_get_zstd_split_frames());
     if (nbk > 0)
         hipLaunchKernelGGL(zsblk_kernel, dim3((unsigned)nbk), dim3(128), 0, st, d_blocks, nblk, d_info, d_lit, d_items,
                            sc);
@@ -2433,6 +2433,10 @@ int launch_split(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, jfs::z
         hipLaunchKernelGGL(zsemit_kernel, dim3((unsigned)nbk, ZSE_PARTS), dim3(ST), 0, st, nblk, (const ZInfo *)d_info,
                            (const uint4 *)d_items, sc);
     const unsigned jx = om::jump_groups(max_cap, nblk);
+    // A chain of origins takes a step per sequence (3 output bytes at least),
+    // however the sequences are spread over blocks and frames -- a frame edge
+    // only ends chains (no origin crosses it) -- so the bound of
+    // origin_map.h does not depend on the number of frames.
     const int jr = om::launch_rounds(max_cap, 3);
     for (int r = 0; r < jr; r++) hipLaunchKernelGGL(zsjump_kernel, dim3(jx, (unsigned)nblk), dim3(ST), 0, st, sc, r);
     hipLaunchKernelGGL(zsgather_kernel, dim3(om::quad_groups(max_cap), (unsigned)nblk), dim3(ST), 0, st, d_blocks,
@@ -2445,24 +2449,31 @@ int launch_split(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, jfs::z
 }  // namespace
 
 namespace {
-// this unit's small-batch counters, added to out[0..1]
-int split_counts_add(uint64_t *out, int reset) {
-    unsigned long long v[2] = {0, 0};
-    if (hipMemcpyFromSymbol(v, HIP_SYMBOL(jfs::JFS_ZNS::g_zsplit_counts), sizeof(v)) != hipSuccess) return -1;
+// this unit's small-batch counters (frames: the multi-frame pair), added to out[0..1]
+int split_counts_add(uint64_t *out, int reset, bool frames = false) {
+    unsigned long long v[2] = {0, 0}, z[2] = {0, 0};
+    if (frames) {
+        if (hipMemcpyFromSymbol(v, HIP_SYMBOL(jfs::JFS_ZNS::g_zsplit_frame_counts), sizeof(v)) != hipSuccess) return -1;
+        if (reset && hipMemcpyToSymbol(HIP_SYMBOL(jfs::JFS_ZNS::g_zsplit_frame_counts), z, sizeof(z)) != hipSuccess)
+            return -1;
+    } else {
+        if (hipMemcpyFromSymbol(v, HIP_SYMBOL(jfs::JFS_ZNS::g_zsplit_counts), sizeof(v)) != hipSuccess) return -1;
+        if (reset && hipMemcpyToSymbol(HIP_SYMBOL(jfs::JFS_ZNS::g_zsplit_counts), z, sizeof(z)) != hipSuccess) return -1;
+    }
     out[0] += v[0];
     out[1] += v[1];
-    if (reset) {
-        unsigned long long z[2] = {0, 0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(jfs::JFS_ZNS::g_zsplit_counts), z, sizeof(z)) != hipSuccess) return -1;
-    }
     return 0;
 }
 }  // namespace
 
 #ifdef JFS_ZSTD_DECODE_PREFIX_TU
 extern "C" int jfs_zstd_prefix_split_counts_add(uint64_t *out, int reset) { return split_counts_add(out, reset); }
+extern "C" int jfs_zstd_prefix_split_frame_counts_add(uint64_t *out, int reset) {
+    return split_counts_add(out, reset, true);
+}
 #else
 extern "C" int jfs_zstd_prefix_split_counts_add(uint64_t *out, int reset);
+extern "C" int jfs_zstd_prefix_split_frame_counts_add(uint64_t *out, int reset);
 extern "C" int jfs_zstd_split_ok(int nblk, const uint64_t *tot) { return split_ok(nblk, tot) ? 1 : 0; }
 extern "C" int64_t jfs_zstd_split_bytes(int nblk, const uint64_t *tot) { return split_bytes(nblk, tot); }
 
@@ -2473,6 +2484,14 @@ extern "C" int jfs_zstd_split_counts(uint64_t *out, int reset) {
     out[0] = out[1] = 0;
     if (split_counts_add(out, reset) != 0) return -1;
     return jfs_zstd_prefix_split_counts_add(out, reset);
+}
+
+// Of out[0] above: the inputs of two frames or more (out[0]) and the frames
+// they held (out[1]).
+extern "C" int jfs_zstd_split_frame_counts(uint64_t *out, int reset) {
+    out[0] = out[1] = 0;
+    if (split_counts_add(out, reset, true) != 0) return -1;
+    return jfs_zstd_prefix_split_frame_counts_add(out, reset);
 }
 #endif
 

@@ -10,7 +10,9 @@
 //             table builds): FSTART / FEND / BSTART / ERR items, the items of
 //             raw and RLE blocks, and one SBlk per block (where it is, its
 //             literal offset, the blocks whose Huffman table and FSE tables
-//             its repeat modes use);
+//             its repeat modes use -- never a block of an earlier frame --
+//             and SB_FEND on the last block of a frame, whose IT_FEND item
+//             follows the block's items);
 //   zsblk     one workgroup per block: wave 0 decodes the literals (zlit's
 //             lit_block; a treeless block rebuilds the table of its source
 //             block), wave 1 builds the FSE tables in LDS and decodes the
@@ -18,9 +20,12 @@
 //             offsets);
 //   zsfix     one wave per input resolves the blocks' repeat-offset entry
 //             states in order (IT_BREP items), the first literal error, and
-//             the blocks' output offsets; an input outside the proven cases
-//             (not exactly one frame, a checksum, any error item, a size or
-//             literal-count check) is marked for the exact replay;
+//             the blocks' output offsets and the output offset their frame
+//             starts at (fbase; libzstd's prefix restarts at every frame); an
+//             input outside the proven cases (no frame or more than the
+//             jfs_set_zstd_split_frames limit, a checksum, any error item, a
+//             frame's content size or a literal-count check) is marked for the
+//             exact replay;
 //   zsemit    one workgroup per block writes the ORIGIN of each output byte
 //             (origin_map.h: the entries, the jump and gather rules and the
 //             round count); a literal's index is its place in the input's
@@ -36,7 +41,7 @@
 constexpr int ST = om::THREADS;  // threads per workgroup (emit / jump / gather)
 constexpr int SCHUNK = 2048;     // sequence bitstream chunk staged per refill
 constexpr int SRING = 4 * SCHUNK;
-enum { SB_STORE = 1, SB_FIRST = 2, SB_SEQ = 4, SB_LIT = 8 };
+enum { SB_STORE = 1, SB_FIRST = 2, SB_SEQ = 4, SB_LIT = 8, SB_FEND = 16 };
 
 struct SBlk {              // one block of an input, in stream order
     int32_t bpos, bsize;   // block content within the input
@@ -53,15 +58,15 @@ struct SBlk {              // one block of an input, in stream order
     uint32_t brep;         // an IT_BREP item belongs at slot + 1
     uint64_t sll, sml;     // sums of literal and match lengths
     // zsfix
-    uint32_t e0, e1, e2, pad;  // repeat offsets at the block start
-    int64_t out;               // output offset of the block
+    uint32_t e0, e1, e2;  // repeat offsets at the block start
+    uint32_t fbase;       // output offset at which the block's frame starts (<= out)
+    int64_t out;          // output offset of the block
 };
 
 struct SIn {                 // one input
     int64_t blk_off, org_off;
-    int32_t nb, ok, has_fcs, todo;
-    int32_t unsettled, pad;  // the gather met an entry that is not a literal yet
-    uint64_t fcs;
+    int32_t nb, ok, frames, todo;  // frames: the frames the walk entered
+    int32_t unsettled, pad;        // the gather met an entry that is not a literal yet
     int64_t total;
     int32_t jmp[om::MAX_ROUNDS];
 };
@@ -80,8 +85,8 @@ __global__ void zsplan_kernel(const ZInfo *__restrict__ info, int nblk, SScr sc)
         SIn &x = sc.in[i];
         x.blk_off = bo;
         x.org_off = oo;
-        x.nb = 0; x.ok = 0; x.has_fcs = 0; x.todo = 1; x.unsettled = 0;
-        x.fcs = 0; x.total = 0;
+        x.nb = 0; x.ok = 0; x.frames = 0; x.todo = 1; x.unsettled = 0;
+        x.total = 0;
         for (int r = 0; r < om::MAX_ROUNDS; r++) x.jmp[r] = 0;
         sc.todo[i] = 1;
         bo += info[i].n_blk;
@@ -101,7 +106,7 @@ __device__ __forceinline__ int input_of(const SIn *in, int n, int64_t g) {
 
 __global__ __launch_bounds__(64) void zswalk_kernel(const jfs_dev_block *__restrict__ blocks, int nblk,
                                                     ZInfo *__restrict__ info, uint4 *__restrict__ items_all, SScr sc,
-                                                    int strict_reserved) {
+                                                    int strict_reserved, int max_frames) {
     const int bi = blockIdx.x;
     if (bi >= nblk) return;
     const int l = lane_id();
@@ -117,8 +122,8 @@ __global__ __launch_bounds__(64) void zswalk_kernel(const jfs_dev_block *__restr
     Walk w;
     walk_init(w, s, b.src_len, b.dst_cap, zwant(zi));
     uint32_t cur = 0, nb = 0;
-    int bug = 0, clean = 0, frames = 0, in_frame = 0, check = 0, first = 0, has_fcs = 0;
-    uint64_t fcs = 0;
+    int bug = 0, clean = 0, frames = 0, in_frame = 0, check = 0, first = 0;
+    uint32_t last_flags = 0;  // of record nb - 1
     int32_t last_h = -1, ts0 = -1, ts1 = -1, ts2 = -1;
     int64_t lpos = 0;
     auto put = [&](uint32_t x, uint32_t y, uint32_t z, uint32_t kind) {
@@ -128,13 +133,14 @@ __global__ __launch_bounds__(64) void zswalk_kernel(const jfs_dev_block *__restr
     };
     auto rec = [&](const SBlk &d) {
         if (l == 0) bk[nb] = d;
+        last_flags = d.flags;
         nb++;
     };
     for (;;) {
         int32_t err = 0;
         uint32_t fl = 0, chk = 0;
         const int ev = walk_next<ZPFX>(w, &err, &fl, &chk);
-        // (prefix decode) a walk stopped inside its one frame is a proven case too: no frame end, so no checks
+        // (prefix decode) a walk stopped inside a frame is a proven case too: that frame has no end, so no checks
         if (ev == EV_DONE) { clean = !in_frame || (ZPFX && w.stopped); break; }
         if (ev == EV_ERROR) { put(0, 0, (uint32_t)err, IT_ERR); break; }
         if (ev == EV_FSTART) {
@@ -148,8 +154,10 @@ __global__ __launch_bounds__(64) void zswalk_kernel(const jfs_dev_block *__restr
         if (ev == EV_FEND) {
             put((uint32_t)w.fcs, (uint32_t)(w.fcs >> 32), chk, IT_FEND | (fl << 8));
             in_frame = 0;
-            has_fcs = (fl & FE_FCS) != 0;
-            fcs = w.fcs;
+            // every frame ends behind a block of its own (a last block, if only an empty raw
+            // one): zsfix finds this item, and the frame's content size in it, behind that
+            // block's items
+            if (l == 0 && nb > 0) bk[nb - 1].flags = (uint8_t)(last_flags | SB_FEND);
             check |= (fl & FE_CHECK) != 0;
             if (fl & FE_MISSING) break;
             continue;
@@ -161,7 +169,7 @@ __global__ __launch_bounds__(64) void zswalk_kernel(const jfs_dev_block *__restr
         d.tsrc[0] = d.tsrc[1] = d.tsrc[2] = -1;
         d.btype = (uint8_t)w.btype; d.flags = 0;
         d.lerr = 0; d.serr = 0; d.r0 = d.r1 = d.r2 = 0; d.brep = 0; d.sll = d.sml = 0;
-        d.e0 = d.e1 = d.e2 = d.pad = 0; d.out = 0;
+        d.e0 = d.e1 = d.e2 = d.fbase = 0; d.out = 0;
         const uint32_t ord = w.ordinal - 1;
         if (w.btype != 2) {  // zlit copies the bytes only while they fit the output
             const int64_t room = (int64_t)w.cap - w.lb;
@@ -215,9 +223,8 @@ __global__ __launch_bounds__(64) void zswalk_kernel(const jfs_dev_block *__restr
     if (l == 0) {
         zi.n_items = bug ? 0xFFFFFFFFu : cur;
         si.nb = (int32_t)nb;
-        si.ok = !bug && clean && frames == 1 && !check;
-        si.has_fcs = has_fcs;
-        si.fcs = fcs;
+        si.ok = !bug && clean && frames >= 1 && frames <= max_frames && !check;
+        si.frames = frames;
     }
 }
 
@@ -622,6 +629,12 @@ __global__ __launch_bounds__(128) void zsblk_kernel(const jfs_dev_block *__restr
 
 // Repeat-offset entry states (IT_BREP items, as zseqb's phase C), the first
 // literal error (zlit's lit_err_blk / lit_err_code), and the output plan.
+// Per frame: the repeat offsets restart at its first sequence block
+// (SB_FIRST), fbase is the output offset it starts at, and at its end
+// (SB_FEND) a declared content size must equal run - fbase.  A frame that
+// declares more than the capacity left either produces that much (run > cap)
+// or does not (the size check): the input is marked either way, and zexec
+// gives libzstd's code.
 __global__ __launch_bounds__(64) void zsfix_kernel(const jfs_dev_block *__restrict__ blocks, int nblk,
                                                    ZInfo *__restrict__ info, uint4 *__restrict__ items_all, SScr sc) {
     const int bi = blockIdx.x;
@@ -635,7 +648,7 @@ __global__ __launch_bounds__(64) void zsfix_kernel(const jfs_dev_block *__restri
     g_u4 *items = (g_u4 *)items_all + zi.item_off;
     const int64_t cap = blocks[bi].dst_cap;
     uint32_t e0 = 1, e1 = 4, e2 = 8;
-    int64_t run = 0;
+    int64_t run = 0, fbase = 0;
     int ok = si.ok && zi.n_items != 0xFFFFFFFFu;
     uint32_t lerr_blk = 0xFFFFFFFFu;
     int32_t lerr_code = 0;
@@ -645,8 +658,11 @@ __global__ __launch_bounds__(64) void zsfix_kernel(const jfs_dev_block *__restri
         if (kk < nb) d = bk[kk];
         else d = bk[k0];
         const uint32_t bt = d.btype, fl = d.flags;
+        // the IT_FEND item behind a frame's last block: {fcs lo, fcs hi, checksum, kind | FE_* << 8}
+        uint4 fe = make_uint4(0, 0, 0, 0);
+        if (ok && kk < nb && (fl & SB_FEND)) fe = items[d.slot + 3 + (bt == 2 ? (uint32_t)d.nseq : 0u)];
         uint32_t me0 = 0, me1 = 0, me2 = 0;
-        int64_t mout = 0;
+        int64_t mout = 0, mbase = 0;
         for (int32_t j = 0; j < cnt; j++) {
             const uint32_t jbt = readlane(bt, j), jfl = readlane(fl, j), jslot = readlane(d.slot, j);
             const int32_t jregen = (int32_t)readlane((uint32_t)d.regen, j), jbsize = (int32_t)readlane((uint32_t)d.bsize, j);
@@ -668,16 +684,21 @@ __global__ __launch_bounds__(64) void zsfix_kernel(const jfs_dev_block *__restri
                 ok = 0;
             }
             ok = ok && !jlerr;
-            if (l == j) mout = run;
+            if (l == j) { mout = run; mbase = fbase; }
             run += jbt == 2 ? (int64_t)jregen + (int64_t)(jsml < (1ull << 40) ? jsml : (1ull << 40)) : (int64_t)jbsize;
             if (run > cap) ok = 0;
+            if (jfl & SB_FEND) {
+                const uint64_t jfcs = ((uint64_t)readlane(fe.y, j) << 32) | readlane(fe.x, j);
+                if (((readlane(fe.w, j) >> 8) & FE_FCS) && (uint64_t)(run - fbase) != jfcs) ok = 0;
+                fbase = run;
+            }
         }
         if (kk < nb) {
             bk[kk].e0 = me0; bk[kk].e1 = me1; bk[kk].e2 = me2;
+            bk[kk].fbase = (uint32_t)mbase;  // (an input whose run passes 2^31 is marked below)
             bk[kk].out = mout;
         }
     }
-    if (si.has_fcs && (uint64_t)run != si.fcs) ok = 0;
     if (run > 0x7FFFFFFF) ok = 0;
     // prefix decode: the origin map is settled and gathered over [0, want) only
     // (origins point backwards), and that is the result
@@ -758,6 +779,9 @@ __global__ __launch_bounds__(ST) void zsemit_kernel(int nblk, const ZInfo *__res
     int64_t pos = o0 + pre_n + (scan_n[t] - sn);
     uint32_t lp = d.lpos + pre_l + (scan_l[t] - sl);
     const uint32_t e0 = d.e0, e1 = d.e1, e2 = d.e2;
+    // a match of this frame never takes a byte of the frame before: libzstd's
+    // ZSTD_decompress restarts its prefix at every frame
+    const int64_t fbase = (int64_t)d.fbase;
     bool bad = false;
     for (int32_t q = q0; q < q1 && !bad; q++) {
         const uint4 v = it[q];
@@ -766,7 +790,7 @@ __global__ __launch_bounds__(ST) void zsemit_kernel(int nblk, const ZInfo *__res
         pos += ll;
         lp += ll;
         if (ml) {
-            if ((int64_t)off > pos) { bad = true; break; }  // before the frame start
+            if ((int64_t)off > pos - fbase) { bad = true; break; }  // before the frame start
             om::put_match<int64_t>(org, pos, ml, off);
             pos += ml;
         }
@@ -796,6 +820,8 @@ __global__ __launch_bounds__(ST) void zsjump_kernel(SScr sc, int round) {
 
 // inputs (small-batch path) decoded by the origin map / handed to zexec
 __device__ unsigned long long g_zsplit_counts[2];
+// of the former, the inputs of two frames or more, and the frames they held
+__device__ unsigned long long g_zsplit_frame_counts[2];
 
 __global__ void zsverd_kernel(int nblk, SScr sc, int32_t *__restrict__ ret) {
     const int bi = blockIdx.x * blockDim.x + threadIdx.x;
@@ -806,6 +832,10 @@ __global__ void zsverd_kernel(int nblk, SScr sc, int32_t *__restrict__ ret) {
     sc.todo[bi] = todo;
     if (!todo) ret[bi] = (int32_t)si.total;
     atomicAdd(&g_zsplit_counts[todo ? 1 : 0], 1ull);
+    if (!todo && si.frames >= 2) {
+        atomicAdd(&g_zsplit_frame_counts[0], 1ull);
+        atomicAdd(&g_zsplit_frame_counts[1], (unsigned long long)si.frames);
+    }
 }
 
 __global__ __launch_bounds__(ST) void zsgather_kernel(const jfs_dev_block *__restrict__ blocks,

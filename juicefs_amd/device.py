@@ -113,6 +113,14 @@ def zstd_split_counts(reset: bool = False):
     return tuple(int(x) for x in out)
 
 
+def zstd_split_frame_counts(reset: bool = False):
+    """(multi-frame inputs -- two frames or more -- the Zstd small-batch path
+    replayed itself, the frames they held) on the current device."""
+    out = (ctypes.c_uint64 * 2)()
+    _check(L.load().jfs_zstd_split_frame_counts(out, 1 if reset else 0), "jfs_zstd_split_frame_counts")
+    return tuple(int(x) for x in out)
+
+
 def set_split_jump_rounds(lz4: int = 0, zstd: int = 0):
     """Test hook (jfs_test_set_split_jump_rounds): the pointer-jumping rounds
     the small-batch decoders launch, full and prefix; 0 = the computed count.
