@@ -417,8 +417,9 @@ int64_t jfs_xxh64_device(const jfs_dev_block *d_blocks, int nblk, uint64_t *d_ha
  *     content) | u32 nb | u8 0x80 | u32 0x8F92EAB1
  * so ret is the seekable call's ret + 4 nb, exactly; the worst case n + 25 nb
  * + 17 stays within jfs_compress_bound(ZSTD, n).  jfs_zstd_decompress_range_device
- * and the JFS_READ_SEEK reads take such a table for no table and decode the
- * object as any other; jfs_zstd_decompress_frames_device reads it.  Does not
+ * and the JFS_READ_SEEK_ON reads take such a table for no table and decode the
+ * object as any other; jfs_zstd_decompress_frames_device,
+ * jfs_zstd_decompress_ranges_device and the JFS_READ_SEEK_SPARSE reads read it.  Does not
  * consult jfs_zstd_parse_mode or jfs_zstd_seek_csum_mode. */
 int64_t jfs_zstd_compress_seekable_csum_device(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, void *stream);
 
@@ -477,6 +478,50 @@ typedef struct jfs_seek_frag {
 } jfs_seek_frag;
 int64_t jfs_zstd_decompress_frames_device(const jfs_seek_frag *d_frags, const int32_t *d_lo, const int32_t *d_hi,
                                           int nblk, int32_t *d_ret, void *stream);
+
+/* Ranges decode: input i, a whole object, is decoded for the list of byte
+ * ranges d_rng[d_rng_first[i] .. d_rng_first[i+1]) of its output (device arrays:
+ * nblk + 1 int32, and that many jfs_range).  The seek table is read on the
+ * device in either layout -- descriptor byte 0x00 (8-byte entries) or 0x80
+ * (12-byte entries, the third word a checksum); any other descriptor is no
+ * table -- and exactly the frames some range touches are decoded, each as an
+ * independent input of jfs_zstd_decompress_prefix_device.  Let lo'_r = max(lo_r,
+ * 0), hi'_r = min(hi_r, dst_cap); a range is live when hi'_r > lo'_r; H = the
+ * largest hi'_r of the live ranges.  Frame k, content [D_k, D_k + d_k), is
+ * selected iff d_k > 0 and some live range has lo'_r < D_k + d_k and hi'_r >
+ * D_k.  ret[i], in this order of precedence:
+ *   NULL src, src_len == 0, dst_cap == 0: the full decoder's answers.
+ *   A bad list -- d_rng_first[i] < 0, d_rng_first[i+1] < d_rng_first[i], a range
+ *     with hi < lo, two ranges out of order or overlapping (the list must be
+ *     ascending and disjoint as given, lo_r <= hi_r <= lo_r+1; empty ranges may
+ *     stand anywhere): -1, nothing written.
+ *   No live range: 0, nothing written.
+ *   A valid table (the conditions of jfs_zstd_decompress_range_device, with
+ *     entries of 8 or 12 bytes; compressed sizes all >= 1 that add up to exactly
+ *     the table's position; D < 2^32): D > dst_cap gives -2.  Else every
+ *     selected frame is decoded into dst[D_k, D_k + d_k) with d_k as its
+ *     capacity and its want.  A selected frame that does not return exactly
+ *     d_k: -1.  Else, with a 12-byte table, a selected frame whose content's
+ *     XXH64 (seed 0) low word differs from its entry: -4.  Else min(D, H).  The
+ *     bytes of every selected frame equal the full decode's, and no byte of dst
+ *     outside the selected frames' spans is written: the frames between two
+ *     ranges are neither decoded nor touched.  A fault in a frame that was not
+ *     selected, or a table entry that lies about such a frame, is unseen.
+ *   Anything else (no valid table) is no error: the input is decoded by
+ *     jfs_zstd_decompress_prefix_device with want = H.
+ * With exactly one range per input, ret and the written bytes are
+ * jfs_zstd_decompress_range_device's for 8-byte tables and for objects without
+ * a table.  Stream behaviour and scratch are the range call's (one host wait
+ * for the number of selected frames; the per-device scratch and lock are shared
+ * with it). */
+typedef struct jfs_range { int32_t lo, hi; } jfs_range;
+int64_t jfs_zstd_decompress_ranges_device(const jfs_dev_block *d_blocks, const int32_t *d_rng_first,
+                                          const jfs_range *d_rng, int nblk, int32_t *d_ret, void *stream);
+/* Diagnostics of that call and of the reads in JFS_READ_SEEK_SPARSE: out[0] =
+ * inputs decoded through a table, out[1] = frames selected, out[2] = frames
+ * whose checksum was compared; on the current device since the last reset;
+ * synchronous.  0, or -1. */
+int jfs_zstd_sparse_counts(uint64_t out[3], int reset);
 
 /* The same from host buffers: what a loadRange adapter calls after
  * jfs_zstd_seek_plan and the ranged GET.  Read i holds the object's table and
@@ -831,7 +876,7 @@ int jfs_set_read_decode_mode_ext(int mode);
  * verdicts are those of the switch being off for every read whose sources are
  * well-formed.  LZ4 and "none" are untouched; the compaction calls do not
  * consult the switch.  The initial value is read once from JFS_READ_SEEK =
- * "off" | "on" (case-insensitive; anything else, or unset: off).
+ * "off" | "on" | "sparse" (case-insensitive; anything else, or unset: off).
  * jfs_set_read_seek_mode returns the previous value, or -1 for an unknown one
  * (which changes nothing); it is atomic and applies to calls that start
  * afterwards. */
@@ -839,6 +884,24 @@ int jfs_set_read_decode_mode_ext(int mode);
 #define JFS_READ_SEEK_ON 1
 int jfs_read_seek_mode(void);
 int jfs_set_read_seek_mode(int mode);
+/* JFS_READ_SEEK_SPARSE (JFS_READ_SEEK = "sparse"): as JFS_READ_SEEK_ON, but each
+ * Zstd source is decoded by jfs_zstd_decompress_ranges_device for the list of
+ * ranges [src_off, src_off + len) of the segments that reference it (clamped
+ * to its capacity, sorted, the ones that overlap or touch merged; a source
+ * nothing references has none), so two reads at the two ends of a seekable
+ * object pay for two frames, and an object written with JFS_ZSTD_SEEK_CSUM=on
+ * is range-decoded too, every decoded frame checked against its table
+ * checksum: a mismatch gives src_n[i] = JFS_ERR_CHECKSUM, behind the object
+ * CRC-32C verdict and the open's, and the reads that use the source fail with
+ * JFS_ERR_CORRUPT like those of any failed source.  src_n, out_n, the gathered
+ * bytes, crc_got, the disk-cache checksums and the jfs_stats accounting are
+ * those of JFS_READ_SEEK_ON for well-formed sources; a fault in a frame no
+ * read touches goes unseen unless the object CRC-32C is checked.
+ * jfs_set_read_seek_mode knows the two values it was introduced with and keeps
+ * answering -1 for any other, JFS_READ_SEEK_SPARSE included;
+ * jfs_set_read_seek_mode_ext is the same call for all three. */
+#define JFS_READ_SEEK_SPARSE 2
+int jfs_set_read_seek_mode_ext(int mode);
 
 /* ---- Runtime / utilities ------------------------------------------------- */
 

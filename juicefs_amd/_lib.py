@@ -55,6 +55,7 @@ EXPORTS = [
     "jfs_set_zstd_seek_csum_mode", "jfs_zstd_seek_plan", "jfs_zstd_decompress_frames_device",
     "jfs_zstd_load_range_batch",
     "jfs_get_zstd_split_frames", "jfs_set_zstd_split_frames", "jfs_zstd_split_frame_counts",
+    "jfs_zstd_decompress_ranges_device", "jfs_zstd_sparse_counts", "jfs_set_read_seek_mode_ext",
 ]
 # the hook include/jfs_gpucodec_lz4_fast_test.h declares (the fast LZ4 encoder's host twin)
 LZ4_FAST_TEST_EXPORTS = ["jfs_test_lz4_fast_host"]
@@ -64,7 +65,7 @@ ZSTD_FAST_TEST_EXPORTS = ["jfs_test_zstd_fast_host_seqs", "jfs_test_zstd_fast_se
 MODE_OFF, MODE_AUTO, MODE_FORCE = 0, 1, 2
 LZ4_PARSE_EXACT, LZ4_PARSE_FAST = 0, 1
 ZSTD_PARSE_EXACT, ZSTD_PARSE_FAST, ZSTD_PARSE_SEEKABLE = 0, 1, 2
-READ_SEEK_OFF, READ_SEEK_ON = 0, 1
+READ_SEEK_OFF, READ_SEEK_ON, READ_SEEK_SPARSE = 0, 1, 2
 ZSTD_SPLIT_FRAMES_MAX = 16384
 ZSTD_SEEK_CSUM_OFF, ZSTD_SEEK_CSUM_ON = 0, 1
 SEEK_PLAN_OK, SEEK_PLAN_MORE, SEEK_PLAN_NONE = 0, 1, 2
@@ -169,6 +170,12 @@ def load() -> ctypes.CDLL:
     lib.jfs_read_seek_mode.restype = ctypes.c_int
     lib.jfs_set_read_seek_mode.argtypes = [ctypes.c_int]
     lib.jfs_set_read_seek_mode.restype = ctypes.c_int
+    lib.jfs_set_read_seek_mode_ext.argtypes = [ctypes.c_int]
+    lib.jfs_set_read_seek_mode_ext.restype = ctypes.c_int
+    lib.jfs_zstd_decompress_ranges_device.argtypes = [vp, vp, vp, ctypes.c_int, vp, vp]
+    lib.jfs_zstd_decompress_ranges_device.restype = i64
+    lib.jfs_zstd_sparse_counts.argtypes = [vp, ctypes.c_int]
+    lib.jfs_zstd_sparse_counts.restype = ctypes.c_int
     lib.jfs_xxh64_device.argtypes = [vp, ctypes.c_int, vp, vp, vp]
     lib.jfs_xxh64_device.restype = i64
     lib.jfs_zstd_compress_seekable_csum_device.argtypes = [vp, ctypes.c_int, vp, vp]

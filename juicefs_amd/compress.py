@@ -345,13 +345,15 @@ def set_read_decode_mode(mode: str) -> str:
     return next(k for k, v in _READ_DECODE.items() if v == prev)
 
 
-_READ_SEEK = {"off": L.READ_SEEK_OFF, "on": L.READ_SEEK_ON}
+_READ_SEEK = {"off": L.READ_SEEK_OFF, "on": L.READ_SEEK_ON, "sparse": L.READ_SEEK_SPARSE}
 
 
 def read_seek_mode() -> str:
     """The seek switch of the read calls (jfs_read_seek_mode): "off", or "on" --
     every Zstd source is decoded through its seek table for the byte range the
-    reads ask of it (an object without one: prefix-decoded to their end)."""
+    reads ask of it (an object without one: prefix-decoded to their end), or
+    "sparse" -- for the list of ranges the reads ask of it, exactly the frames
+    they touch, tables with checksums read and verified too."""
     m = L.load().jfs_read_seek_mode()
     return next(k for k, v in _READ_SEEK.items() if v == m)
 
@@ -360,8 +362,8 @@ def set_read_seek_mode(mode: str) -> str:
     """Set it (process-wide, for calls that start afterwards) and return the
     previous value's name."""
     if mode not in _READ_SEEK:
-        raise ValueError(f"read seek mode {mode!r}: expected 'off' or 'on'")
-    prev = L.load().jfs_set_read_seek_mode(_READ_SEEK[mode])
+        raise ValueError(f"read seek mode {mode!r}: expected 'off', 'on' or 'sparse'")
+    prev = L.load().jfs_set_read_seek_mode_ext(_READ_SEEK[mode])
     return next(k for k, v in _READ_SEEK.items() if v == prev)
 
 

@@ -315,14 +315,14 @@ std::atomic<int> &read_decode() {
     return m;
 }
 
-// JFS_READ_SEEK (include/jfs_gpucodec.h): off (default) | on
+// JFS_READ_SEEK (include/jfs_gpucodec.h): off (default) | on | sparse
 std::atomic<int> &read_seek() {
     static std::atomic<int> m{[] {
         const char *e = getenv("JFS_READ_SEEK");
         if (!e) return JFS_READ_SEEK_OFF;
         std::string v(e);
         for (auto &ch : v) ch = (char)tolower((unsigned char)ch);
-        return v == "on" ? JFS_READ_SEEK_ON : JFS_READ_SEEK_OFF;
+        return v == "on" ? JFS_READ_SEEK_ON : v == "sparse" ? JFS_READ_SEEK_SPARSE : JFS_READ_SEEK_OFF;
     }()};
     return m;
 }
@@ -1916,7 +1916,7 @@ struct Chain {
 // Lays the call out and sizes slot 0 for it: JFS_OK or JFS_ERR_NO_MEMORY.
 int64_t chain_open(Chain &c, Lane &ln, int algo, int cipher, const std::vector<ChainSrc> &st, int ns,
                    const std::vector<ChainOut> &oo, const int32_t *seg_first, bool encode, bool out_crc, bool src_crc,
-                   bool prefix, int64_t npiece = 0, bool seek = false) {
+                   bool prefix, int64_t npiece = 0, bool seek = false, int64_t nrange = -1) {
     c.algo = algo;
     c.cipher = cipher;
     c.ns = ns;
@@ -1929,7 +1929,8 @@ int64_t chain_open(Chain &c, Lane &ln, int algo, int cipher, const std::vector<C
     int64_t nseg = 0;
     for (const ChainOut &o : oo) nseg += seg_first[o.idx + 1] - seg_first[o.idx];
     c.L = ChainLayout(c.off.tin, ns, c.n, c.no, nseg,
-                      ChainFlags{c.sealed, encode, out_crc, src_crc, prefix, npiece > 0, seek}, npiece);
+                      ChainFlags{c.sealed, encode, out_crc, src_crc, prefix, npiece > 0, seek, nrange >= 0}, npiece,
+                      std::max<int64_t>(nrange, 0));
     c.sl = &ln.slot[0];
     c.s1 = &ln.slot[1];
     c.ks = ln.s_k;
@@ -2006,7 +2007,9 @@ bool chain_lz4_scratch(const Chain &c, const jfs_dev_block *h_enc, bool fast) {
 // Queues open -> decode -> the opens' verdicts merged into the source lengths.
 // d_want (prefix modes: LZ4, and Zstd in JFS_READ_DECODE_PREFIX_ALL; else null): where each decode stops.
 // d_from (Zstd with JFS_READ_SEEK on; else null): with d_want the range each source is decoded for.
-int chain_decode(const Chain &c, const int32_t *d_want, int64_t max_want, const int32_t *d_from = nullptr) {
+// d_rf, d_rng (Zstd with JFS_READ_SEEK sparse; else null): the list of ranges each source is decoded for.
+int chain_decode(const Chain &c, const int32_t *d_want, int64_t max_want, const int32_t *d_from = nullptr,
+                 const int32_t *d_rf = nullptr, const jfs_range *d_rng = nullptr) {
     const jfs_dev_block *h_sdesc = c.host<jfs_dev_block>(c.L.sdesc), *d_sdesc = c.dev<jfs_dev_block>(c.L.sdesc);
     int32_t *d_srcn = c.dev<int32_t>(c.L.srcn), *d_open = c.dev<int32_t>(c.L.open);
     const int ns = c.ns;
@@ -2018,7 +2021,8 @@ int chain_decode(const Chain &c, const int32_t *d_want, int64_t max_want, const 
         lk = r == JFS_OK ? 0 : -1;
     } else if (lk == 0 && c.algo == JFS_ALGO_ZSTD && ns > 0) {
         // (with a cipher the frame headers are ciphertext on the host) it plans its own scratch
-        lk = d_from   ? jfs_launch_zstd_decode_range(d_sdesc, d_from, d_want, ns, d_srcn, c.ks)
+        lk = d_rf     ? jfs_launch_zstd_decode_ranges(d_sdesc, d_rf, d_rng, ns, d_srcn, c.ks)
+             : d_from ? jfs_launch_zstd_decode_range(d_sdesc, d_from, d_want, ns, d_srcn, c.ks)
              : d_want ? jfs_launch_zstd_decode_prefix(d_sdesc, ns, d_srcn, d_want, c.ks)
                       : jfs_launch_zstd_decode(d_sdesc, ns, d_srcn, nullptr, c.ks);
     }
@@ -2166,6 +2170,11 @@ int64_t compact_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *
 // of the call, the first byte a segment asks of it.  Every source then goes
 // through the range launcher, [from, need) clamped to its capacity, also in a
 // call that needs every source whole.
+// sparse (Zstd with JFS_READ_SEEK sparse; need and from are then null): every
+// source goes through the ranges launcher with the list chain_ranges makes of
+// the segments that reference it, staged beside want and from in the same H2D
+// copy; a source whose decoded frame fails its table checksum (-4) answers
+// JFS_ERR_CHECKSUM.
 // csum (the _csum calls, else null): per read of the call, where its
 // disk-cache checksum goes (null: none).  The piece prefix of the reads that
 // want one is staged with the plan, read_csum_flat_kernel runs behind the
@@ -2175,7 +2184,8 @@ int64_t compact_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *
 int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src, const uint8_t *const *src_keys,
                  const std::vector<ChainSrc> &st, int ns, const std::vector<int> &src_map, const jfs_iov *out,
                  const std::vector<ChainOut> &oo, const int32_t *seg_first, const jfs_compact_seg *seg, int64_t *src_n,
-                 int64_t *out_n, uint32_t *crc_got, const int64_t *need, const int64_t *from, uint8_t *const *csum) {
+                 int64_t *out_n, uint32_t *crc_got, const int64_t *need, const int64_t *from, uint8_t *const *csum,
+                 int nsrc = 0, int nout = 0, bool sparse = false) {
     LaneRun scope(dev, ln, algo * 2 + DECOMPRESS, (uint64_t)st.size());
     const int n = (int)st.size(), no = (int)oo.size();
     bool any_check = false;
@@ -2191,6 +2201,9 @@ int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src
     const bool seek = need && from && algo == JFS_ALGO_ZSTD && ns > 0;
     if (need && (algo == JFS_ALGO_LZ4 || algo == JFS_ALGO_ZSTD)) want = jfs_plan::chain_want(need, st, ns, &max_want, seek);
     const bool prefix = !want.empty();
+    sparse = sparse && algo == JFS_ALGO_ZSTD && ns > 0;
+    jfs_plan::ChainRanges lists;
+    if (sparse) lists = jfs_plan::chain_ranges(nsrc, nout, seg_first, seg, st, ns);
     std::vector<uint8_t> cs_want(no, 0);
     std::vector<int32_t> piece_first;
     std::vector<int64_t> cs_off;
@@ -2201,13 +2214,18 @@ int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src
         if (npiece < 0) return JFS_ERR_NO_MEMORY;
     }
     Chain c;
-    const int64_t rc = chain_open(c, ln, algo, cipher, st, ns, oo, seg_first, false, false, any_check, prefix, npiece, seek);
+    const int64_t rc = chain_open(c, ln, algo, cipher, st, ns, oo, seg_first, false, false, any_check, prefix, npiece, seek,
+                                  sparse ? (int64_t)lists.rng.size() : -1);
     if (rc != JFS_OK) return rc;
     const ChainLayout &L = c.L;
     memcpy(c.h + L.tf, tile_first.data(), (size_t)(no + 1) * 4);
     if (npiece > 0) memcpy(c.h + L.pf, piece_first.data(), (size_t)(no + 1) * 4);
     if (prefix) memcpy(c.h + L.want, want.data(), (size_t)ns * 4);
     if (seek) memcpy(c.h + L.from, jfs_plan::chain_lo(from, st, ns).data(), (size_t)ns * 4);
+    if (sparse) {
+        memcpy(c.h + L.rf, lists.first.data(), (size_t)(ns + 1) * 4);
+        if (!lists.rng.empty()) memcpy(c.h + L.rng, lists.rng.data(), lists.rng.size() * sizeof(jfs_range));
+    }
     std::vector<CopyJob> jobs;
     chain_stage_sources(c, src, src_keys, st, jobs);
     for (int k = 0; any_check && k < n; k++) {
@@ -2232,7 +2250,8 @@ int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src
         lk = jfs_launch_crc32c_lens(c.dev<jfs_dev_block>(L.scd), n, d_len, c.dev<uint32_t>(L.sseed),
                                     c.dev<uint32_t>(L.scrc), ks);
     if (lk == 0)
-        lk = chain_decode(c, prefix ? c.dev<int32_t>(L.want) : nullptr, max_want, seek ? c.dev<int32_t>(L.from) : nullptr);
+        lk = chain_decode(c, prefix ? c.dev<int32_t>(L.want) : nullptr, max_want, seek ? c.dev<int32_t>(L.from) : nullptr,
+                          sparse ? c.dev<int32_t>(L.rf) : nullptr, sparse ? c.dev<jfs_range>(L.rng) : nullptr);
     if (lk == 0 && any_check)
         lk = jfs_launch_verify_gate(c.dev<uint32_t>(L.scrc), d_len, c.dev<uint32_t>(L.exp), n, ns, d_srcn,
                                     c.dev<uint32_t>(L.got), ks);
@@ -2251,6 +2270,9 @@ int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src
         if (crc_got) crc_got[s.idx] = got;
         if (s.check && got != s.expect) src_n[s.idx] = JFS_ERR_CHECKSUM;  // before aead.Open and the codec
         else if (k < ns) src_n[s.idx] = chain_src_result(c, k);          // (else the host's answer stands)
+        // a decoded frame that fails its table checksum (only the ranges launcher answers -4)
+        if (sparse && k < ns && src_n[s.idx] == JFS_ERR_CORRUPT && c.host<int32_t>(L.srcn)[k] == -4)
+            src_n[s.idx] = JFS_ERR_CHECKSUM;
     }
     jobs.clear();
     for (int k = 0; k < no; k++) {
@@ -2858,6 +2880,11 @@ int jfs_set_read_seek_mode(int mode) {
     return read_seek().exchange(mode);
 }
 
+int jfs_set_read_seek_mode_ext(int mode) {
+    if (mode != JFS_READ_SEEK_OFF && mode != JFS_READ_SEEK_ON && mode != JFS_READ_SEEK_SPARSE) return -1;
+    return read_seek().exchange(mode);
+}
+
 int jfs_get_zstd_split_frames(void) { return zstd_split_frames().load(std::memory_order_relaxed); }
 
 int jfs_set_zstd_split_frames(int max_frames) {
@@ -2886,6 +2913,15 @@ int64_t jfs_zstd_decompress_range_device(const jfs_dev_block *d_blocks, const in
     stat_launch(JFS_ALGO_ZSTD, DECOMPRESS, nblk);
     return jfs_launch_zstd_decode_range(d_blocks, d_lo, d_hi, nblk, d_ret, (hipStream_t)stream) == 0 ? JFS_OK
                                                                                                      : JFS_ERR_HIP;
+}
+
+int64_t jfs_zstd_decompress_ranges_device(const jfs_dev_block *d_blocks, const int32_t *d_rng_first,
+                                          const jfs_range *d_rng, int nblk, int32_t *d_ret, void *stream) {
+    if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
+    if (nblk > 0 && (!d_blocks || !d_rng_first || !d_ret)) return JFS_ERR_INVALID;  // (d_rng: every list may be empty)
+    stat_launch(JFS_ALGO_ZSTD, DECOMPRESS, nblk);
+    return jfs_launch_zstd_decode_ranges(d_blocks, d_rng_first, d_rng, nblk, d_ret, (hipStream_t)stream) == 0 ? JFS_OK
+                                                                                                              : JFS_ERR_HIP;
 }
 
 int jfs_zstd_seek_csum_mode(void) { return zstd_seek_csum().load(std::memory_order_relaxed); }
@@ -3250,14 +3286,17 @@ static int64_t read_call(int algo, int cipher, int nsrc, const jfs_iov *src, con
     std::vector<int64_t> need, from;
     const int dmode = read_decode().load(std::memory_order_relaxed);
     // JFS_READ_SEEK: every Zstd source is decoded for [from, need), whatever the decode mode
-    const bool seek = algo == JFS_ALGO_ZSTD && read_seek().load(std::memory_order_relaxed) == JFS_READ_SEEK_ON;
-    if ((algo == JFS_ALGO_LZ4 && dmode != JFS_READ_DECODE_FULL) || (algo == JFS_ALGO_ZSTD && dmode == JFS_READ_DECODE_PREFIX_ALL) ||
-        seek)
+    const int smode = algo == JFS_ALGO_ZSTD ? read_seek().load(std::memory_order_relaxed) : JFS_READ_SEEK_OFF;
+    const bool seek = smode == JFS_READ_SEEK_ON, sparse = smode == JFS_READ_SEEK_SPARSE;
+    // (JFS_READ_SEEK sparse: the lists of ranges stand for both, read_run makes them)
+    if ((algo == JFS_ALGO_LZ4 && dmode != JFS_READ_DECODE_FULL) ||
+        (algo == JFS_ALGO_ZSTD && dmode == JFS_READ_DECODE_PREFIX_ALL && !sparse) || seek)
         need = jfs_plan::chain_need(nsrc, nout, seg_first, seg);
     if (seek) from = jfs_plan::chain_from(nsrc, nout, seg_first, seg);
     chain_dispatch(ds, algo, DECOMPRESS, st, oo, src_n, out_n, [&](DevCtx *dev, Lane &ln) {
         return read_run(dev, ln, algo, cipher, src, src_keys, st, ns, src_map, out, oo, seg_first, seg, src_n, out_n,
-                        crc_got, need.empty() ? nullptr : need.data(), from.empty() ? nullptr : from.data(), csum);
+                        crc_got, need.empty() ? nullptr : need.data(), from.empty() ? nullptr : from.data(), csum, nsrc, nout,
+                        sparse);
     });
     chain_stat(algo, DECOMPRESS, nsrc, [&](int i) { return src[i].src_len; }, src_n, ns > 0, steady_ns() - t0);
     return JFS_OK;

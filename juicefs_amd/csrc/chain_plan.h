@@ -148,6 +148,46 @@ inline std::vector<int32_t> chain_lo(const int64_t *from, const std::vector<Chai
     return lo;
 }
 
+// Sparse mode (JFS_READ_SEEK_SPARSE): per decoded source k, the ranges [src_off,
+// src_off + len) of the segments that reference it, clamped to its capacity
+// (what is left empty is dropped), sorted by lo, the ones that overlap or touch
+// merged: an ascending, disjoint list of live ranges.  Source k owns rng[first[k]
+// .. first[k + 1]); first has ns + 1 entries.  Holes are no one's; a source
+// nothing references has no range.
+struct ChainRanges {
+    std::vector<int32_t> first;
+    std::vector<jfs_range> rng;
+};
+
+inline ChainRanges chain_ranges(int nsrc, int nout, const int32_t *seg_first, const jfs_compact_seg *seg,
+                                const std::vector<ChainSrc> &st, int ns) {
+    std::vector<std::vector<jfs_range>> per(nsrc > 0 ? nsrc : 0);
+    std::vector<int64_t> cap(nsrc > 0 ? nsrc : 0, 0);
+    for (int k = 0; k < ns; k++) cap[st[k].idx] = std::min<int64_t>(st[k].cap, INT32_MAX);
+    for (int j = 0; j < nout; j++)
+        for (int k = seg_first[j]; k < seg_first[j + 1]; k++) {
+            const jfs_compact_seg &g = seg[k];
+            if (g.src < 0) continue;
+            const int64_t lo = std::min<int64_t>(std::max<int64_t>(g.src_off, 0), cap[g.src]);
+            const int64_t hi = std::min<int64_t>((int64_t)g.src_off + g.len, cap[g.src]);
+            if (hi > lo) per[g.src].push_back(jfs_range{(int32_t)lo, (int32_t)hi});
+        }
+    ChainRanges r;
+    r.first.assign(ns + 1, 0);
+    for (int k = 0; k < ns; k++) {
+        std::vector<jfs_range> &v = per[st[k].idx];
+        std::sort(v.begin(), v.end(), [](const jfs_range &a, const jfs_range &b) { return a.lo < b.lo; });
+        r.first[k] = (int32_t)r.rng.size();
+        size_t base = r.rng.size();
+        for (const jfs_range &x : v) {
+            if (r.rng.size() > base && x.lo <= r.rng.back().hi) r.rng.back().hi = std::max(r.rng.back().hi, x.hi);
+            else r.rng.push_back(x);
+        }
+    }
+    r.first[ns] = (int32_t)r.rng.size();
+    return r;
+}
+
 // ---------------------------------------------------------------------------
 // the reads' disk-cache checksums (disk_cache_file.go checksum()): the
 // big-endian CRC-32C of every 32 KiB piece of a read's gathered bytes
@@ -219,12 +259,14 @@ struct ChainFlags {
     bool prefix;   // per-source decode limits
     bool read_csum = false;  // disk-cache checksums of the reads (last: the initialisers above leave it off)
     bool seek = false;       // per-source lower ends of the decoded ranges (JFS_READ_SEEK)
+    bool sparse = false;     // per-source lists of ranges (JFS_READ_SEEK_SPARSE)
 };
 
 // The staged area, mirrored pinned / HBM: [stored bytes | meta | results |
 // outputs], byte offsets from the slot's base.  ns decoded sources, n staged
 // objects (n - ns of them only for their checksum), no outputs, nseg segments,
-// npiece 32 KiB pieces of the reads that asked for their checksums.
+// npiece 32 KiB pieces of the reads that asked for their checksums, nrange
+// ranges of the sparse lists.
 // An area the call does not use has no bytes and sits where the next one
 // starts.  The host writes [0, h2d), which goes to the device in one copy;
 // [results, out) comes back in one copy.  srcn, the source lengths, lies in
@@ -242,6 +284,7 @@ struct ChainLayout {
     int64_t want;                  // prefix mode's decode limits
     int64_t pf;                    // piece prefix of the reads' checksums, no + 1
     int64_t from;                  // seek mode's lower ends, beside want
+    int64_t rf, rng;               // sparse mode's lists: their running sums, ns + 1, and the nrange ranges
     int64_t srcn;                  // source lengths, ns + 1, preset
     // results, which only the device writes:
     int64_t open;        // the opens'
@@ -254,7 +297,7 @@ struct ChainLayout {
 
     ChainLayout() = default;
     ChainLayout(int64_t tin, int64_t ns, int64_t n, int64_t no, int64_t nseg, const ChainFlags &f,
-                int64_t npiece = 0) {
+                int64_t npiece = 0, int64_t nrange = 0) {
         int64_t o = align16(tin);
         auto take = [&o](bool used, int64_t count, int64_t size) {
             const int64_t at = o;
@@ -279,6 +322,8 @@ struct ChainLayout {
         want = take(f.prefix, ns, 4);
         pf = take(f.read_csum, no + 1, 4);
         from = take(f.seek, ns, 4);
+        rf = take(f.sparse, ns + 1, 4);
+        rng = take(f.sparse, nrange, (int64_t)sizeof(jfs_range));
         results = srcn = take(true, ns + 1, 4);
         h2d = o;
         open = take(f.sealed, ns, 4);

@@ -71,6 +71,10 @@ int jfs_launch_zstd_encode_seek_csum(const jfs_dev_block *d_blocks, int nblk, in
 // table checksum where the table has them
 int jfs_launch_zstd_decode_frames(const jfs_seek_frag *d_frags, const int32_t *d_lo, const int32_t *d_hi, int nblk,
                                   int32_t *d_ret, hipStream_t stream);
+// ranges decode (zstd_seek.hip): a whole object decoded for a list of ranges, exactly the frames some range
+// touches, through a table of either layout; input i owns d_rng[d_rng_first[i] .. d_rng_first[i + 1])
+int jfs_launch_zstd_decode_ranges(const jfs_dev_block *d_blocks, const int32_t *d_rng_first, const jfs_range *d_rng,
+                                  int nblk, int32_t *d_ret, hipStream_t stream);
 // jfs_zstd_load_range_batch: the bytes src[0, len) of a decoded block go to dst
 // where the fragment decode of that read answered `expect`
 struct jfs_range_pack {

@@ -231,5 +231,137 @@ JFS_ZSEEK_HD TableSel table_select(F fetch, int64_t table_len, int64_t object_le
     return s;
 }
 
+// ---- several ranges of one object, either layout ---------------
+// The table at the end of a whole object, as seek_footer finds it, with
+// descriptor byte 0x00 (entries of 8 bytes) or 0x80 (entries of 12); any other
+// descriptor is no table.  Every check of the two layouts above holds: the
+// magics, 1 <= nf <= MAX_FRAMES, the size field; what the entries must add up to
+// is seek_sums_ok's.  Nothing outside [0, src_len) is fetched.
+template <class F>
+JFS_ZSEEK_HD bool seek_footer_any(F fetch, int32_t src_len, int32_t *nf, int32_t *tpos, int32_t *entry) {
+    if (src_len < TABLE_FIXED + ENTRY) return false;
+    if (le32(fetch, src_len - 4) != SEEK_MAGIC) return false;
+    const uint32_t desc = fetch(src_len - 5);
+    if (desc != 0u && desc != DESC_CSUM) return false;
+    const int32_t ent = desc ? ENTRY_CSUM : ENTRY;
+    const uint32_t n = le32(fetch, src_len - 9);
+    if (n < 1u || n > (uint32_t)MAX_FRAMES || (int64_t)n > ((int64_t)src_len - TABLE_FIXED) / ent) return false;
+    const int32_t t = src_len - (ent * (int32_t)n + TABLE_FIXED);
+    if (le32(fetch, t) != SKIP_MAGIC) return false;
+    if (le32(fetch, t + 4) != (uint32_t)ent * n + 9u) return false;
+    *nf = (int32_t)n;
+    *tpos = t;
+    *entry = ent;
+    return true;
+}
+
+// entry k of the table at tpos whose entries take `entry` bytes: table_entry, inside the object
+template <class F>
+JFS_ZSEEK_HD void seek_entry_any(F fetch, int32_t tpos, int32_t entry, int32_t k, uint32_t *c, uint32_t *d, uint32_t *x) {
+    *c = le32(fetch, tpos + 8 + entry * k);
+    *d = le32(fetch, tpos + 12 + entry * k);
+    *x = entry == ENTRY_CSUM ? le32(fetch, tpos + 16 + entry * k) : 0u;
+}
+
+// A list of ranges (any type with int32 lo, hi) is ascending and disjoint as
+// given: lo <= hi for every range and hi <= the next one's lo.  Empty ranges
+// may stand anywhere.  range_follows is the check of one range against the one
+// in front of it (prev = null for the first).
+template <class R>
+JFS_ZSEEK_HD bool range_follows(const R *prev, const R &cur) {
+    return cur.lo <= cur.hi && (prev == nullptr || prev->hi <= cur.lo);
+}
+template <class R>
+JFS_ZSEEK_HD bool ranges_ok(const R *rng, int32_t nr) {
+    for (int32_t r = 0; r < nr; r++)
+        if (!range_follows(r > 0 ? &rng[r - 1] : (const R *)nullptr, rng[r])) return false;
+    return true;
+}
+
+// a range is live when something of it is left after the clamps
+template <class R>
+JFS_ZSEEK_HD bool range_live(const R &r, int32_t dst_cap) { return range_hi(r.hi, dst_cap) > range_lo(r.lo); }
+
+// Frame k, content [d0, d0 + d): selected iff d > 0 and some live range has
+// lo' < d0 + d and hi' > d0.  The clamps keep the list's order, so hi' does not
+// fall along it: a binary search finds the first range with hi' > d0, and the
+// ranges from there on are tried while they start inside the frame (only
+// ranges that are not live are passed over).
+template <class R>
+JFS_ZSEEK_HD bool frame_in_ranges(const R *rng, int32_t nr, int32_t dst_cap, uint64_t d0, uint32_t d) {
+    if (d == 0u) return false;
+    int32_t a = 0, z = nr;
+    while (a < z) {
+        const int32_t m = a + ((z - a) >> 1);
+        if ((int64_t)range_hi(rng[m].hi, dst_cap) > (int64_t)d0) z = m;
+        else a = m + 1;
+    }
+    const int64_t end = (int64_t)d0 + d;
+    for (; a < nr && (int64_t)range_lo(rng[a].lo) < end; a++)
+        if (range_live(rng[a], dst_cap)) return true;
+    return false;
+}
+
+struct RangesSel {
+    int32_t bad;        // 1: the list is not ascending and disjoint (nothing else is filled)
+    int32_t live;       // its live ranges
+    int32_t top;        // H, the largest hi' of the live ranges (0 without one)
+    int32_t table;      // 1: a valid table of either layout
+    int32_t checksums;  // 1: entries of 12 bytes
+    int32_t nf;
+    uint32_t total;     // D
+    int32_t count;      // selected frames
+};
+
+// The whole answer for one object and its list, serially: the rule the sparse
+// scan kernel (zstd_seek.hip) applies 64 frames a round.  emit(k, coff, doff, c,
+// d, x) is called for every selected frame in ascending order: its number, where
+// it starts (compressed, content) and its entry.  With D > dst_cap the selection
+// is computed all the same: the caller answers -2 first.
+template <class F, class R, class E>
+JFS_ZSEEK_HD RangesSel ranges_select(F fetch, int32_t src_len, int32_t dst_cap, const R *rng, int32_t nr, E emit) {
+    RangesSel s;
+    s.bad = 0; s.live = 0; s.top = 0; s.table = 0; s.checksums = 0; s.nf = 0; s.total = 0; s.count = 0;
+    if (!ranges_ok(rng, nr)) {
+        s.bad = 1;
+        return s;
+    }
+    for (int32_t r = 0; r < nr; r++)
+        if (range_live(rng[r], dst_cap)) {
+            s.live++;
+            const int32_t h = range_hi(rng[r].hi, dst_cap);
+            s.top = h > s.top ? h : s.top;
+        }
+    int32_t nf = 0, tpos = 0, entry = 0;
+    if (!seek_footer_any(fetch, src_len, &nf, &tpos, &entry)) return s;
+    uint64_t cs = 0, ds = 0;
+    uint32_t zeros = 0;
+    for (int32_t k = 0; k < nf; k++) {
+        uint32_t c, d, x;
+        seek_entry_any(fetch, tpos, entry, k, &c, &d, &x);
+        zeros += c == 0u;
+        cs += c;
+        ds += d;
+    }
+    if (!seek_sums_ok(cs, ds, zeros, tpos)) return s;
+    s.table = 1;
+    s.checksums = entry == ENTRY_CSUM;
+    s.nf = nf;
+    s.total = (uint32_t)ds;
+    if (s.live == 0) return s;
+    cs = ds = 0;
+    for (int32_t k = 0; k < nf; k++) {
+        uint32_t c, d, x;
+        seek_entry_any(fetch, tpos, entry, k, &c, &d, &x);
+        if (frame_in_ranges(rng, nr, dst_cap, ds, d)) {
+            emit(k, (uint32_t)cs, (uint32_t)ds, c, d, x);
+            s.count++;
+        }
+        cs += c;
+        ds += d;
+    }
+    return s;
+}
+
 }  // namespace zseek
 }  // namespace jfs

@@ -203,6 +203,29 @@ def zstd_decompress_range(desc: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor
                                                      _stream_ptr(stream)), "jfs_zstd_decompress_range_device")
 
 
+def zstd_decompress_ranges(desc: torch.Tensor, rng_first: torch.Tensor, rng: torch.Tensor, ret: torch.Tensor, stream=None):
+    """jfs_zstd_decompress_ranges_device: input i is decoded for the output
+    ranges rng[rng_first[i] .. rng_first[i + 1]) (int32 device tensors: n + 1
+    running sums, and (lo, hi) pairs, flat or of shape (R, 2)) -- exactly the
+    frames some range touches, through a seek table of either layout, decoded
+    frames checked against a 12-byte table's checksums; a prefix decode to the
+    largest hi when the object has no table."""
+    n = desc.numel() // DESC_DTYPE.itemsize
+    assert rng_first.dtype == torch.int32 and rng.dtype == torch.int32 and rng_first.numel() >= n + 1
+    assert rng.is_contiguous() and rng.numel() % 2 == 0
+    _check(L.load().jfs_zstd_decompress_ranges_device(desc.data_ptr(), rng_first.data_ptr(),
+                                                      rng.data_ptr() if rng.numel() else None, n, ret.data_ptr(),
+                                                      _stream_ptr(stream)), "jfs_zstd_decompress_ranges_device")
+
+
+def zstd_sparse_counts(reset: bool = False):
+    """(inputs the ranges decode took through a seek table, frames it selected,
+    frames whose checksum it compared) on the current device."""
+    out = (ctypes.c_uint64 * 3)()
+    _check(L.load().jfs_zstd_sparse_counts(out, 1 if reset else 0), "jfs_zstd_sparse_counts")
+    return tuple(int(x) for x in out)
+
+
 def xxh64(desc: torch.Tensor, hash: torch.Tensor, ret: torch.Tensor | None = None, stream=None):
     """jfs_xxh64_device: hash[i] (an int64 device tensor holding the uint64
     bits) = XXH64, seed 0, of descriptor i's src[0, src_len); ret[i] (int32,
