@@ -2962,19 +2962,17 @@ int64_t jfs_zstd_seek_plan(const uint8_t *tail, int64_t tail_len, int64_t object
         return JFS_ERR_INVALID;
     memset(out, 0, sizeof(*out));
     out->status = JFS_SEEK_PLAN_NONE;
-    if (tail_len < 9) return JFS_OK;
+    if (tail_len < zs::FOOTER) return JFS_OK;
     // the footer: the frame count and the entry size place the table
-    const uint8_t *f = tail + tail_len - 9;
-    const auto ffetch = [f](int32_t p) { return (uint32_t)f[p]; };
-    if (zs::le32(ffetch, 5) != zs::SEEK_MAGIC || (f[4] != 0u && f[4] != zs::DESC_CSUM)) return JFS_OK;
-    const uint32_t n = zs::le32(ffetch, 0);
-    const int64_t entry = f[4] ? zs::ENTRY_CSUM : zs::ENTRY;
-    if (n < 1u || n > (uint32_t)zs::MAX_FRAMES || entry * n + zs::TABLE_FIXED > object_len) return JFS_OK;
-    const int64_t table_len = entry * n + zs::TABLE_FIXED;
+    const uint8_t *f = tail + tail_len - zs::FOOTER;
+    int32_t n = 0, entry = 0;
+    if (!zs::footer_peek([f](int32_t p) { return (uint32_t)f[p]; }, zs::FOOTER, true, &n, &entry)) return JFS_OK;
+    const int64_t table_len = (int64_t)entry * n + zs::TABLE_FIXED;
+    if (table_len > object_len) return JFS_OK;
     if (tail_len < table_len) {
         out->status = JFS_SEEK_PLAN_MORE;
-        out->checksums = f[4] != 0u;
-        out->nf = (int32_t)n;
+        out->checksums = entry == zs::ENTRY_CSUM;
+        out->nf = n;
         out->table_off = object_len - table_len;
         out->table_len = table_len;
         return JFS_OK;

@@ -1,5 +1,5 @@
 // Stand-alone driver of the several-ranges selection of
-// juicefs_amd/csrc/zstd_seek.h (seek_footer_any / ranges_ok / frame_in_ranges /
+// juicefs_amd/csrc/zstd_seek.h (seek_table / ranges_ok / frame_in_ranges /
 // ranges_select), built with AddressSanitizer + UBSan by
 // tests/test_zstd_seek_ranges.py.  The fetch it hands the parser counts every
 // index outside [0, src_len).
