@@ -698,6 +698,104 @@ int64_t jfs_compact_batch(int algo, int nsrc, const jfs_iov *src, int nout, cons
                           const int32_t *seg_first /* nout+1 */, const jfs_compact_seg *seg, int64_t *src_n,
                           int64_t *out_n, uint32_t *crc /* may be NULL */, uint32_t device_mask);
 
+/* ---- Spliced compaction of seekable Zstd objects --------------
+ * Assembling seekable objects from frames that already exist, device-resident.
+ * Output j is frames d_frames[frame_first .. frame_first + frame_count), in
+ * order, and then the seek table.  A PASS frame (unit < 0) is the c stored bytes
+ * at src, copied; a FRESH frame (unit >= 0) is the first d_unit_len[unit] bytes
+ * at src, the buffer encode unit `unit` was written to, so its length is read
+ * on the device from the encoder's results.  d = the frame's content bytes and
+ * x = its checksum word, which go to the table; for a FRESH frame x is ignored
+ * and the low word of d_unit_hash[unit] is written (d_unit_hash == NULL: the
+ * 8-byte layout, descriptor 0x00; else the 12-byte layout, descriptor 0x80).
+ * `out` = the index j of the output that owns the frame.
+ * d_ret[j], in this order of precedence:
+ *   a bad record (NULL dst with frames, dst_cap < 0, frame_first < 0,
+ *     frame_count outside 1 .. 16384, a frame whose `out` is not j, NULL src, d <
+ *     0, a PASS frame with c outside 1 .. 2^24, a FRESH result above 2^24): -1;
+ *   a FRESH unit whose result is JFS_CHAIN_FAILED (INT32_MIN: its gather
+ *     failed): JFS_CHAIN_FAILED, as the gather's verdict replaces an encoder's;
+ *   else a FRESH unit whose result is <= 0: that result, of the first such frame;
+ *   the frames and the table take more than dst_cap: 0;
+ *   else the object's size, sum of the frames' bytes + E frame_count + 17 with
+ *     E = 8 or 12: dst[0, size) holds the frames back to back and the table
+ *         u32 0x184D2A5E | u32 E nf + 9 | nf x (u32 c, u32 d[, u32 x]) | u32 nf
+ *         | u8 0x00 or 0x80 | u32 0x8F92EAB1,   all little-endian.
+ * No byte of dst is written for an output whose d_ret[j] <= 0, and none outside
+ * dst[0, size) otherwise; no byte outside a frame's [src, src + length) is read.
+ * src and dst may have any alignment.  nframes: a HOST value, the number of
+ * records in d_frames (it sizes the launch); every record belongs to one
+ * output.  `unit` indexes d_unit_len (and d_unit_hash) unchecked: their length
+ * is the caller's.  Asynchronous on `stream` (per-device scratch of 4 bytes per frame,
+ * ordered across streams by an event). */
+typedef struct jfs_splice_frame {
+    const uint8_t *src;
+    int32_t c;    /* PASS: stored bytes of the frame */
+    int32_t d;    /* content bytes */
+    uint32_t x;   /* PASS: checksum word for a 12-byte table */
+    int32_t unit; /* < 0: PASS; else FRESH, the index into d_unit_len / d_unit_hash */
+    int32_t out;  /* the output this frame belongs to */
+    int32_t reserved;
+} jfs_splice_frame;
+typedef struct jfs_splice_out {
+    uint8_t *dst;
+    int32_t dst_cap;
+    int32_t frame_first, frame_count;
+    int32_t reserved;
+} jfs_splice_out;
+int64_t jfs_zstd_splice_device(const jfs_splice_out *d_out, int nout, const jfs_splice_frame *d_frames, int nframes,
+                               const int32_t *d_unit_len, const uint64_t *d_unit_hash /* NULL for the 8-byte layout */,
+                               int32_t *d_ret, void *stream);
+
+/* Splice switch of jfs_compact_batch.  JFS_COMPACT_SPLICE_OFF (default): nothing
+ * changes.  JFS_COMPACT_SPLICE_ON: a call with algo = Zstd, while the Zstd parse
+ * mode is JFS_ZSTD_PARSE_SEEKABLE, cuts every output j with total > 131072 into
+ * pieces [131072 f, min(131072 (f + 1), total)).  A piece passes when one
+ * segment covers it whole, that segment's source has a valid seek table (as for
+ * jfs_zstd_decompress_ranges_device, with D <= src[i].dst_cap), the piece is
+ * exactly the content of one frame k of it (D_k == src_off + (lo - dst_off),
+ * d_k == the piece's bytes > 0), c_k <= d_k + 21, and, with
+ * JFS_ZSTD_SEEK_CSUM_ON, the source table has checksums too.  An output with at
+ * least one such piece is spliced; a call without one is the switch off.
+ *   Spliced out[j]: a Zstd object that ZSTD_decompress, jfs_decompress and every
+ *     decoder here decode to the gathered bytes, with a valid seek table of the
+ *     current layout (8-byte entries, or 12-byte ones with
+ *     JFS_ZSTD_SEEK_CSUM_ON).  Its passing frames are the source's stored bytes
+ *     (and table checksum word); every other frame is what
+ *     jfs_zstd_compress_seekable_device returns for that piece alone.  out_n[j]
+ *     is its size, never above jfs_compress_bound(ZSTD, total).
+ *   dst_cap < CompressBound(total) is JFS_ERR_SHORT_BUFFER as before, and the
+ *     error codes are today's: JFS_ERR_CORRUPT when a source that a re-encoded
+ *     piece needs failed or is too short.
+ *   A damaged passing frame is copied and NOT noticed: with the switch on,
+ *     compaction does not validate bytes it does not decode.  A caller that
+ *     needs every source validated checks the object CRC-32C or leaves the
+ *     switch off.
+ *   Unspliced out[j] of such a call: byte-identical to the switch off.
+ *   src_n[i]: only the frames the re-encoded pieces and the unspliced outputs
+ *     read are decoded (jfs_zstd_decompress_ranges_device over the merged
+ *     ranges, every decoded frame checked against a 12-byte table).  For a
+ *     source with a valid table src_n[i] = D, the table's content size, when
+ *     every selected frame decoded and verified -- also for a source that is
+ *     not decoded at all; else the mapped error, -4 being JFS_ERR_CHECKSUM as
+ *     in the JFS_READ_SEEK_SPARSE reads.  For a source without a table it is
+ *     what those reads report, min(size, need).
+ *   crc, jfs_stats: as before.
+ * jfs_compact_seal_batch (the tables are ciphertext on the host), LZ4, "none"
+ * and the read calls do not consult the switch.  The initial value is read once
+ * from JFS_COMPACT_SPLICE = "off" | "on" (case-insensitive; anything else, or
+ * unset: off).  jfs_set_compact_splice_mode returns the previous value, or -1
+ * for an unknown one (which changes nothing); it is atomic and applies to calls
+ * that start afterwards. */
+#define JFS_COMPACT_SPLICE_OFF 0
+#define JFS_COMPACT_SPLICE_ON 1
+int jfs_compact_splice_mode(void);
+int jfs_set_compact_splice_mode(int mode);
+/* Diagnostics of the spliced calls since the last reset, process-wide: out[0] =
+ * outputs spliced, out[1] = frames passed, out[2] = frames re-encoded inside
+ * spliced outputs, out[3] = compressed bytes passed.  0, or -1 (NULL). */
+int jfs_compact_splice_counts(uint64_t out[4], int reset);
+
 /* jfs_compact_batch for a volume with object encryption: every stored object
  * is an envelope (see jfs_compress_seal_batch), so the chain is open -> decode
  * -> gather -> encode -> seal, on one device, and only sealed bytes cross the

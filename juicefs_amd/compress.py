@@ -385,6 +385,36 @@ _SEEK_CSUM = {"off": L.ZSTD_SEEK_CSUM_OFF, "on": L.ZSTD_SEEK_CSUM_ON}
 _PLAN_STATUS = {L.SEEK_PLAN_OK: "ok", L.SEEK_PLAN_MORE: "more", L.SEEK_PLAN_NONE: "none"}
 
 
+_COMPACT_SPLICE = {"off": L.COMPACT_SPLICE_OFF, "on": L.COMPACT_SPLICE_ON}
+
+
+def compact_splice_mode() -> str:
+    """The splice switch of the Zstd compaction call (jfs_compact_splice_mode):
+    "off", or "on" -- while the Zstd parse mode is "seekable", a 128 KiB piece
+    of an output that is exactly one frame of a seekable source is copied as
+    stored bytes, and only the other pieces are decoded and re-encoded."""
+    m = L.load().jfs_compact_splice_mode()
+    return next(k for k, v in _COMPACT_SPLICE.items() if v == m)
+
+
+def set_compact_splice_mode(mode: str) -> str:
+    """Set it (process-wide, for calls that start afterwards) and return the
+    previous value's name."""
+    if mode not in _COMPACT_SPLICE:
+        raise ValueError(f"compact splice mode {mode!r}: expected 'off' or 'on'")
+    prev = L.load().jfs_set_compact_splice_mode(_COMPACT_SPLICE[mode])
+    return next(k for k, v in _COMPACT_SPLICE.items() if v == prev)
+
+
+def compact_splice_counts(reset: bool = False):
+    """(outputs spliced, frames passed, frames re-encoded inside spliced
+    outputs, compressed bytes passed) since the last reset."""
+    out = (ctypes.c_uint64 * 4)()
+    if L.load().jfs_compact_splice_counts(out, 1 if reset else 0) != 0:
+        raise RuntimeError("jfs_compact_splice_counts failed")
+    return tuple(int(x) for x in out)
+
+
 def zstd_seek_csum_mode() -> str:
     """The checksum switch of the seekable parse mode (jfs_zstd_seek_csum_mode):
     "off", or "on" -- while the Zstd parse mode is "seekable" the compress calls

@@ -36,6 +36,7 @@
 #include "blockgen.h"
 #include "chain_plan.h"
 #include "jfs_internal.h"
+#include "splice_plan.h"
 #include "zstd_seek.h"
 
 #define JFS_VERSION "jfs-gpucodec 0.1.0 (gfx950)"
@@ -361,6 +362,17 @@ std::atomic<int> &zstd_seek_csum() {
         std::string v(e);
         for (auto &ch : v) ch = (char)tolower((unsigned char)ch);
         return v == "on" ? JFS_ZSTD_SEEK_CSUM_ON : JFS_ZSTD_SEEK_CSUM_OFF;
+    }()};
+    return m;
+}
+// JFS_COMPACT_SPLICE (include/jfs_gpucodec.h): off (default) | on
+std::atomic<int> &compact_splice() {
+    static std::atomic<int> m{[] {
+        const char *e = getenv("JFS_COMPACT_SPLICE");
+        if (!e) return JFS_COMPACT_SPLICE_OFF;
+        std::string v(e);
+        for (auto &ch : v) ch = (char)tolower((unsigned char)ch);
+        return v == "on" ? JFS_COMPACT_SPLICE_ON : JFS_COMPACT_SPLICE_OFF;
     }()};
     return m;
 }
@@ -1913,10 +1925,17 @@ struct Chain {
     uint8_t *gat(int k) const { return off.gat.empty() ? d_out(k) : sl->sp + off.gat[k]; }
 };
 
+// What a call adds to the layout for itself: bytes of records in the H2D part
+// (ChainLayout::xmeta), of results (xres), of mirrored area behind the outputs
+// and of device scratch behind the decoded sources and gathered blocks.
+struct ChainExtra {
+    int64_t meta = 0, res = 0, out = 0, scratch = 0;
+};
+
 // Lays the call out and sizes slot 0 for it: JFS_OK or JFS_ERR_NO_MEMORY.
 int64_t chain_open(Chain &c, Lane &ln, int algo, int cipher, const std::vector<ChainSrc> &st, int ns,
                    const std::vector<ChainOut> &oo, const int32_t *seg_first, bool encode, bool out_crc, bool src_crc,
-                   bool prefix, int64_t npiece = 0, bool seek = false, int64_t nrange = -1) {
+                   bool prefix, int64_t npiece = 0, bool seek = false, int64_t nrange = -1, const ChainExtra &x = {}) {
     c.algo = algo;
     c.cipher = cipher;
     c.ns = ns;
@@ -1930,12 +1949,12 @@ int64_t chain_open(Chain &c, Lane &ln, int algo, int cipher, const std::vector<C
     for (const ChainOut &o : oo) nseg += seg_first[o.idx + 1] - seg_first[o.idx];
     c.L = ChainLayout(c.off.tin, ns, c.n, c.no, nseg,
                       ChainFlags{c.sealed, encode, out_crc, src_crc, prefix, npiece > 0, seek, nrange >= 0}, npiece,
-                      std::max<int64_t>(nrange, 0));
+                      std::max<int64_t>(nrange, 0), x.meta, x.res);
     c.sl = &ln.slot[0];
     c.s1 = &ln.slot[1];
     c.ks = ln.s_k;
-    if (!c.sl->ensure(c.L.out + c.off.tout)) return JFS_ERR_NO_MEMORY;
-    if (c.codec && !c.sl->ensure_split(std::max<int64_t>(c.off.scratch, 16))) return JFS_ERR_NO_MEMORY;
+    if (!c.sl->ensure(c.L.out + c.off.tout + x.out)) return JFS_ERR_NO_MEMORY;
+    if (c.codec && !c.sl->ensure_split(std::max<int64_t>(c.off.scratch + x.scratch, 16))) return JFS_ERR_NO_MEMORY;
     c.h = c.sl->h;
     c.d = c.sl->d;
     return JFS_OK;
@@ -2148,6 +2167,158 @@ int64_t compact_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *
         if (crc) crc[j] = res[k] >= 0 ? c.host<uint32_t>(L.ocrc)[k] : 0u;
     }
     par_copy(jobs);
+    return JFS_OK;
+}
+
+// jfs_compact_splice_counts: outputs spliced, frames passed, frames re-encoded inside them, bytes passed
+std::atomic<uint64_t> g_splice_counts[4];
+
+// Compaction with untouched frames spliced (JFS_COMPACT_SPLICE on; Zstd in the
+// seekable parse mode, no cipher; P, splice_plan.h's answer, splices at least
+// one of oo).  The chain's outputs are P's encode units -- every unspliced
+// output whole, every FRESH piece of a spliced one -- so staging, gather and
+// encode are compact_run's over the derived plan; a spliced output's object is
+// assembled behind them (zstd_splice.hip) in an area of its own behind the
+// units'.  On the lane's stream: one H2D (stored sources, the derived plan, the
+// lists of ranges, the splice records), the ranges decode of what the derived
+// plan still reads, gather, seekable encode of all units (csum: with the 12-byte
+// table for the whole outputs, and XXH64 of the FRESH pieces), the gather's
+// verdicts merged, scan and copy, CRC-32C of the finished objects, results D2H,
+// then exactly the object bytes.  Results as compact_run's; src_n of a source
+// with a valid table is the table's content size (the header has the contract).
+int64_t compact_splice_run(DevCtx *dev, Lane &ln, const jfs_iov *src, const std::vector<ChainSrc> &ss,
+                           const std::vector<int> &src_map, int nsrc, const jfs_iov *out, const std::vector<ChainOut> &oo,
+                           const jfs_plan::SplicePlan &P, bool csum, int64_t *src_n, int64_t *out_n, uint32_t *crc) {
+    const int algo = JFS_ALGO_ZSTD;
+    LaneRun scope(dev, ln, algo * 2 + COMPRESS, (uint64_t)(ss.size() + oo.size()));
+    const int ns = (int)ss.size(), no = (int)oo.size(), nu = (int)P.units.size(), nfr = (int)P.frames.size();
+    const int nout = (int)P.frame_first.size() - 1;
+    // output j: its place in oo; its whole unit, or its place among the spliced ones
+    std::vector<int> oo_of(nout, -1), unit_of(nout, -1), sp_of(nout, -1), sp;
+    for (int k = 0; k < no; k++) {
+        oo_of[oo[k].idx] = k;
+        if (P.spliced(oo[k].idx)) {
+            sp_of[oo[k].idx] = (int)sp.size();
+            sp.push_back(k);
+        }
+    }
+    const int nsp = (int)sp.size();
+    std::vector<ChainOut> uu(nu);
+    for (int u = 0; u < nu; u++) {
+        const jfs_plan::SpliceUnit &q = P.units[u];
+        const int64_t cap = q.piece < 0 ? oo[oo_of[q.out]].cap : jfs_compress_bound(JFS_ALGO_ZSTD, q.total);
+        uu[u] = ChainOut{u, q.total, cap, cap, 0};
+        if (q.piece < 0) unit_of[q.out] = u;
+    }
+    std::vector<int64_t> xo(nsp + 1, 0);  // the spliced objects' places behind the units' area
+    for (int s = 0; s < nsp; s++) xo[s + 1] = xo[s] + align16(oo[sp[s]].cap);
+    const jfs_plan::ChainRanges lists = jfs_plan::splice_ranges(P, nsrc, ss, ns);
+    const int64_t blk = (int64_t)sizeof(jfs_dev_block);
+    // records: splice outputs | frames | XXH64 descriptors of the units (csum) | checksum descriptors (crc)
+    const int64_t m_fr = align16(nsp * (int64_t)sizeof(jfs_splice_out)),
+                  m_xd = m_fr + align16(nfr * (int64_t)sizeof(jfs_splice_frame)), m_cd = m_xd + (csum ? align16(nu * blk) : 0);
+    // results: the spliced outputs' verdicts | their checksums; scratch: frame offsets | unit hashes
+    const int64_t r_crc = align16(nsp * 4ll), s_hash = align16(nfr * 4ll);
+    ChainExtra x;
+    x.meta = m_cd + (crc ? align16(nsp * blk) : 0);
+    x.res = r_crc + (crc ? align16(nsp * 4ll) : 0);
+    x.out = xo[nsp];
+    x.scratch = s_hash + align16(nu * 8ll);
+    Chain c;
+    const int64_t rc = chain_open(c, ln, algo, -1, ss, ns, uu, P.seg_first.data(), true, crc != nullptr, false, false, 0,
+                                  false, (int64_t)lists.rng.size(), x);
+    if (rc != JFS_OK) return rc;
+    const ChainLayout &L = c.L;
+    const int64_t xout = L.out + c.off.tout;  // the spliced objects' area, mirrored like the outputs'
+    std::vector<CopyJob> jobs;
+    chain_stage_sources(c, src, nullptr, ss, jobs);
+    par_copy(jobs);
+    chain_stage_plan(c, uu, src_map, P.seg_first.data(), P.seg.data());
+    memcpy(c.h + L.rf, lists.first.data(), (size_t)(ns + 1) * 4);
+    if (!lists.rng.empty()) memcpy(c.h + L.rng, lists.rng.data(), lists.rng.size() * sizeof(jfs_range));
+    jfs_dev_block *h_enc = c.host<jfs_dev_block>(L.enc), *h_xd = c.host<jfs_dev_block>(L.xmeta + m_xd);
+    for (int u = 0; u < nu; u++) {
+        h_enc[u] = jfs_dev_block{c.gat(u), c.d_out(u), (int32_t)uu[u].total, (int32_t)uu[u].cap};
+        if (crc) c.host<jfs_dev_block>(L.ocd)[u] = jfs_dev_block{c.d_out(u), nullptr, 0, 0};
+        // only a FRESH piece is hashed here: a whole output's table is the checksummed encoder's
+        if (csum) h_xd[u] = P.units[u].piece < 0 ? jfs_dev_block{nullptr, nullptr, 0, 0}
+                                                 : jfs_dev_block{c.gat(u), nullptr, (int32_t)uu[u].total, 0};
+    }
+    jfs_splice_out *h_so = c.host<jfs_splice_out>(L.xmeta);
+    jfs_splice_frame *h_fr = c.host<jfs_splice_frame>(L.xmeta + m_fr);
+    for (int s = 0; s < nsp; s++) {
+        const int j = oo[sp[s]].idx;
+        const int32_t f0 = P.frame_first[j], f1 = P.frame_first[j + 1];
+        h_so[s] = jfs_splice_out{c.d + xout + xo[s], (int32_t)oo[sp[s]].cap, f0, f1 - f0, 0};
+        if (crc) c.host<jfs_dev_block>(L.xmeta + m_cd)[s] = jfs_dev_block{c.d + xout + xo[s], nullptr, 0, 0};
+        for (int32_t f = f0; f < f1; f++) {
+            const jfs_plan::SpliceFrame &q = P.frames[f];
+            // a PASS frame lies in its staged source (a source with a table is never answered on the host)
+            const uint8_t *from = q.src >= 0 ? c.d_in(src_map[q.src]) + q.coff : c.d_out(q.unit);
+            h_fr[f] = jfs_splice_frame{from, (int32_t)q.c, (int32_t)q.d, q.x, q.unit, s, 0};
+        }
+    }
+    hipStream_t ks = c.ks;
+    if (hipMemcpyAsync(c.d, c.h, (size_t)L.h2d, hipMemcpyHostToDevice, ks) != hipSuccess) return JFS_ERR_HIP;
+    const jfs_dev_block *d_sdesc = c.dev<jfs_dev_block>(L.sdesc), *d_enc = c.dev<jfs_dev_block>(L.enc);
+    int32_t *d_srcn = c.dev<int32_t>(L.srcn), *d_ret = c.dev<int32_t>(L.ret), *d_sret = c.dev<int32_t>(L.xres);
+    uint32_t *d_off = (uint32_t *)(c.sl->sp + c.off.scratch);
+    uint64_t *d_hash = (uint64_t *)(c.sl->sp + c.off.scratch + s_hash);
+    const int32_t max_total = jfs_plan::chain_max_total(uu);
+    auto gather = [&](int pass) {
+        return jfs_launch_gather(d_sdesc, d_srcn, ns + 1, c.dev<jfs_compact_out>(L.plan), nu, c.dev<jfs_compact_seg>(L.seg),
+                                 max_total, d_ret, pass, ks);
+    };
+    int lk = chain_decode(c, nullptr, 0, nullptr, c.dev<int32_t>(L.rf), c.dev<jfs_range>(L.rng));
+    if (lk == 0) lk = gather(0);
+    // a piece of at most 128 KiB comes back as one frame and no table in either layout
+    if (lk == 0) lk = launch_kernel(algo, COMPRESS, d_enc, nu, d_ret, ks, csum ? ZSTD_ENCODE_SEEK_CSUM : JFS_ZSTD_PARSE_SEEKABLE);
+    if (lk == 0 && csum) lk = jfs_launch_xxh64(c.dev<jfs_dev_block>(L.xmeta + m_xd), nu, d_hash, nullptr, ks);
+    // the encoder ran on every unit: a failed gather's verdict replaces its result, and the scan reads it there
+    if (lk == 0) lk = gather(1);
+    if (lk == 0)
+        lk = jfs_launch_zstd_splice(c.dev<jfs_splice_out>(L.xmeta), nsp, c.dev<jfs_splice_frame>(L.xmeta + m_fr), nfr, d_ret,
+                                    csum ? d_hash : nullptr, d_off, d_sret, ks);
+    if (lk == 0 && crc) lk = jfs_launch_crc32c_lens(c.dev<jfs_dev_block>(L.ocd), nu, d_ret, nullptr, c.dev<uint32_t>(L.ocrc), ks);
+    if (lk == 0 && crc)
+        lk = jfs_launch_crc32c_lens(c.dev<jfs_dev_block>(L.xmeta + m_cd), nsp, d_sret, nullptr,
+                                    c.dev<uint32_t>(L.xres + r_crc), ks);
+    if (!chain_results(c, lk, L.out)) return JFS_ERR_HIP;
+    const int32_t *h_ret = c.host<int32_t>(L.ret), *h_sret = c.host<int32_t>(L.xres);
+    std::vector<int64_t> res(no);
+    std::vector<uint8_t *> at(no);  // where output k's object lies in the pinned mirror
+    for (int k = 0; k < no; k++) {
+        const int j = oo[k].idx, s = sp_of[j];
+        const int32_t raw = s >= 0 ? h_sret[s] : h_ret[unit_of[j]];
+        // (an object that outgrows its capacity: the bound keeps it out of reach)
+        res[k] = s >= 0 && raw == 0 ? JFS_ERR_SHORT_BUFFER : chain_out_result(algo, true, raw);
+        at[k] = s >= 0 ? c.h + xout + xo[s] : c.h_out(unit_of[j]);
+        const uint8_t *d_at = s >= 0 ? c.d + xout + xo[s] : c.d_out(unit_of[j]);
+        if (res[k] > 0 && hipMemcpyAsync(at[k], d_at, (size_t)res[k], hipMemcpyDeviceToHost, ks) != hipSuccess) {
+            (void)hipStreamSynchronize(ks);
+            return JFS_ERR_HIP;
+        }
+    }
+    if (hipStreamSynchronize(ks) != hipSuccess) return JFS_ERR_HIP;
+    for (int k = 0; k < ns; k++) {
+        const int i = ss[k].idx;
+        const int32_t raw = c.host<int32_t>(L.srcn)[k];
+        // a table: its content size where every selected frame decoded and verified (none selected: 0)
+        if (P.tab[i].valid && raw >= 0) src_n[i] = (int64_t)P.tab[i].total;
+        else src_n[i] = raw == -4 ? JFS_ERR_CHECKSUM : chain_src_result(c, k);
+    }
+    jobs.clear();
+    for (int k = 0; k < no; k++) {
+        const int j = oo[k].idx, s = sp_of[j];
+        if (res[k] > 0) jobs.push_back({out[j].dst, at[k], res[k]});
+        out_n[j] = res[k];
+        if (crc) crc[j] = res[k] < 0 ? 0u : s >= 0 ? c.host<uint32_t>(L.xres + r_crc)[s] : c.host<uint32_t>(L.ocrc)[unit_of[j]];
+    }
+    par_copy(jobs);
+    g_splice_counts[0].fetch_add(P.outs, std::memory_order_relaxed);
+    g_splice_counts[1].fetch_add(P.passed, std::memory_order_relaxed);
+    g_splice_counts[2].fetch_add(P.fresh, std::memory_order_relaxed);
+    g_splice_counts[3].fetch_add(P.passed_bytes, std::memory_order_relaxed);
     return JFS_OK;
 }
 
@@ -2392,7 +2563,7 @@ struct SplitScratch {
     int64_t cap = 0;
     hipEvent_t ev_done = nullptr;
 };
-SplitScratch g_split[64], g_eseg_scr[64], g_fast_scr[64], g_read_scr[64];
+SplitScratch g_split[64], g_eseg_scr[64], g_fast_scr[64], g_read_scr[64], g_splice_scr[64];
 
 // One LZ4 small-batch launch (nblk > 0) on the caller's stream with `need`
 // bytes of the current device's scratch in `tab`: launch(scratch, cap, stream)
@@ -2885,6 +3056,49 @@ int jfs_set_read_seek_mode_ext(int mode) {
     return read_seek().exchange(mode);
 }
 
+int jfs_compact_splice_mode(void) { return compact_splice().load(std::memory_order_relaxed); }
+
+int jfs_set_compact_splice_mode(int mode) {
+    if (mode != JFS_COMPACT_SPLICE_OFF && mode != JFS_COMPACT_SPLICE_ON) return -1;
+    return compact_splice().exchange(mode);
+}
+
+int jfs_compact_splice_counts(uint64_t out[4], int reset) {
+    if (!out) return -1;
+    for (int k = 0; k < 4; k++)
+        out[k] = reset ? g_splice_counts[k].exchange(0) : g_splice_counts[k].load(std::memory_order_relaxed);
+    return 0;
+}
+
+int64_t jfs_zstd_splice_device(const jfs_splice_out *d_out, int nout, const jfs_splice_frame *d_frames, int nframes,
+                               const int32_t *d_unit_len, const uint64_t *d_unit_hash, int32_t *d_ret, void *stream) {
+    if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
+    if (nout < 0 || nframes < 0 || (nout > 0 && (!d_out || !d_ret)) || (nframes > 0 && !d_frames)) return JFS_ERR_INVALID;
+    if (nout == 0) return JFS_OK;
+    // the frames' places: the current device's shared scratch, ordered across streams by its event
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return JFS_ERR_HIP;
+    SplitScratch &z = g_splice_scr[dev];
+    std::lock_guard<std::mutex> lk(z.mu);
+    if (!z.ev_done && hipEventCreateWithFlags(&z.ev_done, hipEventDisableTiming) != hipSuccess) return JFS_ERR_HIP;
+    const int64_t need = ((int64_t)nframes + 1) * 4;
+    if (need > z.cap) {
+        if (hipEventSynchronize(z.ev_done) != hipSuccess) return JFS_ERR_HIP;  // earlier launches may still use it
+        if (z.p) (void)hipFree(z.p);
+        z.p = nullptr;
+        z.cap = 0;
+        int64_t want = 1ll << 20;
+        while (want < need) want <<= 1;
+        if (hipMalloc((void **)&z.p, (size_t)want) != hipSuccess) return JFS_ERR_NO_MEMORY;
+        z.cap = want;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (hipStreamWaitEvent(st, z.ev_done, 0) != hipSuccess) return JFS_ERR_HIP;
+    if (jfs_launch_zstd_splice(d_out, nout, d_frames, nframes, d_unit_len, d_unit_hash, (uint32_t *)z.p, d_ret, st) != 0)
+        return JFS_ERR_HIP;
+    return hipEventRecord(z.ev_done, st) == hipSuccess ? JFS_OK : JFS_ERR_HIP;
+}
+
 int jfs_get_zstd_split_frames(void) { return zstd_split_frames().load(std::memory_order_relaxed); }
 
 int jfs_set_zstd_split_frames(int max_frames) {
@@ -3171,7 +3385,24 @@ static int64_t compact_call(int algo, int cipher, int nsrc, const jfs_iov *src, 
             if (sealed) own.push_back(j);
         }
     }
+    // JFS_COMPACT_SPLICE: the call takes the spliced path when the rule (splice_plan.h) passes at least one frame
+    jfs_plan::SplicePlan splice;
+    const bool splice_csum = zstd_seek_csum().load(std::memory_order_relaxed) == JFS_ZSTD_SEEK_CSUM_ON;
+    if (!sealed && algo == JFS_ALGO_ZSTD && !oo.empty() && zstd_parse_now() == JFS_ZSTD_PARSE_SEEKABLE &&
+        compact_splice().load(std::memory_order_relaxed) == JFS_COMPACT_SPLICE_ON) {
+        std::vector<uint8_t> use(nout, 0);
+        std::vector<int64_t> len(nsrc), cap(nsrc);
+        for (const ChainOut &o : oo) use[o.idx] = 1;
+        for (int i = 0; i < nsrc; i++) {
+            len[i] = src[i].src_len;
+            cap[i] = src_map[i] >= 0 ? ss[src_map[i]].cap : 0;
+        }
+        splice = jfs_plan::splice_plan([&](int i, int32_t p) { return src[i].src[p]; }, nsrc, len.data(), cap.data(), nout,
+                                       seg_first, seg, total.data(), use.data(), splice_csum);
+    }
     const int64_t rc = chain_dispatch(ds, algo, COMPRESS, ss, oo, src_n, out_n, [&](DevCtx *dev, Lane &ln) {
+        if (splice.outs > 0)
+            return compact_splice_run(dev, ln, src, ss, src_map, nsrc, out, oo, splice, splice_csum, src_n, out_n, crc);
         return compact_run(dev, ln, algo, cipher, src, src_keys, ss, src_map, out, out_p, oo, seg_first, seg, src_n, out_n,
                            crc);
     });

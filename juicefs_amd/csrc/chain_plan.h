@@ -266,7 +266,8 @@ struct ChainFlags {
 // outputs], byte offsets from the slot's base.  ns decoded sources, n staged
 // objects (n - ns of them only for their checksum), no outputs, nseg segments,
 // npiece 32 KiB pieces of the reads that asked for their checksums, nrange
-// ranges of the sparse lists.
+// ranges of the sparse lists, xmeta_bytes / xres_bytes of records and results
+// that only the call itself knows.
 // An area the call does not use has no bytes and sits where the next one
 // starts.  The host writes [0, h2d), which goes to the device in one copy;
 // [results, out) comes back in one copy.  srcn, the source lengths, lies in
@@ -285,6 +286,7 @@ struct ChainLayout {
     int64_t pf;                    // piece prefix of the reads' checksums, no + 1
     int64_t from;                  // seek mode's lower ends, beside want
     int64_t rf, rng;               // sparse mode's lists: their running sums, ns + 1, and the nrange ranges
+    int64_t xmeta;                 // a call's own records (the spliced compaction's), xmeta_bytes of them
     int64_t srcn;                  // source lengths, ns + 1, preset
     // results, which only the device writes:
     int64_t open;        // the opens'
@@ -292,12 +294,13 @@ struct ChainLayout {
     int64_t ocrc;        // output checksums
     int64_t scrc, got;   // stored objects' checksums: raw, checked
     int64_t csum;        // the reads' checksums, 4 bytes per piece
+    int64_t xres;        // a call's own results, xres_bytes of them
     int64_t out;         // the output area
     int64_t h2d, results;
 
     ChainLayout() = default;
     ChainLayout(int64_t tin, int64_t ns, int64_t n, int64_t no, int64_t nseg, const ChainFlags &f,
-                int64_t npiece = 0, int64_t nrange = 0) {
+                int64_t npiece = 0, int64_t nrange = 0, int64_t xmeta_bytes = 0, int64_t xres_bytes = 0) {
         int64_t o = align16(tin);
         auto take = [&o](bool used, int64_t count, int64_t size) {
             const int64_t at = o;
@@ -324,6 +327,7 @@ struct ChainLayout {
         from = take(f.seek, ns, 4);
         rf = take(f.sparse, ns + 1, 4);
         rng = take(f.sparse, nrange, (int64_t)sizeof(jfs_range));
+        xmeta = take(xmeta_bytes > 0, xmeta_bytes, 1);
         results = srcn = take(true, ns + 1, 4);
         h2d = o;
         open = take(f.sealed, ns, 4);
@@ -333,6 +337,7 @@ struct ChainLayout {
         scrc = take(f.src_crc, n, 4);
         got = take(f.src_crc, n, 4);
         csum = take(f.read_csum, npiece, 4);
+        xres = take(xres_bytes > 0, xres_bytes, 1);
         out = o;
     }
 };

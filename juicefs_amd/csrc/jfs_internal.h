@@ -75,6 +75,11 @@ int jfs_launch_zstd_decode_frames(const jfs_seek_frag *d_frags, const int32_t *d
 // touches, through a table of either layout; input i owns d_rng[d_rng_first[i] .. d_rng_first[i + 1])
 int jfs_launch_zstd_decode_ranges(const jfs_dev_block *d_blocks, const int32_t *d_rng_first, const jfs_range *d_rng,
                                   int nblk, int32_t *d_ret, hipStream_t stream);
+// spliced objects (zstd_splice.hip; jfs_zstd_splice_device's contract): the scan (verdicts into d_ret, every
+// frame's place into d_off, nframes words of scratch, and the seek tables) and the copy of the frames
+int jfs_launch_zstd_splice(const jfs_splice_out *d_out, int nout, const jfs_splice_frame *d_frames, int nframes,
+                           const int32_t *d_unit_len, const uint64_t *d_unit_hash, uint32_t *d_off, int32_t *d_ret,
+                           hipStream_t stream);
 // jfs_zstd_load_range_batch: the bytes src[0, len) of a decoded block go to dst
 // where the fragment decode of that read answered `expect`
 struct jfs_range_pack {

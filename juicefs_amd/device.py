@@ -218,6 +218,35 @@ def zstd_decompress_ranges(desc: torch.Tensor, rng_first: torch.Tensor, rng: tor
                                                       _stream_ptr(stream)), "jfs_zstd_decompress_ranges_device")
 
 
+SPLICE_FRAME_DTYPE = np.dtype([("src", "<u8"), ("c", "<i4"), ("d", "<i4"), ("x", "<u4"), ("unit", "<i4"), ("out", "<i4"),
+                               ("reserved", "<i4")])
+SPLICE_OUT_DTYPE = np.dtype([("dst", "<u8"), ("dst_cap", "<i4"), ("frame_first", "<i4"), ("frame_count", "<i4"),
+                             ("reserved", "<i4")])
+assert SPLICE_FRAME_DTYPE.itemsize == ctypes.sizeof(L.JfsSpliceFrame)
+assert SPLICE_OUT_DTYPE.itemsize == ctypes.sizeof(L.JfsSpliceOut)
+
+
+def zstd_splice(outs: torch.Tensor, frames: torch.Tensor, unit_len: torch.Tensor | None,
+                unit_hash: torch.Tensor | None, ret: torch.Tensor, stream=None):
+    """jfs_zstd_splice_device: every output (a uint8 device tensor of
+    SPLICE_OUT_DTYPE records) is assembled from its frames (SPLICE_FRAME_DTYPE
+    records: PASS frames copied from stored bytes, FRESH ones from their encode
+    unit's buffer with the length the encoder left in unit_len) and gets its
+    seek table -- 12-byte entries with the low words of unit_hash (an int64
+    tensor of XXH64 values) for the FRESH frames, 8-byte entries when unit_hash
+    is None.  ret[j] = the object's size, 0 when it exceeds dst_cap, or a failed
+    unit's verdict.  Asynchronous."""
+    no = outs.numel() // SPLICE_OUT_DTYPE.itemsize
+    nf = frames.numel() // SPLICE_FRAME_DTYPE.itemsize
+    assert ret.dtype == torch.int32 and ret.numel() >= no
+    assert unit_len is None or unit_len.dtype == torch.int32
+    assert unit_hash is None or unit_hash.dtype == torch.int64
+    _check(L.load().jfs_zstd_splice_device(outs.data_ptr(), no, frames.data_ptr() if nf else None, nf,
+                                           unit_len.data_ptr() if unit_len is not None else None,
+                                           unit_hash.data_ptr() if unit_hash is not None else None, ret.data_ptr(),
+                                           _stream_ptr(stream)), "jfs_zstd_splice_device")
+
+
 def zstd_sparse_counts(reset: bool = False):
     """(inputs the ranges decode took through a seek table, frames it selected,
     frames whose checksum it compared) on the current device."""
