@@ -747,6 +747,28 @@ int64_t jfs_zstd_splice_device(const jfs_splice_out *d_out, int nout, const jfs_
                                const int32_t *d_unit_len, const uint64_t *d_unit_hash /* NULL for the 8-byte layout */,
                                int32_t *d_ret, void *stream);
 
+/* Seek tables out of device-resident objects, what the sealed
+ * spliced compaction brings to the host of every opened source.  Input i is the
+ * d_len[i] bytes at d_blocks[i].src (dst and dst_cap are ignored); d_len is read
+ * on the device -- in the chain it is the AEAD open's result array, the
+ * plaintext length, or negative when the tag fails.  d_slot_first (device, nblk
+ * + 1 entries, bytes, ascending multiples of 16): input i's slot is d_tables[
+ * d_slot_first[i], d_slot_first[i + 1]).
+ * One wave per input reads the 9-byte footer at the input's end and checks: the
+ * footer magic; the descriptor is 0x00 or 0x80 (E = 8 or 12); 1 <= nf <= 16384; T
+ * = E nf + 17 <= d_len[i]; the skippable magic 0x184D2A5E and the size word E nf +
+ * 9 stand at d_len[i] - T.  Nothing else: what the entries add up to is the
+ * caller's to check on the copied bytes.  If all of it holds and T fits the
+ * slot, the T bytes of the table go to the slot's start and d_table_len[i] = T;
+ * otherwise d_table_len[i] = 0 and no byte of the slot is written -- also for
+ * d_len[i] < 25 (negative included) and a NULL src.
+ * No byte outside src[0, d_len[i]) is read and none outside the slot's first T
+ * bytes is written.  src may have any alignment (an opened payload lies behind
+ * an envelope header of 15 + wrapped_len bytes).  Asynchronous on `stream`. */
+int64_t jfs_zstd_seek_tables_device(const jfs_dev_block *d_blocks, const int32_t *d_len, int nblk,
+                                    const int32_t *d_slot_first /* nblk + 1, bytes, multiples of 16 */,
+                                    uint8_t *d_tables, int32_t *d_table_len, void *stream);
+
 /* Splice switch of jfs_compact_batch.  JFS_COMPACT_SPLICE_OFF (default): nothing
  * changes.  JFS_COMPACT_SPLICE_ON: a call with algo = Zstd, while the Zstd parse
  * mode is JFS_ZSTD_PARSE_SEEKABLE, cuts every output j with total > 131072 into
@@ -781,16 +803,23 @@ int64_t jfs_zstd_splice_device(const jfs_splice_out *d_out, int nout, const jfs_
  *     in the JFS_READ_SEEK_SPARSE reads.  For a source without a table it is
  *     what those reads report, min(size, need).
  *   crc, jfs_stats: as before.
- * jfs_compact_seal_batch (the tables are ciphertext on the host), LZ4, "none"
- * and the read calls do not consult the switch.  The initial value is read once
- * from JFS_COMPACT_SPLICE = "off" | "on" (case-insensitive; anything else, or
- * unset: off).  jfs_set_compact_splice_mode returns the previous value, or -1
- * for an unknown one (which changes nothing); it is atomic and applies to calls
- * that start afterwards. */
+ * JFS_COMPACT_SPLICE_ALL: JFS_COMPACT_SPLICE_ON for jfs_compact_batch, and
+ * jfs_compact_seal_batch splices too (its own comment has that contract; the
+ * tables are ciphertext on the host, so it opens the sources first and pays one
+ * more host wait).  With OFF or ON jfs_compact_seal_batch does not consult the
+ * switch; LZ4, "none" and the read calls never do.  The initial value is read
+ * once from JFS_COMPACT_SPLICE = "off" | "on" | "all" (case-insensitive; anything
+ * else, or unset: off).  jfs_set_compact_splice_mode returns the previous
+ * value, or -1 for an unknown one (which changes nothing) -- ALL among them, as
+ * callers built against two values rely on; jfs_set_compact_splice_mode_ext is
+ * the same call for all three.  Both are atomic and apply to calls that start
+ * afterwards. */
 #define JFS_COMPACT_SPLICE_OFF 0
 #define JFS_COMPACT_SPLICE_ON 1
+#define JFS_COMPACT_SPLICE_ALL 2
 int jfs_compact_splice_mode(void);
 int jfs_set_compact_splice_mode(int mode);
+int jfs_set_compact_splice_mode_ext(int mode);
 /* Diagnostics of the spliced calls since the last reset, process-wide: out[0] =
  * outputs spliced, out[1] = frames passed, out[2] = frames re-encoded inside
  * spliced outputs, out[3] = compressed bytes passed.  0, or -1 (NULL). */
@@ -818,6 +847,34 @@ int jfs_compact_splice_counts(uint64_t out[4], int reset);
  *   than a segment needs; this wins over the block's own error.  Nothing is
  *   written to out[j].dst for a failed block.  crc[j] (crc may be NULL) = the
  *   CRC-32C of the whole envelope, computed on the GPU; 0 for a failed block.
+ * With JFS_COMPACT_SPLICE_ALL, algo = Zstd and the Zstd parse mode
+ * JFS_ZSTD_PARSE_SEEKABLE, a call of which at least one output survives the
+ * host checks splices as jfs_compact_batch does with JFS_COMPACT_SPLICE_ON (the
+ * rule is stated there).  The sources are opened on the device, their seek tables alone
+ * come to the host (jfs_zstd_seek_tables_device), the rule runs on those, and
+ * the call waits once more than with the switch off.  A source's table counts
+ * only if it fits 12 ceil(dst_cap / 131072) + 17 bytes rounded up to 16 -- what
+ * the seekable encoder and this path write for a block of dst_cap bytes; a
+ * longer one is "no table" here, where jfs_compact_batch accepts up to 16,384
+ * frames.  If no piece passes, src_n, out_n, the bytes and crc are the switch
+ * off's exactly.  Otherwise:
+ *   Spliced out[j]: an envelope whose opened payload is byte-identical to what
+ *     jfs_compact_batch writes with JFS_COMPACT_SPLICE_ON and the same Zstd
+ *     switches for the same plan over the sources' plaintext payloads; its
+ *     header is jfs_compress_seal_batch's for out_p[j], and out_n[j] is never
+ *     above jfs_envelope_bound(ZSTD, total, wrapped_len).  Unspliced out[j]:
+ *     byte-identical to the switch off.
+ *   src_n[i], in this order: JFS_ERR_CORRUPT for a header jfs_envelope_parse
+ *     rejects; JFS_ERR_AUTH for a tag that does not verify -- such a source has
+ *     no table, passes no frame, and every output it feeds is JFS_ERR_CORRUPT as
+ *     before; else the spliced jfs_compact_batch's rule: D for a valid table,
+ *     else the mapped decoder result, -4 being JFS_ERR_CHECKSUM.
+ *   Every passing frame comes from a payload whose tag verified, so "a damaged
+ *     passing frame is copied and NOT noticed" shrinks to damage from before the
+ *     source was sealed.
+ *   An output's own errors (JFS_ERR_SHORT_BUFFER below the envelope bound,
+ *     JFS_ERR_INVALID), "a failed source wins", crc and jfs_stats are unchanged;
+ *     jfs_compact_splice_counts counts these calls as the plain ones.
  * A FRESH data key / nonce pair per output is the caller's duty, as on the PUT
  * path (encrypt.go:230-243): sealing two blocks under one key and nonce breaks
  * the AEAD; never reuse a source's.

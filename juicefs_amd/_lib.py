@@ -57,6 +57,7 @@ EXPORTS = [
     "jfs_get_zstd_split_frames", "jfs_set_zstd_split_frames", "jfs_zstd_split_frame_counts",
     "jfs_zstd_decompress_ranges_device", "jfs_zstd_sparse_counts", "jfs_set_read_seek_mode_ext",
     "jfs_zstd_splice_device", "jfs_compact_splice_mode", "jfs_set_compact_splice_mode", "jfs_compact_splice_counts",
+    "jfs_set_compact_splice_mode_ext", "jfs_zstd_seek_tables_device",
 ]
 # the hook include/jfs_gpucodec_lz4_fast_test.h declares (the fast LZ4 encoder's host twin)
 LZ4_FAST_TEST_EXPORTS = ["jfs_test_lz4_fast_host"]
@@ -69,7 +70,7 @@ ZSTD_PARSE_EXACT, ZSTD_PARSE_FAST, ZSTD_PARSE_SEEKABLE = 0, 1, 2
 READ_SEEK_OFF, READ_SEEK_ON, READ_SEEK_SPARSE = 0, 1, 2
 ZSTD_SPLIT_FRAMES_MAX = 16384
 ZSTD_SEEK_CSUM_OFF, ZSTD_SEEK_CSUM_ON = 0, 1
-COMPACT_SPLICE_OFF, COMPACT_SPLICE_ON = 0, 1
+COMPACT_SPLICE_OFF, COMPACT_SPLICE_ON, COMPACT_SPLICE_ALL = 0, 1, 2
 SEEK_PLAN_OK, SEEK_PLAN_MORE, SEEK_PLAN_NONE = 0, 1, 2
 READ_DECODE_FULL, READ_DECODE_PREFIX, READ_DECODE_PREFIX_ALL = 0, 1, 2
 CIPHER_AES256GCM, CIPHER_CHACHA20POLY1305, CIPHER_SM4GCM = 0, 1, 2
@@ -193,6 +194,10 @@ def load() -> ctypes.CDLL:
     lib.jfs_compact_splice_mode.restype = ctypes.c_int
     lib.jfs_set_compact_splice_mode.argtypes = [ctypes.c_int]
     lib.jfs_set_compact_splice_mode.restype = ctypes.c_int
+    lib.jfs_set_compact_splice_mode_ext.argtypes = [ctypes.c_int]
+    lib.jfs_set_compact_splice_mode_ext.restype = ctypes.c_int
+    lib.jfs_zstd_seek_tables_device.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp, vp]
+    lib.jfs_zstd_seek_tables_device.restype = i64
     lib.jfs_compact_splice_counts.argtypes = [vp, ctypes.c_int]
     lib.jfs_compact_splice_counts.restype = ctypes.c_int
     lib.jfs_zstd_sparse_counts.argtypes = [vp, ctypes.c_int]

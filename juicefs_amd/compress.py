@@ -385,14 +385,16 @@ _SEEK_CSUM = {"off": L.ZSTD_SEEK_CSUM_OFF, "on": L.ZSTD_SEEK_CSUM_ON}
 _PLAN_STATUS = {L.SEEK_PLAN_OK: "ok", L.SEEK_PLAN_MORE: "more", L.SEEK_PLAN_NONE: "none"}
 
 
-_COMPACT_SPLICE = {"off": L.COMPACT_SPLICE_OFF, "on": L.COMPACT_SPLICE_ON}
+_COMPACT_SPLICE = {"off": L.COMPACT_SPLICE_OFF, "on": L.COMPACT_SPLICE_ON, "all": L.COMPACT_SPLICE_ALL}
 
 
 def compact_splice_mode() -> str:
     """The splice switch of the Zstd compaction call (jfs_compact_splice_mode):
     "off", or "on" -- while the Zstd parse mode is "seekable", a 128 KiB piece
     of an output that is exactly one frame of a seekable source is copied as
-    stored bytes, and only the other pieces are decoded and re-encoded."""
+    stored bytes, and only the other pieces are decoded and re-encoded; or
+    "all" -- "on", and the sealed compaction call splices too, from seek tables
+    it lifts out of the sources once they are opened on the device."""
     m = L.load().jfs_compact_splice_mode()
     return next(k for k, v in _COMPACT_SPLICE.items() if v == m)
 
@@ -401,8 +403,8 @@ def set_compact_splice_mode(mode: str) -> str:
     """Set it (process-wide, for calls that start afterwards) and return the
     previous value's name."""
     if mode not in _COMPACT_SPLICE:
-        raise ValueError(f"compact splice mode {mode!r}: expected 'off' or 'on'")
-    prev = L.load().jfs_set_compact_splice_mode(_COMPACT_SPLICE[mode])
+        raise ValueError(f"compact splice mode {mode!r}: expected 'off', 'on' or 'all'")
+    prev = L.load().jfs_set_compact_splice_mode_ext(_COMPACT_SPLICE[mode])
     return next(k for k, v in _COMPACT_SPLICE.items() if v == prev)
 
 

@@ -365,14 +365,14 @@ std::atomic<int> &zstd_seek_csum() {
     }()};
     return m;
 }
-// JFS_COMPACT_SPLICE (include/jfs_gpucodec.h): off (default) | on
+// JFS_COMPACT_SPLICE (include/jfs_gpucodec.h): off (default) | on | all
 std::atomic<int> &compact_splice() {
     static std::atomic<int> m{[] {
         const char *e = getenv("JFS_COMPACT_SPLICE");
         if (!e) return JFS_COMPACT_SPLICE_OFF;
         std::string v(e);
         for (auto &ch : v) ch = (char)tolower((unsigned char)ch);
-        return v == "on" ? JFS_COMPACT_SPLICE_ON : JFS_COMPACT_SPLICE_OFF;
+        return v == "on" ? JFS_COMPACT_SPLICE_ON : v == "all" ? JFS_COMPACT_SPLICE_ALL : JFS_COMPACT_SPLICE_OFF;
     }()};
     return m;
 }
@@ -1912,17 +1912,29 @@ struct Chain {
     ChainLayout L;
     Slot *sl, *s1;
     uint8_t *h, *d;
+    uint8_t *hin, *din;          // the stored bytes: h and d, or where an earlier pass left them opened
+    int32_t *open_h, *open_d;    // the opens' results: L.open's, or that pass's
+    bool opened;                 // the sources were staged and opened by an earlier pass (ChainOpened)
     hipStream_t ks;
 
     template <class T>
     T *host(int64_t o) const { return (T *)(h + o); }
     template <class T>
     T *dev(int64_t o) const { return (T *)(d + o); }
-    uint8_t *d_in(int k) const { return d + off.in[k]; }
+    uint8_t *d_in(int k) const { return din + off.in[k]; }
     uint8_t *d_out(int k) const { return d + L.out + off.out[k]; }
     uint8_t *h_out(int k) const { return h + L.out + off.out[k]; }
     // where output k is gathered: in front of an encoder in the scratch, else in place
     uint8_t *gat(int k) const { return off.gat.empty() ? d_out(k) : sl->sp + off.gat[k]; }
+};
+
+// Sources that a call staged and opened before it could lay itself out (the
+// sealed spliced compaction, whose plan needs their tables): the pinned / HBM
+// pair their payloads lie in, at ChainOffsets::in, and the opens' results.  The
+// layout then has no stored bytes of its own.
+struct ChainOpened {
+    uint8_t *h, *d;
+    int32_t *open_h, *open_d;
 };
 
 // What a call adds to the layout for itself: bytes of records in the H2D part
@@ -1930,6 +1942,7 @@ struct Chain {
 // and of device scratch behind the decoded sources and gathered blocks.
 struct ChainExtra {
     int64_t meta = 0, res = 0, out = 0, scratch = 0;
+    const ChainOpened *opened = nullptr;  // the call's sources, where an earlier pass of it opened them
 };
 
 // Lays the call out and sizes slot 0 for it: JFS_OK or JFS_ERR_NO_MEMORY.
@@ -1947,7 +1960,7 @@ int64_t chain_open(Chain &c, Lane &ln, int algo, int cipher, const std::vector<C
     c.off = jfs_plan::chain_offsets(st, ns, oo, c.codec, encode);
     int64_t nseg = 0;
     for (const ChainOut &o : oo) nseg += seg_first[o.idx + 1] - seg_first[o.idx];
-    c.L = ChainLayout(c.off.tin, ns, c.n, c.no, nseg,
+    c.L = ChainLayout(x.opened ? 0 : c.off.tin, ns, c.n, c.no, nseg,
                       ChainFlags{c.sealed, encode, out_crc, src_crc, prefix, npiece > 0, seek, nrange >= 0}, npiece,
                       std::max<int64_t>(nrange, 0), x.meta, x.res);
     c.sl = &ln.slot[0];
@@ -1957,6 +1970,11 @@ int64_t chain_open(Chain &c, Lane &ln, int algo, int cipher, const std::vector<C
     if (c.codec && !c.sl->ensure_split(std::max<int64_t>(c.off.scratch + x.scratch, 16))) return JFS_ERR_NO_MEMORY;
     c.h = c.sl->h;
     c.d = c.sl->d;
+    c.opened = x.opened != nullptr;
+    c.hin = c.opened ? x.opened->h : c.h;
+    c.din = c.opened ? x.opened->d : c.d;
+    c.open_h = c.opened ? x.opened->open_h : c.host<int32_t>(c.L.open);
+    c.open_d = c.opened ? x.opened->open_d : c.dev<int32_t>(c.L.open);
     return JFS_OK;
 }
 
@@ -1978,10 +1996,10 @@ void chain_stage_sources(const Chain &c, const jfs_iov *src, const uint8_t *cons
     for (int k = 0; k < c.n; k++) {
         const ChainSrc &s = st[k];
         const jfs_iov &v = src[s.idx];
-        if (s.pay > 0) jobs.push_back({c.h + c.off.in[k], v.src + s.off, s.pay});
+        if (s.pay > 0 && !c.opened) jobs.push_back({c.hin + c.off.in[k], v.src + s.off, s.pay});
         if (k >= c.ns) continue;  // staged for its checksum only
         const int64_t plain = c.sealed ? s.pay - 16 : s.pay;  // sealed: pay >= 16, the host answered shorter ones
-        if (c.sealed) {
+        if (c.sealed && !c.opened) {
             uint8_t *d_cell = chain_cell(c, k, src_keys[s.idx], v.src + s.noff);
             // open in place over the staged payload; the codec reads the plaintext
             c.host<jfs_aead_block>(c.L.sad)[k] =
@@ -2030,10 +2048,10 @@ bool chain_lz4_scratch(const Chain &c, const jfs_dev_block *h_enc, bool fast) {
 int chain_decode(const Chain &c, const int32_t *d_want, int64_t max_want, const int32_t *d_from = nullptr,
                  const int32_t *d_rf = nullptr, const jfs_range *d_rng = nullptr) {
     const jfs_dev_block *h_sdesc = c.host<jfs_dev_block>(c.L.sdesc), *d_sdesc = c.dev<jfs_dev_block>(c.L.sdesc);
-    int32_t *d_srcn = c.dev<int32_t>(c.L.srcn), *d_open = c.dev<int32_t>(c.L.open);
+    int32_t *d_srcn = c.dev<int32_t>(c.L.srcn), *d_open = c.open_d;
     const int ns = c.ns;
     int lk = 0;
-    if (c.sealed && ns > 0) lk = jfs_launch_aead(c.cipher, c.dev<jfs_aead_block>(c.L.sad), ns, 1, d_open, nullptr, c.ks);
+    if (c.sealed && !c.opened && ns > 0) lk = jfs_launch_aead(c.cipher, c.dev<jfs_aead_block>(c.L.sad), ns, 1, d_open, nullptr, c.ks);
     if (lk == 0 && c.lz4 && ns > 0) {
         const int64_t r = d_want ? launch_lz4_decode_prefix(*c.s1, h_sdesc, d_sdesc, ns, d_srcn, d_want, max_want, c.ks)
                                  : launch_lz4_decode(*c.s1, h_sdesc, d_sdesc, ns, d_srcn, c.ks);
@@ -2063,7 +2081,7 @@ bool chain_results(const Chain &c, int lk, int64_t end) {
 
 // decoded source k's result: aead.Open first (encrypt.go:283), then the codec
 int64_t chain_src_result(const Chain &c, int k) {
-    if (c.sealed && c.host<int32_t>(c.L.open)[k] < 0) return JFS_ERR_AUTH;
+    if (c.sealed && c.open_h[k] < 0) return JFS_ERR_AUTH;
     const int32_t raw = c.host<int32_t>(c.L.srcn)[k];
     return c.codec ? finish_result(c.algo, DECOMPRESS, raw) : (int64_t)raw;
 }
@@ -2173,24 +2191,114 @@ int64_t compact_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *
 // jfs_compact_splice_counts: outputs spliced, frames passed, frames re-encoded inside them, bytes passed
 std::atomic<uint64_t> g_splice_counts[4];
 
-// Compaction with untouched frames spliced (JFS_COMPACT_SPLICE on; Zstd in the
-// seekable parse mode, no cipher; P, splice_plan.h's answer, splices at least
-// one of oo).  The chain's outputs are P's encode units -- every unspliced
-// output whole, every FRESH piece of a spliced one -- so staging, gather and
-// encode are compact_run's over the derived plan; a spliced output's object is
-// assembled behind them (zstd_splice.hip) in an area of its own behind the
-// units'.  On the lane's stream: one H2D (stored sources, the derived plan, the
-// lists of ranges, the splice records), the ranges decode of what the derived
-// plan still reads, gather, seekable encode of all units (csum: with the 12-byte
-// table for the whole outputs, and XXH64 of the FRESH pieces), the gather's
-// verdicts merged, scan and copy, CRC-32C of the finished objects, results D2H,
-// then exactly the object bytes.  Results as compact_run's; src_n of a source
-// with a valid table is the table's content size (the header has the contract).
-int64_t compact_splice_run(DevCtx *dev, Lane &ln, const jfs_iov *src, const std::vector<ChainSrc> &ss,
-                           const std::vector<int> &src_map, int nsrc, const jfs_iov *out, const std::vector<ChainOut> &oo,
-                           const jfs_plan::SplicePlan &P, bool csum, int64_t *src_n, int64_t *out_n, uint32_t *crc) {
+// The sealed spliced compaction's first pass (JFS_COMPACT_SPLICE all; DESIGN
+// 11e), which brings the host what its plan needs of sources that are
+// ciphertext there.  In slot 1's pinned / HBM pair, which no other chain uses:
+// one H2D (the envelopes' payloads, AEAD descriptors, key cells, the slots),
+// the open of every source in place, the seek tables out of the opened payloads
+// into their slots (zstd_seek_tables.hip), one D2H of the opens' verdicts, the
+// table lengths and the packed tables, and the wait.  The opened payloads stay
+// where they are for the second pass (`at`).
+struct OpenedTables {
+    ChainOpened at;
+    std::vector<int64_t> slot, len;  // per source of the call: its slot's place; its plaintext bytes, or < 0
+    std::vector<int32_t> tlen;       // per source of the call: its table's bytes, 0 without one
+    const uint8_t *tab = nullptr;    // the packed tables
+};
+
+int64_t splice_open_tables(Lane &ln, int cipher, const jfs_iov *src, const uint8_t *const *src_keys,
+                           const std::vector<ChainSrc> &ss, int nsrc, OpenedTables &T) {
+    const int ns = (int)ss.size();
+    const jfs_plan::ChainOffsets off = jfs_plan::chain_offsets(ss, ns, std::vector<ChainOut>(), false, false);
+    std::vector<int32_t> sf(ns + 1, 0);
+    for (int k = 0; k < ns; k++) sf[k + 1] = sf[k] + (int32_t)jfs_plan::splice_slot_bytes(ss[k].cap);
+    const int64_t blk = (int64_t)sizeof(jfs_dev_block), aead = (int64_t)sizeof(jfs_aead_block);
+    // [payloads | descriptors | AEAD descriptors | key cells | slots' places || opens | table lengths | tables]
+    const int64_t a_blk = align16(off.tin), a_sad = a_blk + align16(ns * blk), a_kn = a_sad + align16(ns * aead),
+                  a_sf = a_kn + 64ll * ns, h2d = a_sf + align16((ns + 1) * 4ll), r_tlen = h2d + align16(ns * 4ll),
+                  r_tab = r_tlen + align16(ns * 4ll), end = r_tab + sf[ns];
+    Slot &sl = ln.slot[1];
+    if (!sl.ensure(end)) return JFS_ERR_NO_MEMORY;
+    std::vector<CopyJob> jobs;
+    for (int k = 0; k < ns; k++) {
+        const ChainSrc &s = ss[k];
+        const jfs_iov &v = src[s.idx];
+        jobs.push_back({sl.h + off.in[k], v.src + s.off, s.pay});
+        uint8_t *cell = sl.h + a_kn + 64ll * k, *d_cell = sl.d + a_kn + 64ll * k, *d_pay = sl.d + off.in[k];
+        memcpy(cell, src_keys[s.idx], (size_t)jfs_cipher_key_size(cipher));
+        memcpy(cell + 32, v.src + s.noff, 12);
+        ((jfs_aead_block *)(sl.h + a_sad))[k] = jfs_aead_block{d_pay, d_pay, (int32_t)s.pay, (int32_t)s.pay, d_cell, d_cell + 32};
+        ((jfs_dev_block *)(sl.h + a_blk))[k] = jfs_dev_block{d_pay, nullptr, 0, 0};
+    }
+    par_copy(jobs);
+    memcpy(sl.h + a_sf, sf.data(), (size_t)(ns + 1) * 4);
+    hipStream_t ks = ln.s_k;
+    int32_t *d_open = (int32_t *)(sl.d + h2d);
+    if (hipMemcpyAsync(sl.d, sl.h, (size_t)h2d, hipMemcpyHostToDevice, ks) != hipSuccess) return JFS_ERR_HIP;
+    int lk = jfs_launch_aead(cipher, (const jfs_aead_block *)(sl.d + a_sad), ns, 1, d_open, nullptr, ks);
+    // the open's result is the plaintext length, or negative: a failed open has no table
+    if (lk == 0)
+        lk = jfs_launch_zstd_seek_tables((const jfs_dev_block *)(sl.d + a_blk), d_open, ns, (const int32_t *)(sl.d + a_sf),
+                                         sl.d + r_tab, (int32_t *)(sl.d + r_tlen), ks);
+    if (lk != 0 || hipMemcpyAsync(sl.h + h2d, sl.d + h2d, (size_t)(end - h2d), hipMemcpyDeviceToHost, ks) != hipSuccess ||
+        hipStreamSynchronize(ks) != hipSuccess) {
+        (void)hipStreamSynchronize(ks);
+        return JFS_ERR_HIP;
+    }
+    T.at = ChainOpened{sl.h, sl.d, (int32_t *)(sl.h + h2d), d_open};
+    T.tab = sl.h + r_tab;
+    T.slot.assign(nsrc, 0);
+    T.len.assign(nsrc, -1);  // a source the host answered: no table
+    T.tlen.assign(nsrc, 0);
+    for (int k = 0; k < ns; k++) {
+        T.slot[ss[k].idx] = sf[k];
+        T.len[ss[k].idx] = T.at.open_h[k];
+        T.tlen[ss[k].idx] = T.at.open_h[k] < 0 ? 0 : ((const int32_t *)(sl.h + r_tlen))[k];
+    }
+    return JFS_OK;
+}
+
+// the sealed call's plan, once the tables are on the host
+typedef std::function<jfs_plan::SplicePlan(const jfs_plan::PackedTables &)> SpliceReplan;
+
+// Compaction with untouched frames spliced (Zstd in the seekable parse mode).
+// Without a cipher (JFS_COMPACT_SPLICE on or all): P0, splice_plan.h's answer
+// over the stored objects, splices at least one of oo.  With one (all): the
+// sources are opened first (splice_open_tables), `replan` answers from their
+// packed tables, and every output is sealed at the end; a plan that splices
+// nothing is then the switch off, continued from the opened sources -- every
+// output one whole unit, the sources decoded whole.  own, seg_first, seg: the
+// sealed outputs the host already answered, and the caller's plan (see `lists`).
+// The chain's outputs are the plan's encode units -- every unspliced output
+// whole, every FRESH piece of a spliced one -- so staging, gather and encode are
+// compact_run's over the derived plan; a spliced output's object is assembled
+// behind them (zstd_splice.hip) in an area of its own behind the units'.  On the
+// lane's stream: one H2D (stored sources unless opened, the derived plan, the
+// lists of ranges, the splice and seal records), the ranges decode of what the
+// derived plan still reads, gather, seekable encode of all units (csum: with the
+// 12-byte table for the whole outputs, and XXH64 of the FRESH pieces), the
+// gather's verdicts merged, scan and copy, every output's payload length picked
+// from the units' results or the scan's, the seal in place, CRC-32C of the
+// finished objects, results D2H, then exactly the object bytes.  Results as
+// compact_run's; src_n of a source with a valid table is the table's content
+// size (the header has the contract).
+int64_t compact_splice_run(DevCtx *dev, Lane &ln, int cipher, const jfs_iov *src, const uint8_t *const *src_keys,
+                           const std::vector<ChainSrc> &ss, const std::vector<int> &src_map, int nsrc, const jfs_iov *out,
+                           const jfs_seal_param *out_p, const std::vector<ChainOut> &oo, const jfs_plan::SplicePlan *P0,
+                           const SpliceReplan &replan, const std::vector<int> &own, const int32_t *seg_first,
+                           const jfs_compact_seg *seg, bool csum, int64_t *src_n, int64_t *out_n, uint32_t *crc) {
     const int algo = JFS_ALGO_ZSTD;
+    const bool sealed = cipher >= 0;
     LaneRun scope(dev, ln, algo * 2 + COMPRESS, (uint64_t)(ss.size() + oo.size()));
+    OpenedTables T;
+    jfs_plan::SplicePlan replanned;
+    if (sealed) {
+        const int64_t rc = splice_open_tables(ln, cipher, src, src_keys, ss, nsrc, T);
+        if (rc != JFS_OK) return rc;
+        replanned = replan(jfs_plan::PackedTables{T.tab, T.slot.data(), T.tlen.data(), T.len.data(), nullptr});
+    }
+    const jfs_plan::SplicePlan &P = sealed ? replanned : *P0;
+    const bool whole = P.outs == 0;  // nothing passes: the switch off
     const int ns = (int)ss.size(), no = (int)oo.size(), nu = (int)P.units.size(), nfr = (int)P.frames.size();
     const int nout = (int)P.frame_first.size() - 1;
     // output j: its place in oo; its whole unit, or its place among the spliced ones
@@ -2207,39 +2315,55 @@ int64_t compact_splice_run(DevCtx *dev, Lane &ln, const jfs_iov *src, const std:
     for (int u = 0; u < nu; u++) {
         const jfs_plan::SpliceUnit &q = P.units[u];
         const int64_t cap = q.piece < 0 ? oo[oo_of[q.out]].cap : jfs_compress_bound(JFS_ALGO_ZSTD, q.total);
-        uu[u] = ChainOut{u, q.total, cap, cap, 0};
+        // a whole output is sealed where it is encoded: its area also holds the tag
+        uu[u] = ChainOut{u, q.total, q.piece < 0 ? oo[oo_of[q.out]].area : cap, cap, 0};
         if (q.piece < 0) unit_of[q.out] = u;
     }
     std::vector<int64_t> xo(nsp + 1, 0);  // the spliced objects' places behind the units' area
-    for (int s = 0; s < nsp; s++) xo[s + 1] = xo[s] + align16(oo[sp[s]].cap);
-    const jfs_plan::ChainRanges lists = jfs_plan::splice_ranges(P, nsrc, ss, ns);
-    const int64_t blk = (int64_t)sizeof(jfs_dev_block);
-    // records: splice outputs | frames | XXH64 descriptors of the units (csum) | checksum descriptors (crc)
+    for (int s = 0; s < nsp; s++) xo[s + 1] = xo[s] + align16(oo[sp[s]].area);
+    // What is decoded: what the derived plan reads, and what the sealed outputs with an error of their own (`own`,
+    // which are no units) would have read -- "a failed or short source wins" over that error, so src_n must tell.
+    std::vector<int32_t> rd_first = P.seg_first;
+    std::vector<jfs_compact_seg> rd_seg = P.seg;
+    for (int j : own) {
+        rd_seg.insert(rd_seg.end(), seg + seg_first[j], seg + seg_first[j + 1]);
+        rd_first.push_back((int32_t)rd_seg.size());
+    }
+    const jfs_plan::ChainRanges lists =
+        jfs_plan::chain_ranges(nsrc, (int)rd_first.size() - 1, rd_first.data(), rd_seg.data(), ss, ns);
+    const int64_t blk = (int64_t)sizeof(jfs_dev_block), aead = (int64_t)sizeof(jfs_aead_block);
+    // records: splice outputs | frames | XXH64 descriptors of the units (csum) | where every output's length is picked
+    // from | checksum descriptors (crc) | the seals' descriptors, key cells and checksum seeds (sealed)
     const int64_t m_fr = align16(nsp * (int64_t)sizeof(jfs_splice_out)),
-                  m_xd = m_fr + align16(nfr * (int64_t)sizeof(jfs_splice_frame)), m_cd = m_xd + (csum ? align16(nu * blk) : 0);
-    // results: the spliced outputs' verdicts | their checksums; scratch: frame offsets | unit hashes
-    const int64_t r_crc = align16(nsp * 4ll), s_hash = align16(nfr * 4ll);
+                  m_xd = m_fr + align16(nfr * (int64_t)sizeof(jfs_splice_frame)), m_pk = m_xd + (csum ? align16(nu * blk) : 0),
+                  m_cd = m_pk + align16(no * 4ll), m_ad = m_cd + (crc ? align16(no * blk) : 0),
+                  m_kn = m_ad + (sealed ? align16(no * aead) : 0), m_sd = m_kn + (sealed ? 64ll * no : 0);
+    // results: the spliced outputs' verdicts | every output's payload length | the seals' results | the checksums;
+    // scratch: frame offsets | unit hashes
+    const int64_t r_len = align16(nsp * 4ll), r_r2 = r_len + align16(no * 4ll), r_crc = r_r2 + (sealed ? align16(no * 4ll) : 0),
+                  s_hash = align16(nfr * 4ll);
     ChainExtra x;
-    x.meta = m_cd + (crc ? align16(nsp * blk) : 0);
-    x.res = r_crc + (crc ? align16(nsp * 4ll) : 0);
+    x.meta = m_sd + (sealed && crc ? align16(no * 4ll) : 0);
+    x.res = r_crc + (crc ? align16(no * 4ll) : 0);
     x.out = xo[nsp];
     x.scratch = s_hash + align16(nu * 8ll);
+    x.opened = sealed ? &T.at : nullptr;
     Chain c;
-    const int64_t rc = chain_open(c, ln, algo, -1, ss, ns, uu, P.seg_first.data(), true, crc != nullptr, false, false, 0,
-                                  false, (int64_t)lists.rng.size(), x);
+    // (the chain's own seal and checksum areas stay unused: the outputs are not its units)
+    const int64_t rc = chain_open(c, ln, algo, cipher, ss, ns, uu, P.seg_first.data(), true, false, false, false, 0, false,
+                                  whole ? -1 : (int64_t)lists.rng.size(), x);
     if (rc != JFS_OK) return rc;
     const ChainLayout &L = c.L;
     const int64_t xout = L.out + c.off.tout;  // the spliced objects' area, mirrored like the outputs'
     std::vector<CopyJob> jobs;
-    chain_stage_sources(c, src, nullptr, ss, jobs);
+    chain_stage_sources(c, src, src_keys, ss, jobs);
     par_copy(jobs);
     chain_stage_plan(c, uu, src_map, P.seg_first.data(), P.seg.data());
-    memcpy(c.h + L.rf, lists.first.data(), (size_t)(ns + 1) * 4);
-    if (!lists.rng.empty()) memcpy(c.h + L.rng, lists.rng.data(), lists.rng.size() * sizeof(jfs_range));
+    if (!whole) memcpy(c.h + L.rf, lists.first.data(), (size_t)(ns + 1) * 4);
+    if (!whole && !lists.rng.empty()) memcpy(c.h + L.rng, lists.rng.data(), lists.rng.size() * sizeof(jfs_range));
     jfs_dev_block *h_enc = c.host<jfs_dev_block>(L.enc), *h_xd = c.host<jfs_dev_block>(L.xmeta + m_xd);
     for (int u = 0; u < nu; u++) {
         h_enc[u] = jfs_dev_block{c.gat(u), c.d_out(u), (int32_t)uu[u].total, (int32_t)uu[u].cap};
-        if (crc) c.host<jfs_dev_block>(L.ocd)[u] = jfs_dev_block{c.d_out(u), nullptr, 0, 0};
         // only a FRESH piece is hashed here: a whole output's table is the checksummed encoder's
         if (csum) h_xd[u] = P.units[u].piece < 0 ? jfs_dev_block{nullptr, nullptr, 0, 0}
                                                  : jfs_dev_block{c.gat(u), nullptr, (int32_t)uu[u].total, 0};
@@ -2250,18 +2374,34 @@ int64_t compact_splice_run(DevCtx *dev, Lane &ln, const jfs_iov *src, const std:
         const int j = oo[sp[s]].idx;
         const int32_t f0 = P.frame_first[j], f1 = P.frame_first[j + 1];
         h_so[s] = jfs_splice_out{c.d + xout + xo[s], (int32_t)oo[sp[s]].cap, f0, f1 - f0, 0};
-        if (crc) c.host<jfs_dev_block>(L.xmeta + m_cd)[s] = jfs_dev_block{c.d + xout + xo[s], nullptr, 0, 0};
         for (int32_t f = f0; f < f1; f++) {
             const jfs_plan::SpliceFrame &q = P.frames[f];
-            // a PASS frame lies in its staged source (a source with a table is never answered on the host)
+            // a PASS frame lies in its staged (opened) source (a source with a table is never answered on the host)
             const uint8_t *from = q.src >= 0 ? c.d_in(src_map[q.src]) + q.coff : c.d_out(q.unit);
             h_fr[f] = jfs_splice_frame{from, (int32_t)q.c, (int32_t)q.d, q.x, q.unit, s, 0};
         }
+    }
+    // every output's finished object: its whole unit's payload area, or its spliced area
+    auto d_obj = [&](int k) { return sp_of[oo[k].idx] >= 0 ? c.d + xout + xo[sp_of[oo[k].idx]] : c.d_out(unit_of[oo[k].idx]); };
+    for (int k = 0; k < no; k++) {
+        const int j = oo[k].idx, s = sp_of[j];
+        c.host<int32_t>(L.xmeta + m_pk)[k] = s >= 0 ? ~s : unit_of[j];
+        if (crc) c.host<jfs_dev_block>(L.xmeta + m_cd)[k] = jfs_dev_block{d_obj(k), nullptr, 0, 0};
+        if (!sealed) continue;
+        const jfs_seal_param &p = out_p[j];
+        uint8_t *cell = c.h + L.xmeta + m_kn + 64ll * k, *d_cell = c.d + L.xmeta + m_kn + 64ll * k;
+        memcpy(cell, p.key, (size_t)jfs_cipher_key_size(cipher));
+        memcpy(cell + 32, p.nonce, 12);
+        // seal in place; the length comes from the pick on the device
+        c.host<jfs_aead_block>(L.xmeta + m_ad)[k] =
+            jfs_aead_block{d_obj(k), d_obj(k), (int32_t)oo[k].total, (int32_t)(oo[k].cap + 16), d_cell, d_cell + 32};
+        if (crc) c.host<uint32_t>(L.xmeta + m_sd)[k] = seal_header_crc(p);
     }
     hipStream_t ks = c.ks;
     if (hipMemcpyAsync(c.d, c.h, (size_t)L.h2d, hipMemcpyHostToDevice, ks) != hipSuccess) return JFS_ERR_HIP;
     const jfs_dev_block *d_sdesc = c.dev<jfs_dev_block>(L.sdesc), *d_enc = c.dev<jfs_dev_block>(L.enc);
     int32_t *d_srcn = c.dev<int32_t>(L.srcn), *d_ret = c.dev<int32_t>(L.ret), *d_sret = c.dev<int32_t>(L.xres);
+    int32_t *d_len = c.dev<int32_t>(L.xres + r_len), *d_r2 = c.dev<int32_t>(L.xres + r_r2);
     uint32_t *d_off = (uint32_t *)(c.sl->sp + c.off.scratch);
     uint64_t *d_hash = (uint64_t *)(c.sl->sp + c.off.scratch + s_hash);
     const int32_t max_total = jfs_plan::chain_max_total(uu);
@@ -2269,7 +2409,8 @@ int64_t compact_splice_run(DevCtx *dev, Lane &ln, const jfs_iov *src, const std:
         return jfs_launch_gather(d_sdesc, d_srcn, ns + 1, c.dev<jfs_compact_out>(L.plan), nu, c.dev<jfs_compact_seg>(L.seg),
                                  max_total, d_ret, pass, ks);
     };
-    int lk = chain_decode(c, nullptr, 0, nullptr, c.dev<int32_t>(L.rf), c.dev<jfs_range>(L.rng));
+    int lk = whole ? chain_decode(c, nullptr, 0)
+                   : chain_decode(c, nullptr, 0, nullptr, c.dev<int32_t>(L.rf), c.dev<jfs_range>(L.rng));
     if (lk == 0) lk = gather(0);
     // a piece of at most 128 KiB comes back as one frame and no table in either layout
     if (lk == 0) lk = launch_kernel(algo, COMPRESS, d_enc, nu, d_ret, ks, csum ? ZSTD_ENCODE_SEEK_CSUM : JFS_ZSTD_PARSE_SEEKABLE);
@@ -2279,22 +2420,26 @@ int64_t compact_splice_run(DevCtx *dev, Lane &ln, const jfs_iov *src, const std:
     if (lk == 0)
         lk = jfs_launch_zstd_splice(c.dev<jfs_splice_out>(L.xmeta), nsp, c.dev<jfs_splice_frame>(L.xmeta + m_fr), nfr, d_ret,
                                     csum ? d_hash : nullptr, d_off, d_sret, ks);
-    if (lk == 0 && crc) lk = jfs_launch_crc32c_lens(c.dev<jfs_dev_block>(L.ocd), nu, d_ret, nullptr, c.dev<uint32_t>(L.ocrc), ks);
+    // a seal also runs over an output whose gather failed (its verdict in d_len decides on the host)
+    if (lk == 0) lk = jfs_launch_chain_pick(c.dev<int32_t>(L.xmeta + m_pk), no, d_ret, d_sret, d_len, ks);
+    if (lk == 0 && sealed) lk = jfs_launch_aead(cipher, c.dev<jfs_aead_block>(L.xmeta + m_ad), no, 0, d_r2, d_len, ks);
     if (lk == 0 && crc)
-        lk = jfs_launch_crc32c_lens(c.dev<jfs_dev_block>(L.xmeta + m_cd), nsp, d_sret, nullptr,
-                                    c.dev<uint32_t>(L.xres + r_crc), ks);
+        lk = jfs_launch_crc32c_lens(c.dev<jfs_dev_block>(L.xmeta + m_cd), no, sealed ? d_r2 : d_len,
+                                    sealed ? c.dev<uint32_t>(L.xmeta + m_sd) : nullptr, c.dev<uint32_t>(L.xres + r_crc), ks);
     if (!chain_results(c, lk, L.out)) return JFS_ERR_HIP;
-    const int32_t *h_ret = c.host<int32_t>(L.ret), *h_sret = c.host<int32_t>(L.xres);
-    std::vector<int64_t> res(no);
-    std::vector<uint8_t *> at(no);  // where output k's object lies in the pinned mirror
+    const int32_t *h_len = c.host<int32_t>(L.xres + r_len), *h_r2 = c.host<int32_t>(L.xres + r_r2);
+    std::vector<int64_t> res(no), back(no);  // per output: its result, its bytes behind the envelope header
+    std::vector<uint8_t *> at(no);           // where output k's object lies in the pinned mirror
     for (int k = 0; k < no; k++) {
         const int j = oo[k].idx, s = sp_of[j];
-        const int32_t raw = s >= 0 ? h_sret[s] : h_ret[unit_of[j]];
         // (an object that outgrows its capacity: the bound keeps it out of reach)
-        res[k] = s >= 0 && raw == 0 ? JFS_ERR_SHORT_BUFFER : chain_out_result(algo, true, raw);
-        at[k] = s >= 0 ? c.h + xout + xo[s] : c.h_out(unit_of[j]);
-        const uint8_t *d_at = s >= 0 ? c.d + xout + xo[s] : c.d_out(unit_of[j]);
-        if (res[k] > 0 && hipMemcpyAsync(at[k], d_at, (size_t)res[k], hipMemcpyDeviceToHost, ks) != hipSuccess) {
+        int64_t r = s >= 0 && h_len[k] == 0 ? JFS_ERR_SHORT_BUFFER : chain_out_result(algo, true, h_len[k]);
+        if (sealed && r >= 0 && h_r2[k] != r + 16) r = JFS_ERR_HIP;
+        else if (sealed && r >= 0 && oo[k].hdr + r + 16 > out[j].dst_cap) r = JFS_ERR_SHORT_BUFFER;
+        res[k] = r;
+        back[k] = r < 0 ? 0 : sealed ? r + 16 : r;
+        at[k] = c.h + (d_obj(k) - c.d);
+        if (back[k] > 0 && hipMemcpyAsync(at[k], d_obj(k), (size_t)back[k], hipMemcpyDeviceToHost, ks) != hipSuccess) {
             (void)hipStreamSynchronize(ks);
             return JFS_ERR_HIP;
         }
@@ -2304,15 +2449,16 @@ int64_t compact_splice_run(DevCtx *dev, Lane &ln, const jfs_iov *src, const std:
         const int i = ss[k].idx;
         const int32_t raw = c.host<int32_t>(L.srcn)[k];
         // a table: its content size where every selected frame decoded and verified (none selected: 0)
-        if (P.tab[i].valid && raw >= 0) src_n[i] = (int64_t)P.tab[i].total;
-        else src_n[i] = raw == -4 ? JFS_ERR_CHECKSUM : chain_src_result(c, k);
+        if (!whole && P.tab[i].valid && raw >= 0) src_n[i] = (int64_t)P.tab[i].total;
+        else src_n[i] = !whole && raw == -4 ? JFS_ERR_CHECKSUM : chain_src_result(c, k);
     }
     jobs.clear();
     for (int k = 0; k < no; k++) {
-        const int j = oo[k].idx, s = sp_of[j];
-        if (res[k] > 0) jobs.push_back({out[j].dst, at[k], res[k]});
-        out_n[j] = res[k];
-        if (crc) crc[j] = res[k] < 0 ? 0u : s >= 0 ? c.host<uint32_t>(L.xres + r_crc)[s] : c.host<uint32_t>(L.ocrc)[unit_of[j]];
+        const int j = oo[k].idx;
+        if (sealed && res[k] >= 0) seal_header_write(out[j].dst, out_p[j]);
+        if (back[k] > 0) jobs.push_back({out[j].dst + oo[k].hdr, at[k], back[k]});
+        out_n[j] = res[k] >= 0 ? oo[k].hdr + back[k] : res[k];
+        if (crc) crc[j] = res[k] < 0 ? 0u : c.host<uint32_t>(L.xres + r_crc)[k];
     }
     par_copy(jobs);
     g_splice_counts[0].fetch_add(P.outs, std::memory_order_relaxed);
@@ -3063,6 +3209,11 @@ int jfs_set_compact_splice_mode(int mode) {
     return compact_splice().exchange(mode);
 }
 
+int jfs_set_compact_splice_mode_ext(int mode) {
+    if (mode != JFS_COMPACT_SPLICE_OFF && mode != JFS_COMPACT_SPLICE_ON && mode != JFS_COMPACT_SPLICE_ALL) return -1;
+    return compact_splice().exchange(mode);
+}
+
 int jfs_compact_splice_counts(uint64_t out[4], int reset) {
     if (!out) return -1;
     for (int k = 0; k < 4; k++)
@@ -3097,6 +3248,15 @@ int64_t jfs_zstd_splice_device(const jfs_splice_out *d_out, int nout, const jfs_
     if (jfs_launch_zstd_splice(d_out, nout, d_frames, nframes, d_unit_len, d_unit_hash, (uint32_t *)z.p, d_ret, st) != 0)
         return JFS_ERR_HIP;
     return hipEventRecord(z.ev_done, st) == hipSuccess ? JFS_OK : JFS_ERR_HIP;
+}
+
+int64_t jfs_zstd_seek_tables_device(const jfs_dev_block *d_blocks, const int32_t *d_len, int nblk,
+                                    const int32_t *d_slot_first, uint8_t *d_tables, int32_t *d_table_len, void *stream) {
+    if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
+    if (nblk < 0 || (nblk > 0 && (!d_blocks || !d_len || !d_slot_first || !d_tables || !d_table_len))) return JFS_ERR_INVALID;
+    return jfs_launch_zstd_seek_tables(d_blocks, d_len, nblk, d_slot_first, d_tables, d_table_len, (hipStream_t)stream) == 0
+               ? JFS_OK
+               : JFS_ERR_HIP;
 }
 
 int jfs_get_zstd_split_frames(void) { return zstd_split_frames().load(std::memory_order_relaxed); }
@@ -3385,24 +3545,33 @@ static int64_t compact_call(int algo, int cipher, int nsrc, const jfs_iov *src, 
             if (sealed) own.push_back(j);
         }
     }
-    // JFS_COMPACT_SPLICE: the call takes the spliced path when the rule (splice_plan.h) passes at least one frame
+    // JFS_COMPACT_SPLICE: the call takes the spliced path when the rule (splice_plan.h) passes at least one frame.
+    // With a cipher (mode all) the rule runs inside the path, once the sources are opened and their tables back.
     jfs_plan::SplicePlan splice;
     const bool splice_csum = zstd_seek_csum().load(std::memory_order_relaxed) == JFS_ZSTD_SEEK_CSUM_ON;
-    if (!sealed && algo == JFS_ALGO_ZSTD && !oo.empty() && zstd_parse_now() == JFS_ZSTD_PARSE_SEEKABLE &&
-        compact_splice().load(std::memory_order_relaxed) == JFS_COMPACT_SPLICE_ON) {
-        std::vector<uint8_t> use(nout, 0);
-        std::vector<int64_t> len(nsrc), cap(nsrc);
-        for (const ChainOut &o : oo) use[o.idx] = 1;
-        for (int i = 0; i < nsrc; i++) {
-            len[i] = src[i].src_len;
-            cap[i] = src_map[i] >= 0 ? ss[src_map[i]].cap : 0;
-        }
-        splice = jfs_plan::splice_plan([&](int i, int32_t p) { return src[i].src[p]; }, nsrc, len.data(), cap.data(), nout,
-                                       seg_first, seg, total.data(), use.data(), splice_csum);
+    const int splice_mode = compact_splice().load(std::memory_order_relaxed);
+    const bool splice_try = algo == JFS_ALGO_ZSTD && !oo.empty() && zstd_parse_now() == JFS_ZSTD_PARSE_SEEKABLE &&
+                            (sealed ? splice_mode == JFS_COMPACT_SPLICE_ALL : splice_mode != JFS_COMPACT_SPLICE_OFF);
+    std::vector<uint8_t> use(nout, 0);
+    std::vector<int64_t> len(nsrc), cap(nsrc);
+    for (const ChainOut &o : oo) use[o.idx] = 1;
+    for (int i = 0; i < nsrc; i++) cap[i] = src_map[i] >= 0 ? ss[src_map[i]].cap : 0;
+    auto plan_from = [&](auto fetch) {
+        return jfs_plan::splice_plan(fetch, nsrc, len.data(), cap.data(), nout, seg_first, seg, total.data(), use.data(),
+                                     splice_csum);
+    };
+    if (splice_try && !sealed) {
+        for (int i = 0; i < nsrc; i++) len[i] = src[i].src_len;
+        splice = plan_from([&](int i, int32_t p) { return src[i].src[p]; });
     }
+    const SpliceReplan replan = [&](const jfs_plan::PackedTables &t) {
+        for (int i = 0; i < nsrc; i++) len[i] = t.src_len(i);
+        return plan_from(t);
+    };
     const int64_t rc = chain_dispatch(ds, algo, COMPRESS, ss, oo, src_n, out_n, [&](DevCtx *dev, Lane &ln) {
-        if (splice.outs > 0)
-            return compact_splice_run(dev, ln, src, ss, src_map, nsrc, out, oo, splice, splice_csum, src_n, out_n, crc);
+        if (sealed ? splice_try : splice.outs > 0)
+            return compact_splice_run(dev, ln, cipher, src, src_keys, ss, src_map, nsrc, out, out_p, oo, &splice, replan,
+                                      own, seg_first, seg, splice_csum, src_n, out_n, crc);
         return compact_run(dev, ln, algo, cipher, src, src_keys, ss, src_map, out, out_p, oo, seg_first, seg, src_n, out_n,
                            crc);
     });

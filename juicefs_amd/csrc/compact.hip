@@ -246,6 +246,20 @@ __global__ __launch_bounds__(LANES) void chain_merge_kernel(const int32_t *__res
     if (r < 0) ((JFS_GLOBAL int32_t *)src_n)[i] = r;
 }
 
+// The spliced compaction (capi.hip, compact_splice_run) finishes every output
+// with one seal and one checksum launch, which read the payload's length on the
+// device: a whole output's is its encode unit's result, a spliced one's the
+// splice scan's verdict.  One lane per output k: idx[k] >= 0 picks a[idx[k]],
+// else b[~idx[k]].
+__global__ __launch_bounds__(LANES) void chain_pick_kernel(const int32_t *__restrict__ idx, int n,
+                                                           const int32_t *__restrict__ a,
+                                                           const int32_t *__restrict__ b, int32_t *__restrict__ out) {
+    const int k = blockIdx.x * LANES + threadIdx.x;
+    if (k >= n) return;
+    const int32_t q = ((gc_i32 *)idx)[k];
+    ((JFS_GLOBAL int32_t *)out)[k] = q >= 0 ? ((gc_i32 *)a)[q] : ((gc_i32 *)b)[~q];
+}
+
 // The read chain (capi.hip, read_run) checks every stored object's CRC-32C
 // before anything else sees a byte of it (pkg/object/checksum.go:55-85).  The
 // decoders still run on a mismatching object; like a failed open, only its
@@ -275,6 +289,15 @@ extern "C" int jfs_launch_chain_merge(const int32_t *d_open_ret, int nsrc, int32
     if (nsrc <= 0) return 0;
     hipLaunchKernelGGL(chain_merge_kernel, dim3((unsigned)((nsrc + LANES - 1) / LANES)), dim3(LANES), 0, stream,
                        d_open_ret, nsrc, d_src_n);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+extern "C" int jfs_launch_chain_pick(const int32_t *d_idx, int n, const int32_t *d_a, const int32_t *d_b, int32_t *d_out,
+                                     hipStream_t stream) {
+    using namespace jfs::compact;
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(chain_pick_kernel, dim3((unsigned)((n + LANES - 1) / LANES)), dim3(LANES), 0, stream, d_idx, n, d_a,
+                       d_b, d_out);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

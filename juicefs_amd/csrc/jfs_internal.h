@@ -80,6 +80,9 @@ int jfs_launch_zstd_decode_ranges(const jfs_dev_block *d_blocks, const int32_t *
 int jfs_launch_zstd_splice(const jfs_splice_out *d_out, int nout, const jfs_splice_frame *d_frames, int nframes,
                            const int32_t *d_unit_len, const uint64_t *d_unit_hash, uint32_t *d_off, int32_t *d_ret,
                            hipStream_t stream);
+// seek tables out of device-resident objects (zstd_seek_tables.hip; jfs_zstd_seek_tables_device's contract)
+int jfs_launch_zstd_seek_tables(const jfs_dev_block *d_blocks, const int32_t *d_len, int nblk, const int32_t *d_slot_first,
+                                uint8_t *d_tables, int32_t *d_table_len, hipStream_t stream);
 // jfs_zstd_load_range_batch: the bytes src[0, len) of a decoded block go to dst
 // where the fragment decode of that read answered `expect`
 struct jfs_range_pack {
@@ -137,6 +140,10 @@ int jfs_launch_gather(const jfs_dev_block *d_src, const int32_t *d_src_n, int ns
 // sealed compaction: d_src_n[i] = d_open_ret[i] where the AEAD open of source i
 // failed (d_open_ret[i] < 0), so the gather counts it as a failed source
 int jfs_launch_chain_merge(const int32_t *d_open_ret, int nsrc, int32_t *d_src_n, hipStream_t stream);
+// spliced compaction: d_out[k] = d_a[d_idx[k]] for d_idx[k] >= 0, else d_b[~d_idx[k]] (the payload length of
+// output k: its whole encode unit's result, or the splice scan's verdict)
+int jfs_launch_chain_pick(const int32_t *d_idx, int n, const int32_t *d_a, const int32_t *d_b, int32_t *d_out,
+                          hipStream_t stream);
 // src_n value of a read source whose CRC-32C did not match (compact.hip, verify_gate_kernel)
 #define JFS_CHECKSUM_FAILED (-2147483647)
 // the read path's gather (compact.hip): verdicts and the copy on a one-dimensional

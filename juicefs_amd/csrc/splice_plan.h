@@ -3,7 +3,8 @@
 // a source's frame, the gather plan of everything else, and what that plan still
 // reads of every source.  Plain C++17 integer code -- no HIP types -- with the
 // byte fetch as a parameter, as in zstd_seek.h, whose table parser it uses for
-// both layouts; tests/splice_plan_main.cc checks it on a CPU under ASan + UBSan.
+// both layouts; tests/splice_plan_main.cc and tests/splice_tables_main.cc check
+// it on a CPU under ASan + UBSan.
 //
 // The rule.  F = FRAME_BYTES.  Output j with total > F is cut into pieces p =
 // [f F, min((f + 1) F, total)).  Piece p is PASS(i, k) iff
@@ -188,6 +189,43 @@ inline SplicePlan splice_plan(F fetch, int nsrc, const int64_t *src_len, const i
     P.frame_first[nout] = (int32_t)P.frames.size();
     return P;
 }
+
+// ---- the tables alone --------------------------------------------
+// On a volume with object encryption the host never sees a source's plaintext:
+// the sealed call opens the sources on the device, zstd_seek_tables.hip packs
+// their tables into slots, and the rule above runs on those.
+
+// Source i's slot: room for the 12-byte table of ceil(cap / F) frames -- what the
+// seekable encoder and the spliced path write for a block of cap bytes -- rounded
+// up to 16.  A table that does not fit is "no table" for the call.
+inline int64_t splice_slot_bytes(int64_t cap) {
+    const int64_t F = jfs::zseek::FRAME_BYTES, nf = cap > 0 ? (cap + F - 1) / F : 0;
+    return align16(jfs::zseek::ENTRY_CSUM * nf + jfs::zseek::TABLE_FIXED);
+}
+
+// splice_plan's fetch over packed tables.  Source i's plaintext has len[i]
+// bytes, of which only the last tlen[i], its table, are here, at tab + at[i];
+// tlen[i] == 0: it has no table (also a failed open, len[i] < 0).  Every other
+// position answers 0 and is counted in *outside (when given): the rule never
+// asks for one -- zstd_seek.h's parser starts at the footer and reads nothing
+// in front of the skippable header it points to.
+struct PackedTables {
+    const uint8_t *tab;
+    const int64_t *at;
+    const int32_t *tlen;
+    const int64_t *len;
+    uint64_t *outside;
+    // what splice_plan is handed as src_len[i]: nothing to parse without a table
+    int64_t src_len(int i) const { return tlen[i] > 0 && len[i] >= tlen[i] ? len[i] : 0; }
+    uint8_t operator()(int i, int32_t p) const {
+        const int64_t n = src_len(i), q = (int64_t)p - (n - tlen[i]);
+        if (n == 0 || q < 0 || q >= tlen[i]) {
+            if (outside) ++*outside;
+            return 0;
+        }
+        return tab[at[i] + q];
+    }
+};
 
 // What the derived plan still reads of every decoded source: chain_ranges' lists
 // over the units.  A source that only PASS pieces reference has an empty list.

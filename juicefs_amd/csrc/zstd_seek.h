@@ -80,6 +80,17 @@ JFS_ZSEEK_HD bool seek_table(F fetch, int64_t end, bool csum, bool alone, int32_
     return true;
 }
 
+// The bytes T of the table at the end of the region [0, len), either layout, by
+// its placement alone -- the footer, and the skippable header where the footer
+// says the table starts; 17 bytes are fetched -- or 0.  What the kernel of
+// zstd_seek_tables.hip checks before it copies a table out; the
+// copy then goes through seek_table and seek_sums_ok like any object.
+template <class F>
+JFS_ZSEEK_HD int32_t table_at_end(F fetch, int64_t len) {
+    int32_t nf = 0, tpos = 0, entry = 0;
+    return seek_table(fetch, len, true, false, &nf, &tpos, &entry) ? (int32_t)len - tpos : 0;
+}
+
 // entry k of the table at tpos whose entries take `entry` bytes: compressed
 // size, decompressed size, checksum (0 without one)
 template <class F>

@@ -247,6 +247,22 @@ def zstd_splice(outs: torch.Tensor, frames: torch.Tensor, unit_len: torch.Tensor
                                            _stream_ptr(stream)), "jfs_zstd_splice_device")
 
 
+def zstd_seek_tables(desc: torch.Tensor, lens: torch.Tensor, slot_first: torch.Tensor, tables: torch.Tensor,
+                     table_len: torch.Tensor, stream=None):
+    """jfs_zstd_seek_tables_device: the seek table at the end of input i -- the
+    lens[i] bytes at descriptor i's src (lens: an int32 device tensor, negative
+    for "no input") -- goes to tables[slot_first[i] : slot_first[i + 1]] (int32
+    device tensor of n + 1 multiples of 16; tables: uint8) and its bytes to
+    table_len[i]; 0, and nothing written, without a table that fits.
+    Asynchronous."""
+    n = desc.numel() // DESC_DTYPE.itemsize
+    assert lens.dtype == torch.int32 and slot_first.dtype == torch.int32 and table_len.dtype == torch.int32
+    assert lens.numel() >= n and slot_first.numel() >= n + 1 and table_len.numel() >= n and tables.dtype == torch.uint8
+    _check(L.load().jfs_zstd_seek_tables_device(desc.data_ptr(), lens.data_ptr(), n, slot_first.data_ptr(),
+                                                tables.data_ptr(), table_len.data_ptr(), _stream_ptr(stream)),
+           "jfs_zstd_seek_tables_device")
+
+
 def zstd_sparse_counts(reset: bool = False):
     """(inputs the ranges decode took through a seek table, frames it selected,
     frames whose checksum it compared) on the current device."""
