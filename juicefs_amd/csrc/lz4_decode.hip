@@ -1227,7 +1227,11 @@ __device__ __forceinline__ void parser_wave(Smem &s, Ctx &c PROF_ARG) {
                     // the span at pip: the walk started ahead of time, or a fresh one
                     if (!(spv && nxt && wk.base == pip)) wk.start(pip);
                     PFIRST(const uint64_t it0 = pr.acc[11] + pr.acc[13]; pfirst = true);
+                    // the copier waits for this walk: at its priority until the
+                    // chain is final
+                    __builtin_amdgcn_s_setprio(1);
                     wk.advance(c, 1 << 20 PROF_PASS);
+                    __builtin_amdgcn_s_setprio(0);
                     PSTAMP(1);
                     PFIRST(const uint64_t its = pr.acc[11] + pr.acc[13] - it0; pr.acc[22] += 1; pr.acc[23] += its;
                            pr.acc[24] += pr.last; pr.acc[25] += its == 0);
@@ -1288,8 +1292,8 @@ template <bool PREFIX>
 __device__ __forceinline__ void copier_wave(Smem &s, Ctx &c, int32_t *retp, int32_t want PROF_ARG) {
     // Since the walk step waits for one load round the parser is the critical
     // wave of the pair; the copier keeps the priority it was
-    // tuned with (2 / 3: no better; the parser raised to it for a span
-    // boundary's blocking advance: DESIGN.md 3i).
+    // tuned with (2 / 3: no better); the parser raises itself to it for a span
+    // boundary's blocking advance.
     __builtin_amdgcn_s_setprio(1);
     Ser st;
     st.ip = 0;
