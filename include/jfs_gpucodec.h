@@ -523,6 +523,57 @@ int64_t jfs_zstd_decompress_ranges_device(const jfs_dev_block *d_blocks, const i
  * synchronous.  0, or -1. */
 int jfs_zstd_sparse_counts(uint64_t out[3], int reset);
 
+/* LZ4 ranges decode by ORIGIN CHASE: block i is decoded for the list of byte
+ * ranges d_rng[d_rng_first[i] .. d_rng_first[i+1]) of its output and nothing
+ * else.  A raw LZ4 block has no seek table and needs none: the token chain is
+ * walked once over the compressed bytes (the small-batch decoder's index: per
+ * 256 compressed bytes, the first token and the output offset there), then
+ * every requested byte is resolved on its own -- its sequence is found through
+ * the index; a literal is copied from src; a match byte steps to the byte it
+ * copies, and so on down to a literal.  Work is (compressed bytes, once) +
+ * (requested bytes x chain depth) instead of (output bytes up to the last one
+ * requested); it works on every LZ4 block already stored.
+ * src_len / dst_cap are HOST copies of the descriptors' sizes, as for the
+ * _small calls (a block whose device descriptor asks for more is handed over,
+ * see below); d_rng_first (nblk + 1 int32) and d_rng are device arrays, as for
+ * jfs_zstd_decompress_ranges_device, and so are the list's rules: lo'_r =
+ * max(lo_r, 0), hi'_r = min(hi_r, dst_cap); a range is live when hi'_r > lo'_r;
+ * H = the largest hi'_r of the live ranges.  Let `size` be what
+ * jfs_lz4_decompress_device returns for the block.  ret[i], in this order:
+ *   NULL src, src_len == 0, dst_cap == 0: the full decoder's answers.
+ *   A bad list (d_rng_first[i] < 0, d_rng_first[i+1] < d_rng_first[i], a range
+ *     with hi < lo, two ranges out of order or overlapping; empty ranges may
+ *     stand anywhere in an ascending list): -1, nothing written.
+ *   No live range: 0, nothing written.
+ *   Well-formed stream (size >= 0): ret = min(size, H), and every byte of every
+ *     live range below size equals the full decode's.  A block the chase
+ *     resolves itself has no byte of dst outside its live ranges written.
+ *   A block the chase does not cover -- a chain deeper than 2,048 steps, a
+ *     visited token at the edge of the acceptance conditions, a token chain
+ *     whose fix-up did not settle, a block over the host's sizes -- is handed,
+ *     on the device, to jfs_lz4_decompress_prefix_device with want = H: ret and
+ *     bytes are that call's, so dst[0, ret) may be written.
+ *   A fault in a sequence no requested byte visits is UNSEEN, as the sparse
+ *     Zstd call leaves unselected frames unseen; a caller that needs the whole
+ *     object validated uses the CRC-32C check or the full decoders.
+ *   Rejected stream (size < 0): ret is that negative value, or min(total, H)
+ *     with the bytes the visited sequences define (total = the output the token
+ *     chain adds up to) -- the latitude the prefix call documents.
+ * Nothing outside dst[0, dst_cap) is ever written.  Asynchronous on `stream`,
+ * no host wait; the per-device scratch (some 44 bytes per 256 compressed
+ * bytes: no origin area, so no limit on the batch) and its lock are shared with
+ * the _small calls.  The requested positions are spread over the GPU one quad
+ * per thread; a thread finds its range by walking its block's list, so lists
+ * of a few ranges per block are what the call is built for. */
+int64_t jfs_lz4_decompress_ranges_device(const jfs_dev_block *d_blocks, const int32_t *src_len, const int32_t *dst_cap,
+                                         const int32_t *d_rng_first, const jfs_range *d_rng, int nblk, int32_t *d_ret,
+                                         void *stream);
+/* Diagnostics of that call and of the reads in JFS_READ_LZ4_CHASE_ON: out[0] =
+ * blocks resolved by the chase, out[1] = bytes requested of them, out[2] =
+ * chain steps taken, out[3] = blocks handed to the prefix path; on the current
+ * device since the last reset; synchronous.  0, or -1. */
+int jfs_lz4_chase_counts(uint64_t out[4], int reset);
+
 /* The same from host buffers: what a loadRange adapter calls after
  * jfs_zstd_seek_plan and the ranged GET.  Read i holds the object's table and
  * the fragment [frag_off, frag_off + frag_len) of the object, and asks for the
@@ -1057,6 +1108,40 @@ int jfs_set_read_seek_mode(int mode);
  * jfs_set_read_seek_mode_ext is the same call for all three. */
 #define JFS_READ_SEEK_SPARSE 2
 int jfs_set_read_seek_mode_ext(int mode);
+
+/* LZ4 chase switch of the same calls (and their _csum forms), beside the decode
+ * mode.  JFS_READ_LZ4_CHASE_OFF (default): nothing changes.
+ * JFS_READ_LZ4_CHASE_ON: in every decode mode, an LZ4 source whose reads ask
+ * for at least one and at most JFS_LZ4_CHASE_MAX bytes in all (the list of
+ * ranges [src_off, src_off + len) of the segments that reference it, clamped
+ * to its capacity, the ones that overlap or touch merged) is decoded by
+ * jfs_lz4_decompress_ranges_device for that list; every other source is decoded
+ * as with the switch off.  src_n[i] of such a source is min(size, need), as in
+ * JFS_READ_DECODE_PREFIX; out_n, the gathered bytes, crc_got, the disk-cache
+ * checksums and the precedence of verdicts are those of the switch being off
+ * for every read whose sources are well-formed (the gather and the checksum
+ * kernels read only bytes inside the reads).  A fault in a sequence no read
+ * visits goes unseen unless the object CRC-32C is checked.  The compaction
+ * calls do not consult the switch.
+ * JFS_LZ4_CHASE_MAX (environment, bytes, read once; default 0) is the largest
+ * request per source that takes the chase.  The default comes from the
+ * measurement in DESIGN 12h: on 4 MiB text blocks the chase was slower than the
+ * prefix decode at every read size measured, so nothing is chased until a
+ * deployment sets a threshold of its own.
+ * The initial value is read once from JFS_READ_LZ4_CHASE = "off" | "on"
+ * (case-insensitive; anything else, or unset: off).
+ * jfs_set_read_lz4_chase_mode returns the previous value, or -1 for an unknown
+ * one (which changes nothing); it is atomic and applies to calls that start
+ * afterwards. */
+#define JFS_READ_LZ4_CHASE_OFF 0
+#define JFS_READ_LZ4_CHASE_ON 1
+int jfs_read_lz4_chase_mode(void);
+int jfs_set_read_lz4_chase_mode(int mode);
+/* The threshold in force, and a new one (0 .. 2^31 - 1 bytes; returns the
+ * previous value, or -1 and no change for anything else).  Atomic; applies to
+ * calls that start afterwards. */
+int64_t jfs_lz4_chase_max(void);
+int64_t jfs_set_lz4_chase_max(int64_t bytes);
 
 /* ---- Runtime / utilities ------------------------------------------------- */
 

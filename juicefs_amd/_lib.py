@@ -58,6 +58,8 @@ EXPORTS = [
     "jfs_zstd_decompress_ranges_device", "jfs_zstd_sparse_counts", "jfs_set_read_seek_mode_ext",
     "jfs_zstd_splice_device", "jfs_compact_splice_mode", "jfs_set_compact_splice_mode", "jfs_compact_splice_counts",
     "jfs_set_compact_splice_mode_ext", "jfs_zstd_seek_tables_device",
+    "jfs_lz4_decompress_ranges_device", "jfs_lz4_chase_counts", "jfs_read_lz4_chase_mode",
+    "jfs_set_read_lz4_chase_mode", "jfs_lz4_chase_max", "jfs_set_lz4_chase_max",
 ]
 # the hook include/jfs_gpucodec_lz4_fast_test.h declares (the fast LZ4 encoder's host twin)
 LZ4_FAST_TEST_EXPORTS = ["jfs_test_lz4_fast_host"]
@@ -68,6 +70,7 @@ MODE_OFF, MODE_AUTO, MODE_FORCE = 0, 1, 2
 LZ4_PARSE_EXACT, LZ4_PARSE_FAST = 0, 1
 ZSTD_PARSE_EXACT, ZSTD_PARSE_FAST, ZSTD_PARSE_SEEKABLE = 0, 1, 2
 READ_SEEK_OFF, READ_SEEK_ON, READ_SEEK_SPARSE = 0, 1, 2
+READ_LZ4_CHASE_OFF, READ_LZ4_CHASE_ON = 0, 1
 ZSTD_SPLIT_FRAMES_MAX = 16384
 ZSTD_SEEK_CSUM_OFF, ZSTD_SEEK_CSUM_ON = 0, 1
 COMPACT_SPLICE_OFF, COMPACT_SPLICE_ON, COMPACT_SPLICE_ALL = 0, 1, 2
@@ -188,6 +191,18 @@ def load() -> ctypes.CDLL:
     lib.jfs_set_read_seek_mode_ext.restype = ctypes.c_int
     lib.jfs_zstd_decompress_ranges_device.argtypes = [vp, vp, vp, ctypes.c_int, vp, vp]
     lib.jfs_zstd_decompress_ranges_device.restype = i64
+    lib.jfs_lz4_decompress_ranges_device.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int, vp, vp]
+    lib.jfs_lz4_decompress_ranges_device.restype = i64
+    lib.jfs_lz4_chase_counts.argtypes = [vp, ctypes.c_int]
+    lib.jfs_lz4_chase_counts.restype = ctypes.c_int
+    lib.jfs_read_lz4_chase_mode.argtypes = []
+    lib.jfs_read_lz4_chase_mode.restype = ctypes.c_int
+    lib.jfs_set_read_lz4_chase_mode.argtypes = [ctypes.c_int]
+    lib.jfs_set_read_lz4_chase_mode.restype = ctypes.c_int
+    lib.jfs_lz4_chase_max.argtypes = []
+    lib.jfs_lz4_chase_max.restype = i64
+    lib.jfs_set_lz4_chase_max.argtypes = [i64]
+    lib.jfs_set_lz4_chase_max.restype = i64
     lib.jfs_zstd_splice_device.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp, vp]
     lib.jfs_zstd_splice_device.restype = i64
     lib.jfs_compact_splice_mode.argtypes = []

@@ -367,6 +367,40 @@ def set_read_seek_mode(mode: str) -> str:
     return next(k for k, v in _READ_SEEK.items() if v == prev)
 
 
+_READ_LZ4_CHASE = {"off": L.READ_LZ4_CHASE_OFF, "on": L.READ_LZ4_CHASE_ON}
+
+
+def read_lz4_chase_mode() -> str:
+    """The LZ4 chase switch of the read calls (jfs_read_lz4_chase_mode): "off",
+    or "on" -- an LZ4 source whose reads ask for at most lz4_chase_max() bytes
+    is decoded for exactly those bytes by the origin chase."""
+    m = L.load().jfs_read_lz4_chase_mode()
+    return next(k for k, v in _READ_LZ4_CHASE.items() if v == m)
+
+
+def set_read_lz4_chase_mode(mode: str) -> str:
+    """Set it (process-wide, for calls that start afterwards) and return the
+    previous value's name."""
+    if mode not in _READ_LZ4_CHASE:
+        raise ValueError(f"read lz4 chase mode {mode!r}: expected 'off' or 'on'")
+    prev = L.load().jfs_set_read_lz4_chase_mode(_READ_LZ4_CHASE[mode])
+    return next(k for k, v in _READ_LZ4_CHASE.items() if v == prev)
+
+
+def lz4_chase_max() -> int:
+    """The most bytes the reads may ask of one LZ4 source for it to take the
+    chase (jfs_lz4_chase_max; JFS_LZ4_CHASE_MAX, default 0)."""
+    return int(L.load().jfs_lz4_chase_max())
+
+
+def set_lz4_chase_max(nbytes: int) -> int:
+    """Set it (jfs_set_lz4_chase_max) and return the previous value."""
+    prev = int(L.load().jfs_set_lz4_chase_max(int(nbytes)))
+    if prev < 0:
+        raise ValueError(f"lz4 chase max {nbytes!r}: expected 0 .. 2^31 - 1")
+    return prev
+
+
 def zstd_split_frames() -> int:
     """The most frames a Zstd input may hold for the small-batch decode path to
     replay it block-parallel (jfs_get_zstd_split_frames; default 16384)."""

@@ -328,6 +328,31 @@ std::atomic<int> &read_seek() {
     return m;
 }
 
+// JFS_READ_LZ4_CHASE (include/jfs_gpucodec.h): off (default) | on
+std::atomic<int> &read_lz4_chase() {
+    static std::atomic<int> m{[] {
+        const char *e = getenv("JFS_READ_LZ4_CHASE");
+        if (!e) return JFS_READ_LZ4_CHASE_OFF;
+        std::string v(e);
+        for (auto &ch : v) ch = (char)tolower((unsigned char)ch);
+        return v == "on" ? JFS_READ_LZ4_CHASE_ON : JFS_READ_LZ4_CHASE_OFF;
+    }()};
+    return m;
+}
+
+// JFS_LZ4_CHASE_MAX (include/jfs_gpucodec.h): bytes per source, default 0 (the measured crossover);
+// anything else in the environment leaves the default
+std::atomic<int64_t> &lz4_chase_max() {
+    static std::atomic<int64_t> m{[] {
+        const char *e = getenv("JFS_LZ4_CHASE_MAX");
+        if (!e) return (int64_t)0;
+        char *end = nullptr;
+        const long long v = strtoll(e, &end, 10);
+        return end != e && *end == 0 && v >= 0 && v <= INT32_MAX ? (int64_t)v : (int64_t)0;
+    }()};
+    return m;
+}
+
 // JFS_ZSTD_SPLIT_FRAMES (include/jfs_gpucodec.h): 1 .. 16384 (default 16384);
 // anything else in the environment leaves the default
 std::atomic<int> &zstd_split_frames() {
@@ -2045,16 +2070,26 @@ bool chain_lz4_scratch(const Chain &c, const jfs_dev_block *h_enc, bool fast) {
 // d_want (prefix modes: LZ4, and Zstd in JFS_READ_DECODE_PREFIX_ALL; else null): where each decode stops.
 // d_from (Zstd with JFS_READ_SEEK on; else null): with d_want the range each source is decoded for.
 // d_rf, d_rng (Zstd with JFS_READ_SEEK sparse; else null): the list of ranges each source is decoded for.
+// nchase (LZ4 with JFS_READ_LZ4_CHASE on; else 0): sources [0, nchase) take the origin chase for their lists in
+// d_rf, d_rng, which touch at most max_quads 4-byte groups; the rest are decoded as without the switch.
 int chain_decode(const Chain &c, const int32_t *d_want, int64_t max_want, const int32_t *d_from = nullptr,
-                 const int32_t *d_rf = nullptr, const jfs_range *d_rng = nullptr) {
+                 const int32_t *d_rf = nullptr, const jfs_range *d_rng = nullptr, int nchase = 0, int64_t max_quads = 0) {
     const jfs_dev_block *h_sdesc = c.host<jfs_dev_block>(c.L.sdesc), *d_sdesc = c.dev<jfs_dev_block>(c.L.sdesc);
     int32_t *d_srcn = c.dev<int32_t>(c.L.srcn), *d_open = c.open_d;
     const int ns = c.ns;
     int lk = 0;
     if (c.sealed && !c.opened && ns > 0) lk = jfs_launch_aead(c.cipher, c.dev<jfs_aead_block>(c.L.sad), ns, 1, d_open, nullptr, c.ks);
     if (lk == 0 && c.lz4 && ns > 0) {
-        const int64_t r = d_want ? launch_lz4_decode_prefix(*c.s1, h_sdesc, d_sdesc, ns, d_srcn, d_want, max_want, c.ks)
-                                 : launch_lz4_decode(*c.s1, h_sdesc, d_sdesc, ns, d_srcn, c.ks);
+        int64_t r = JFS_OK;
+        const int rest = ns - nchase;
+        // (the slot's scratch was sized for both launches before anything was queued: read_run)
+        if (nchase > 0)
+            r = launch_rc(jfs_launch_lz4_chase(d_sdesc, desc_lens(h_sdesc, nchase).data(), desc_caps(h_sdesc, nchase).data(),
+                                               d_rf, d_rng, nchase, d_srcn, c.s1->sp, max_quads, c.ks));
+        if (r == JFS_OK && rest > 0)
+            r = d_want ? launch_lz4_decode_prefix(*c.s1, h_sdesc + nchase, d_sdesc + nchase, rest, d_srcn + nchase,
+                                                  d_want + nchase, max_want, c.ks)
+                       : launch_lz4_decode(*c.s1, h_sdesc + nchase, d_sdesc + nchase, rest, d_srcn + nchase, c.ks);
         lk = r == JFS_OK ? 0 : -1;
     } else if (lk == 0 && c.algo == JFS_ALGO_ZSTD && ns > 0) {
         // (with a cipher the frame headers are ciphertext on the host) it plans its own scratch
@@ -2502,7 +2537,7 @@ int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src
                  const std::vector<ChainSrc> &st, int ns, const std::vector<int> &src_map, const jfs_iov *out,
                  const std::vector<ChainOut> &oo, const int32_t *seg_first, const jfs_compact_seg *seg, int64_t *src_n,
                  int64_t *out_n, uint32_t *crc_got, const int64_t *need, const int64_t *from, uint8_t *const *csum,
-                 int nsrc = 0, int nout = 0, bool sparse = false) {
+                 int nsrc = 0, int nout = 0, bool sparse = false, int nchase = 0) {
     LaneRun scope(dev, ln, algo * 2 + DECOMPRESS, (uint64_t)st.size());
     const int n = (int)st.size(), no = (int)oo.size();
     bool any_check = false;
@@ -2520,7 +2555,10 @@ int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src
     const bool prefix = !want.empty();
     sparse = sparse && algo == JFS_ALGO_ZSTD && ns > 0;
     jfs_plan::ChainRanges lists;
-    if (sparse) lists = jfs_plan::chain_ranges(nsrc, nout, seg_first, seg, st, ns);
+    // (LZ4 with JFS_READ_LZ4_CHASE on: read_call moved the nchase sources that take the chase to the front)
+    nchase = algo == JFS_ALGO_LZ4 ? std::min(nchase, ns) : 0;
+    const bool listed = sparse || nchase > 0;
+    if (listed) lists = jfs_plan::chain_ranges(nsrc, nout, seg_first, seg, st, ns);
     std::vector<uint8_t> cs_want(no, 0);
     std::vector<int32_t> piece_first;
     std::vector<int64_t> cs_off;
@@ -2532,14 +2570,14 @@ int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src
     }
     Chain c;
     const int64_t rc = chain_open(c, ln, algo, cipher, st, ns, oo, seg_first, false, false, any_check, prefix, npiece, seek,
-                                  sparse ? (int64_t)lists.rng.size() : -1);
+                                  listed ? (int64_t)lists.rng.size() : -1);
     if (rc != JFS_OK) return rc;
     const ChainLayout &L = c.L;
     memcpy(c.h + L.tf, tile_first.data(), (size_t)(no + 1) * 4);
     if (npiece > 0) memcpy(c.h + L.pf, piece_first.data(), (size_t)(no + 1) * 4);
     if (prefix) memcpy(c.h + L.want, want.data(), (size_t)ns * 4);
     if (seek) memcpy(c.h + L.from, jfs_plan::chain_lo(from, st, ns).data(), (size_t)ns * 4);
-    if (sparse) {
+    if (listed) {
         memcpy(c.h + L.rf, lists.first.data(), (size_t)(ns + 1) * 4);
         if (!lists.rng.empty()) memcpy(c.h + L.rng, lists.rng.data(), lists.rng.size() * sizeof(jfs_range));
     }
@@ -2555,7 +2593,17 @@ int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src
     }
     par_copy(jobs);
     chain_stage_plan(c, oo, src_map, seg_first, seg);
-    if (!chain_lz4_scratch(c, nullptr, false)) return JFS_ERR_NO_MEMORY;
+    if (nchase > 0) {
+        // the chase and the decoders of the rest run one after the other on slot 1's scratch
+        const jfs_dev_block *h_sdesc = c.host<jfs_dev_block>(L.sdesc);
+        int64_t sneed = jfs_lz4_chase_scratch_bytes(nchase, desc_lens(h_sdesc, nchase).data());
+        if (ns > nchase)
+            sneed = std::max(sneed, lz4_decode_scratch(ns - nchase, desc_lens(h_sdesc + nchase, ns - nchase).data(),
+                                                       desc_caps(h_sdesc + nchase, ns - nchase).data()));
+        if (!c.s1->ensure_split(sneed)) return JFS_ERR_NO_MEMORY;
+    } else if (!chain_lz4_scratch(c, nullptr, false)) {
+        return JFS_ERR_NO_MEMORY;
+    }
     hipStream_t ks = c.ks;
     // one H2D: stored bytes, the plan, keys, checksum inputs and the preset source lengths
     if (hipMemcpyAsync(c.d, c.h, (size_t)L.h2d, hipMemcpyHostToDevice, ks) != hipSuccess) return JFS_ERR_HIP;
@@ -2568,7 +2616,8 @@ int64_t read_run(DevCtx *dev, Lane &ln, int algo, int cipher, const jfs_iov *src
                                     c.dev<uint32_t>(L.scrc), ks);
     if (lk == 0)
         lk = chain_decode(c, prefix ? c.dev<int32_t>(L.want) : nullptr, max_want, seek ? c.dev<int32_t>(L.from) : nullptr,
-                          sparse ? c.dev<int32_t>(L.rf) : nullptr, sparse ? c.dev<jfs_range>(L.rng) : nullptr);
+                          listed ? c.dev<int32_t>(L.rf) : nullptr, listed ? c.dev<jfs_range>(L.rng) : nullptr, nchase,
+                          nchase > 0 ? jfs_plan::chain_range_quads(lists, nchase) : 0);
     if (lk == 0 && any_check)
         lk = jfs_launch_verify_gate(c.dev<uint32_t>(L.scrc), d_len, c.dev<uint32_t>(L.exp), n, ns, d_srcn,
                                     c.dev<uint32_t>(L.got), ks);
@@ -3127,6 +3176,35 @@ int64_t jfs_lz4_decompress_prefix_device_small(const jfs_dev_block *d_blocks, co
                               return jfs_launch_lz4_split_prefix(d_blocks, nblk, d_ret, d_want, p, g.nseg, g.max_cap,
                                                                  g.norg, g.max_cap, st);
                           });
+}
+
+int64_t jfs_lz4_decompress_ranges_device(const jfs_dev_block *d_blocks, const int32_t *src_len, const int32_t *dst_cap,
+                                         const int32_t *d_rng_first, const jfs_range *d_rng, int nblk, int32_t *d_ret,
+                                         void *stream) {
+    if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
+    // (d_rng: every list may be empty)
+    if (nblk < 0 || (nblk > 0 && (!d_blocks || !src_len || !dst_cap || !d_rng_first || !d_ret))) return JFS_ERR_INVALID;
+    if (nblk == 0) return JFS_OK;
+    // (the lists live on the device only: the capacities bound the chase's grid)
+    return scratch_launch(g_split, DECOMPRESS, nblk, jfs_lz4_chase_scratch_bytes(nblk, src_len), stream,
+                          [&](uint8_t *p, int64_t, hipStream_t st) {
+                              return jfs_launch_lz4_chase(d_blocks, src_len, dst_cap, d_rng_first, d_rng, nblk, d_ret, p,
+                                                          -1, st);
+                          });
+}
+
+int jfs_read_lz4_chase_mode(void) { return read_lz4_chase().load(std::memory_order_relaxed); }
+
+int jfs_set_read_lz4_chase_mode(int mode) {
+    if (mode != JFS_READ_LZ4_CHASE_OFF && mode != JFS_READ_LZ4_CHASE_ON) return -1;
+    return read_lz4_chase().exchange(mode);
+}
+
+int64_t jfs_lz4_chase_max(void) { return lz4_chase_max().load(std::memory_order_relaxed); }
+
+int64_t jfs_set_lz4_chase_max(int64_t bytes) {
+    if (bytes < 0 || bytes > INT32_MAX) return -1;
+    return lz4_chase_max().exchange(bytes);
 }
 
 int64_t jfs_lz4_compress_device_small(const jfs_dev_block *d_blocks, const int32_t *src_len, int nblk, int32_t *d_ret,
@@ -3691,10 +3769,15 @@ static int64_t read_call(int algo, int cipher, int nsrc, const jfs_iov *src, con
         (algo == JFS_ALGO_ZSTD && dmode == JFS_READ_DECODE_PREFIX_ALL && !sparse) || seek)
         need = jfs_plan::chain_need(nsrc, nout, seg_first, seg);
     if (seek) from = jfs_plan::chain_from(nsrc, nout, seg_first, seg);
+    // JFS_READ_LZ4_CHASE: the LZ4 sources whose reads ask for little enough go first and take the chase
+    int nchase = 0;
+    if (algo == JFS_ALGO_LZ4 && ns > 0 && read_lz4_chase().load(std::memory_order_relaxed) == JFS_READ_LZ4_CHASE_ON)
+        nchase = jfs_plan::chain_chase_front(nsrc, nout, seg_first, seg, st, ns, src_map,
+                                             lz4_chase_max().load(std::memory_order_relaxed));
     chain_dispatch(ds, algo, DECOMPRESS, st, oo, src_n, out_n, [&](DevCtx *dev, Lane &ln) {
         return read_run(dev, ln, algo, cipher, src, src_keys, st, ns, src_map, out, oo, seg_first, seg, src_n, out_n,
                         crc_got, need.empty() ? nullptr : need.data(), from.empty() ? nullptr : from.data(), csum, nsrc, nout,
-                        sparse);
+                        sparse, nchase);
     });
     chain_stat(algo, DECOMPRESS, nsrc, [&](int i) { return src[i].src_len; }, src_n, ns > 0, steady_ns() - t0);
     return JFS_OK;

@@ -188,6 +188,34 @@ inline ChainRanges chain_ranges(int nsrc, int nout, const int32_t *seg_first, co
     return r;
 }
 
+// LZ4 chase (JFS_READ_LZ4_CHASE_ON): the decoded sources whose lists ask for at
+// least one and at most max_bytes bytes are moved, in their order, to the
+// front of st[0, ns) and src_map follows; their count is returned.  The chase
+// then takes st[0, count) and the decoders of the switch being off the rest,
+// each a run of the staged descriptors.
+inline int chain_chase_front(int nsrc, int nout, const int32_t *seg_first, const jfs_compact_seg *seg,
+                             std::vector<ChainSrc> &st, int ns, std::vector<int> &src_map, int64_t max_bytes) {
+    const ChainRanges r = chain_ranges(nsrc, nout, seg_first, seg, st, ns);
+    std::vector<ChainSrc> front, back;
+    for (int k = 0; k < ns; k++) {
+        int64_t bytes = 0;
+        for (int32_t q = r.first[k]; q < r.first[k + 1]; q++) bytes += (int64_t)r.rng[q].hi - r.rng[q].lo;
+        (bytes > 0 && bytes <= max_bytes ? front : back).push_back(st[k]);
+    }
+    const int nf = (int)front.size();
+    std::copy(front.begin(), front.end(), st.begin());
+    std::copy(back.begin(), back.end(), st.begin() + nf);
+    for (int k = 0; k < ns; k++) src_map[st[k].idx] = k;
+    return nf;
+}
+
+// the 4-aligned groups of output positions the lists of sources [0, n) touch (the chase's grid)
+inline int64_t chain_range_quads(const ChainRanges &r, int n) {
+    int64_t quads = 0;
+    for (int32_t q = r.first[0]; q < r.first[n]; q++) quads += ((r.rng[q].hi + 3) >> 2) - (r.rng[q].lo >> 2);
+    return quads;
+}
+
 // ---------------------------------------------------------------------------
 // the reads' disk-cache checksums (disk_cache_file.go checksum()): the
 // big-endian CRC-32C of every 32 KiB piece of a read's gathered bytes

@@ -130,6 +130,14 @@ int jfs_launch_lz4_split(const jfs_dev_block *d_desc, int nb, int32_t *d_ret, vo
 int jfs_launch_lz4_split_prefix(const jfs_dev_block *d_desc, int nb, int32_t *d_ret, const int32_t *d_want,
                                 void *d_scratch, int64_t nseg_all, int64_t max_cap, int64_t norg_all, int64_t max_want,
                                 hipStream_t st);
+// ranges decode by origin chase (lz4_chase.hip): block i is decoded for the ranges d_rng[d_rng_first[i] ..
+// d_rng_first[i + 1]) of its output.  src_len / cap: the host's copies of the descriptors' sizes, which size the
+// scratch (jfs_lz4_chase_scratch_bytes) and the index grids; max_quads: a host-side upper bound of the 4-byte
+// groups the lists touch, or < 0 where the host does not know the lists (it only sizes the grid)
+int64_t jfs_lz4_chase_scratch_bytes(int nb, const int32_t *src_len);
+int jfs_launch_lz4_chase(const jfs_dev_block *d_desc, const int32_t *src_len, const int32_t *cap, const int32_t *d_rf,
+                         const jfs_range *d_rng, int nb, int32_t *d_ret, void *d_scratch, int64_t max_quads,
+                         hipStream_t st);
 // ret value of a fused chain's second step when its first step failed
 #define JFS_CHAIN_FAILED (-2147483647 - 1)
 // compaction gather (compact.hip): verdicts into d_ret and the copy; merge != 0:

@@ -51,15 +51,21 @@
 #include <stdint.h>
 
 #include "jfs_internal.h"
+#include "lz4_chase.h"  // Tok, parse_rd, tok_ok: the token parse and its checks, shared with the host tests
 #include "origin_map.h"
 #include "wave.cuh"
 
 namespace jfs {
 namespace lz4s {
 
+// ---- shared with the ranges decode: lz4_chase.hip includes this file with
+// JFS_LZ4_SPLIT_RECORDS_ONLY defined and takes the records the kernels keep in
+// scratch and the launch of the INDEX steps (plan, spec, fix, count, scan, which
+// walk compressed bytes only), not the kernels.
 constexpr int SEG = JFS_LZ4_SPLIT_SEG;  // compressed bytes per segment (one lane)
 constexpr int FIX_ROUNDS = 6;
 constexpr int T = om::THREADS;  // threads per workgroup
+static_assert(SEG == lz4c::SEG, "lz4_chase.h restates the segment size");
 
 struct SBlock {
     const uint8_t *src;
@@ -86,87 +92,6 @@ struct Scratch {
     int32_t *org;
 };
 
-// one token at x (x < n): next token position, output bytes, and the fields
-// the acceptance conditions need.  A token whose literals reach n is the last.
-// 32-bit positions and lengths (the plan sends blocks with n or cap >= 2^30 to
-// the exact kernel): the wave-per-segment emit parses in scalar registers, and
-// 64-bit fields cost it two scalar ops per add and a VALU round trip per
-// compare.  A length field stops growing at 2^30: such a token ends past n
-// (or its match past cap) either way, so it is rejected as before.
-constexpr int32_t LEN_CAP = 1 << 30;
-struct Tok {
-    uint32_t tok;    // the token byte
-    int32_t lenip;   // input position after the literal-length bytes
-    int32_t ll;      // literal length
-    int32_t lit_end; // lenip + ll
-    int32_t next;    // next token (n for the last token)
-    int32_t mlip;    // input position after the match-length bytes
-    int32_t ml;      // match length (0 for the last token)
-    int32_t off;
-    bool last, cut;  // cut: the stream ends inside the token's header fields
-};
-
-template <class RD>
-__device__ __forceinline__ Tok parse_rd(RD s, int32_t n, int32_t x, bool want_off) {
-    Tok t;
-    t.cut = false;
-    t.off = 0;
-    t.ml = 0;
-    const uint32_t tok = s[x];
-    t.tok = tok;
-    int32_t ip = x + 1;
-    int32_t ll = (int32_t)(tok >> 4);
-    if (ll == 15) {
-        uint32_t b;
-        do {
-            if (ip >= n) {
-                t.cut = true;
-                break;
-            }
-            b = s[ip++];
-            ll += (int32_t)b;
-        } while (b == 255 && ll < LEN_CAP);
-    }
-    t.lenip = ip;
-    t.ll = ll;
-    t.lit_end = ip + ll;
-    t.mlip = ip;
-    if (t.cut || t.lit_end >= n) {
-        t.last = true;
-        t.next = n;
-        return t;
-    }
-    t.last = false;
-    int32_t q = t.lit_end;
-    if (q + 2 > n) {
-        t.cut = true;
-        t.next = n;
-        return t;
-    }
-    if (want_off) t.off = (int32_t)s[q] | ((int32_t)s[q + 1] << 8);
-    q += 2;
-    int32_t ml = (int32_t)(tok & 15);
-    if (ml == 15) {
-        uint32_t b;
-        do {
-            if (q >= n) {
-                t.cut = true;
-                break;
-            }
-            b = s[q++];
-            ml += (int32_t)b;
-        } while (b == 255 && ml < LEN_CAP);
-    }
-    t.mlip = q;
-    t.ml = ml + 4;
-    t.next = q;
-    return t;
-}
-__device__ __forceinline__ Tok parse(const gc_u8 *s, int32_t n, int32_t x, bool want_off) {
-    return parse_rd(s, n, x, want_off);
-}
-
-// block of global segment g (blocks are few: linear search over the seg0's)
 // the block holding segment g: the last b with seg0 <= g (binary search)
 __device__ __forceinline__ int block_of(const SBlock *blk, int nb, int g) {
     int lo = 0, hi = nb - 1;
@@ -176,6 +101,22 @@ __device__ __forceinline__ int block_of(const SBlock *blk, int nb, int g) {
         else hi = mid - 1;
     }
     return lo;
+}
+
+// Carves the index areas (everything but the todo mask and the origin map) for
+// nb blocks of nseg_all segments in all; the caller goes on carving behind them.
+void carve_index(om::Carve &c, int64_t nb, int64_t nseg_all, Scratch &sc);
+
+// Queues plan, spec, the fix rounds, count and scan on st.  d_want (null: the
+// full decode), max_cap, norg_all and max_want as the launchers below take
+// them; a caller without an origin area passes norg_all = INT64_MAX.
+void launch_index(const jfs_dev_block *d_desc, const int32_t *d_want, int nb, const Scratch &sc, int64_t nseg_all,
+                  int64_t max_cap, int64_t norg_all, int64_t max_want, hipStream_t st);
+
+#ifndef JFS_LZ4_SPLIT_RECORDS_ONLY
+
+__device__ __forceinline__ Tok parse(const gc_u8 *s, int32_t n, int32_t x, bool want_off) {
+    return parse_rd(s, n, x, want_off);
 }
 
 // The scratch and the grids were sized on the host from its own (src_len,
@@ -359,29 +300,6 @@ __global__ __launch_bounds__(T) void scan_kernel(Scratch sc) {
     }
 }
 
-// the token checks the exact decoder makes (the emit keeps a token only if
-// it would run it the same way)
-__device__ __forceinline__ bool tok_ok(uint32_t tok, const Tok &t, int32_t n, int32_t op, int32_t cap) {
-    // (op <= cap < 2^30 and every length < 2^30 + 2^8: no sum below overflows;
-    // the last is evaluated only once op + ll <= cap - 12 holds)
-    // literal-length bytes: liblz4 stops reading them (a "loop error" it
-    // ignores) once its input position reaches iend-15 after a 255 byte;
-    // lenip < iend-14 means the terminator was read before that point
-    bool ok = !t.cut && ((tok >> 4) != 15 || t.lenip < n - 14);
-    if (t.last) {
-        ok = ok && t.lit_end == n && op + t.ll <= cap;
-    } else {
-        ok = ok && t.lit_end <= n - 8 && op + t.ll <= cap - 12 && t.off >= 1 && t.off <= op + t.ll &&
-             ((tok & 15) != 15 || t.mlip < n - 4) && op + t.ll + t.ml <= cap - 5;
-    }
-    return ok;
-}
-
-// a rejected token that is a whole sequence, match included, and ends the
-// stream: the block has no final literal run (BStat::bad = 2, the verdict's
-// reason [5]; such a token always fails tok_ok -- its literals end past n - 8)
-__device__ __forceinline__ bool ends_in_match(const Tok &t, int32_t n) { return !t.last && !t.cut && t.next >= n; }
-
 // One WAVE per segment: the segment's true tokens are parsed wave-uniformly
 // and each token's origin run is written by the whole wave (consecutive
 // entries per lane: coalesced stores).  (One thread per segment wrote ~2 KB
@@ -561,25 +479,46 @@ __global__ __launch_bounds__(T) void gather_kernel(Scratch sc) {
     if (!om::gather_quad(org, (const gc_u8 *)B.src, (g_u8 *)B.dst, p, total)) st.unsettled = 1;
 }
 
+#endif  // JFS_LZ4_SPLIT_RECORDS_ONLY
+
 }  // namespace lz4s
 }  // namespace jfs
+
+#ifndef JFS_LZ4_SPLIT_RECORDS_ONLY
 
 using namespace jfs::lz4s;
 namespace om = jfs::om;
 
 // Scratch layout: carves the areas from d_scratch (null: only the size
 // counts) and returns the bytes it takes, for the host's size query and the launcher.
-static int64_t layout(void *d_scratch, int64_t nb, int64_t nseg_all, int64_t norg_all, Scratch &sc, int32_t *&todo) {
-    om::Carve c(d_scratch);
+void jfs::lz4s::carve_index(om::Carve &c, int64_t nb, int64_t nseg_all, Scratch &sc) {
     c.take(sc.blk, nb * (int64_t)sizeof(SBlock));
     c.take(sc.st, nb * (int64_t)sizeof(BStat));
     c.take(sc.spec_exit, nseg_all * 4);
     c.take(sc.entry, nseg_all * 4);
     c.take(sc.cnt, nseg_all * 4);
     c.take(sc.bits, nseg_all * (SEG / 8));
+    sc.org = nullptr;
+}
+
+static int64_t layout(void *d_scratch, int64_t nb, int64_t nseg_all, int64_t norg_all, Scratch &sc, int32_t *&todo) {
+    om::Carve c(d_scratch);
+    carve_index(c, nb, nseg_all, sc);
     c.take(todo, nb * 4);
     c.take(sc.org, norg_all * 4);
     return c.bytes;
+}
+
+void jfs::lz4s::launch_index(const jfs_dev_block *d_desc, const int32_t *d_want, int nb, const Scratch &sc,
+                             int64_t nseg_all, int64_t max_cap, int64_t norg_all, int64_t max_want, hipStream_t st) {
+    const int gs = (int)((nseg_all + T - 1) / T);
+    hipLaunchKernelGGL(plan_kernel, dim3(1), dim3(T), 0, st, d_desc, d_want, nb, sc, nseg_all, max_cap, norg_all, max_want);
+    if (nseg_all > 0) {
+        hipLaunchKernelGGL(spec_kernel, dim3(gs), dim3(T), 0, st, nb, (int)nseg_all, sc);
+        for (int r = 0; r < FIX_ROUNDS; r++) hipLaunchKernelGGL(fix_kernel, dim3(gs), dim3(T), 0, st, nb, (int)nseg_all, sc, r);
+        hipLaunchKernelGGL(count_kernel, dim3(gs), dim3(T), 0, st, nb, (int)nseg_all, sc);
+    }
+    hipLaunchKernelGGL(scan_kernel, dim3(nb), dim3(T), 0, st, sc);
 }
 
 extern "C" int64_t jfs_lz4_split_scratch_bytes(int nb, const int32_t *src_len, const int32_t *cap) {
@@ -608,13 +547,7 @@ static int launch_split(const jfs_dev_block *d_desc, int nb, int32_t *d_ret, con
     int32_t *todo;
     layout(d_scratch, nb, nseg_all, norg_all, sc, todo);
     const int gs = (int)((nseg_all + T - 1) / T);
-    hipLaunchKernelGGL(plan_kernel, dim3(1), dim3(T), 0, st, d_desc, d_want, nb, sc, nseg_all, max_cap, norg_all, max_want);
-    if (nseg_all > 0) {
-        hipLaunchKernelGGL(spec_kernel, dim3(gs), dim3(T), 0, st, nb, (int)nseg_all, sc);
-        for (int r = 0; r < FIX_ROUNDS; r++) hipLaunchKernelGGL(fix_kernel, dim3(gs), dim3(T), 0, st, nb, (int)nseg_all, sc, r);
-        hipLaunchKernelGGL(count_kernel, dim3(gs), dim3(T), 0, st, nb, (int)nseg_all, sc);
-    }
-    hipLaunchKernelGGL(scan_kernel, dim3(nb), dim3(T), 0, st, sc);
+    launch_index(d_desc, d_want, nb, sc, nseg_all, max_cap, norg_all, max_want, st);
     if (nseg_all > 0) {
         // a wave per segment while that leaves the GPU short of waves (a lone
         // block: ~16 k segments), a thread per segment beyond
@@ -666,3 +599,5 @@ extern "C" int jfs_lz4_split_counts(uint64_t *out, int reset) {
     }
     return 0;
 }
+
+#endif  // JFS_LZ4_SPLIT_RECORDS_ONLY

@@ -218,6 +218,31 @@ def zstd_decompress_ranges(desc: torch.Tensor, rng_first: torch.Tensor, rng: tor
                                                       _stream_ptr(stream)), "jfs_zstd_decompress_ranges_device")
 
 
+def lz4_decompress_ranges(desc: torch.Tensor, rng_first: torch.Tensor, rng: torch.Tensor, ret: torch.Tensor, src_lens,
+                          dst_caps, stream=None):
+    """jfs_lz4_decompress_ranges_device: block i is decoded for the output
+    ranges rng[rng_first[i] .. rng_first[i + 1]) only (int32 device tensors, as
+    for zstd_decompress_ranges), every requested byte by the origin chase;
+    src_lens / dst_caps are host copies of the descriptors' sizes.  ret[i] =
+    min(size, largest clamped hi) for a well-formed block."""
+    n = desc.numel() // DESC_DTYPE.itemsize
+    assert rng_first.dtype == torch.int32 and rng.dtype == torch.int32 and rng_first.numel() >= n + 1
+    assert rng.is_contiguous() and rng.numel() % 2 == 0
+    sl = (ctypes.c_int32 * max(n, 1))(*[int(x) for x in src_lens])
+    dc = (ctypes.c_int32 * max(n, 1))(*[int(x) for x in dst_caps])
+    _check(L.load().jfs_lz4_decompress_ranges_device(desc.data_ptr(), sl, dc, rng_first.data_ptr(),
+                                                     rng.data_ptr() if rng.numel() else None, n, ret.data_ptr(),
+                                                     _stream_ptr(stream)), "jfs_lz4_decompress_ranges_device")
+
+
+def lz4_chase_counts(reset: bool = False):
+    """(blocks the origin chase resolved, bytes requested of them, chain steps
+    taken, blocks handed to the prefix path) on the current device."""
+    out = (ctypes.c_uint64 * 4)()
+    _check(L.load().jfs_lz4_chase_counts(out, 1 if reset else 0), "jfs_lz4_chase_counts")
+    return tuple(int(x) for x in out)
+
+
 SPLICE_FRAME_DTYPE = np.dtype([("src", "<u8"), ("c", "<i4"), ("d", "<i4"), ("x", "<u4"), ("unit", "<i4"), ("out", "<i4"),
                                ("reserved", "<i4")])
 SPLICE_OUT_DTYPE = np.dtype([("dst", "<u8"), ("dst_cap", "<i4"), ("frame_first", "<i4"), ("frame_count", "<i4"),
