@@ -1,4 +1,4 @@
-// Host-only planning of the on-device chain calls (capi.hip compact_run and
+// Host-only planning of the on-device chain calls (capi_chain.hip compact_run and
 // read_run): which sources the host answers, where each area of a call's
 // staging lies, and what the plan asks of every source.  Plain C++17 integer
 // code -- no HIP, no environment, no globals -- so that

@@ -1,4 +1,4 @@
-// Host-only planning of the spliced Zstd compaction (capi.hip
+// Host-only planning of the spliced Zstd compaction (capi_chain.hip
 // compact_splice_run): which 128 KiB pieces of an output are the stored bytes of
 // a source's frame, the gather plan of everything else, and what that plan still
 // reads of every source.  Plain C++17 integer code -- no HIP types -- with the

@@ -138,6 +138,36 @@ def test_read_gather_verdicts_per_read(gpu):
     assert np.array_equal(img, want)
 
 
+def test_read_gather_scratch_regrows_behind_a_call_in_flight(gpu):
+    """The tile prefix lives in a per-device scratch block shared by every caller, 1 MiB at first and ordered across
+    calls by an event.  Three calls in a row on one stream, nothing waited for in between: 4 one-byte reads, 300,000
+    (their prefix, (nout + 1) * 4 bytes, no longer fits, so the block is freed and regrown while the first call's event
+    is outstanding), 4 again.  Every byte and every result against numpy."""
+    import torch
+    from juicefs_amd import device as D
+    src = np.frombuffer(gen_block("R", 41, 4096), dtype=np.uint8)
+    sbuf = torch.from_numpy(src.copy()).to(gpu)
+    sdesc = D.make_desc(sbuf, [0], [4096], sbuf, [0], [4096])
+    src_n = torch.tensor([4096], dtype=torch.int32, device=gpu)
+    calls = []
+    for k, n in enumerate((4, 300000, 4)):
+        at = (np.arange(n, dtype=np.int64) * 7 + k) % 4096  # read j is source byte at[j]
+        seg = np.stack([np.zeros(n, np.int64), at, np.zeros(n, np.int64), np.ones(n, np.int64)], axis=1)
+        dbuf = torch.full((n + 64,), CANARY, dtype=torch.uint8, device=gpu)
+        odesc, sdev = D.make_compact_desc(dbuf, np.arange(n) + 32, np.ones(n, np.int32), np.arange(n + 1), seg)
+        ret = torch.full((n,), 12345, dtype=torch.int32, device=gpu)
+        calls.append((n, at, dbuf, odesc, sdev, ret))
+    assert (300000 + 1) * 4 > 1 << 20 >= (4 + 1) * 4
+    for n, _, _, odesc, sdev, ret in calls:
+        D.read_gather(sdesc, src_n, odesc, sdev, np.ones(n, np.int32), ret)
+    torch.cuda.synchronize()
+    for n, at, dbuf, _, _, ret in calls:
+        want = np.full(n + 64, CANARY, dtype=np.uint8)
+        want[32:32 + n] = src[at]
+        assert np.array_equal(ret.cpu().numpy(), np.ones(n, np.int32)), n
+        assert np.array_equal(dbuf.cpu().numpy(), want), n
+
+
 # ---- jfs_read_batch -----------------------------------------------------------
 
 SRC = [("T", 65539), ("T", 40000), ("R", 4097), ("Z", 1)]  # class, decoded length
