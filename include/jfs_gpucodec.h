@@ -574,6 +574,51 @@ int64_t jfs_lz4_decompress_ranges_device(const jfs_dev_block *d_blocks, const in
  * device since the last reset; synchronous.  0, or -1. */
 int jfs_lz4_chase_counts(uint64_t out[4], int reset);
 
+/* LZ4 WINDOW decode: block i is decoded for its output bytes [d_lo[i], d_hi[i])
+ * from the 64 KiB chunk boundary below d_lo[i] instead of from byte 0.  Blocks
+ * written by the fast parse (JFS_LZ4_PARSE_FAST) are cut into independent
+ * 64 KiB chunks: no match reaches before its chunk's first byte.  Nothing in
+ * the stored bytes says which encoder wrote them, so the call checks the
+ * property on the device, for the sequences the window visits, and a block
+ * that lacks it is decoded from byte 0 as by the prefix call -- it works on
+ * every LZ4 block already stored.  The token chain is walked once over the
+ * compressed bytes (the small-batch decoder's index), as for the prefix call;
+ * what the window saves is the replay of the output in front of it.
+ * src_len / dst_cap are HOST copies of the descriptors' sizes, as for the other
+ * _small calls; d_lo and d_hi are device arrays of nblk int32.  Let lo' =
+ * max(lo, 0), hi' = min(hi, dst_cap), Fc = lo' rounded down to 64 KiB, `size`
+ * what jfs_lz4_decompress_device returns for the block, and F the block's
+ * FLOOR: Fc where no visited sequence has a match byte at or above Fc that
+ * copies from below Fc, else 0.  ret[i], in this order:
+ *   NULL src, src_len == 0, dst_cap == 0: the full decoder's answers.
+ *   hi' <= lo': 0, nothing written.
+ *   Well-formed stream (size >= 0): ret = min(size, hi'), and dst[F, ret)
+ *     equals the full decode's bytes.  For a block the path decodes itself no
+ *     byte of dst outside [F, ret) is written.
+ *   A fault in a sequence wholly in front of F is UNSEEN, as the sparse Zstd
+ *     call leaves unselected frames unseen and the chase the sequences no
+ *     requested byte visits; a caller that needs the whole object validated
+ *     uses the CRC-32C check or the full decoders.
+ *   A fault in a visited sequence, at or above F, and every block outside the
+ *     small-batch decoder's proven cases (a token at the edge of the acceptance
+ *     conditions, a fix-up or jump that did not settle, a block over the host's
+ *     sizes): the block is handed, on the device, to
+ *     jfs_lz4_decompress_prefix_device with want = hi; ret and bytes are that
+ *     call's, with the latitude it documents, so dst[0, ret) may be written.
+ * Nothing outside dst[0, dst_cap) is ever written.  Asynchronous on `stream`,
+ * no host wait; scratch, its lock and the batch sizes it suits are
+ * jfs_lz4_decompress_device_small's, and jfs_lz4_split_counts counts its
+ * blocks too. */
+int64_t jfs_lz4_decompress_window_device_small(const jfs_dev_block *d_blocks, const int32_t *src_len,
+                                               const int32_t *dst_cap, const int32_t *d_lo, const int32_t *d_hi, int nblk,
+                                               int32_t *d_ret, void *stream);
+/* Diagnostics of that call and of the reads in JFS_READ_LZ4_WINDOW_ON: out[0] =
+ * blocks decoded from a floor above 0, out[1] = blocks whose probe sent them to
+ * floor 0, out[2] = blocks handed to the exact kernel, out[3] = origin entries
+ * written (the bytes of [F, ret) of the blocks the path decoded itself); on the
+ * current device since the last reset; synchronous.  0, or -1. */
+int jfs_lz4_window_counts(uint64_t out[4], int reset);
+
 /* The same from host buffers: what a loadRange adapter calls after
  * jfs_zstd_seek_plan and the ranged GET.  Read i holds the object's table and
  * the fragment [frag_off, frag_off + frag_len) of the object, and asks for the
@@ -1142,6 +1187,32 @@ int jfs_set_read_lz4_chase_mode(int mode);
  * calls that start afterwards. */
 int64_t jfs_lz4_chase_max(void);
 int64_t jfs_set_lz4_chase_max(int64_t bytes);
+
+/* LZ4 window switch of the same calls (and their _csum forms), beside the
+ * decode mode and the chase switch.  JFS_READ_LZ4_WINDOW_OFF (default): nothing
+ * changes.  JFS_READ_LZ4_WINDOW_ON: in every decode mode, the LZ4 sources that
+ * the chase does not take and that would take the small-batch decoder (at most
+ * JFS_LZ4_SPLIT_MAX of them) are decoded by
+ * jfs_lz4_decompress_window_device_small for [from, need): the first and the
+ * last byte a segment asks of the source, clamped to its capacity.  src_n[i]
+ * of such a source is min(size, need), as in JFS_READ_DECODE_PREFIX; out_n, the
+ * gathered bytes, crc_got, the disk-cache checksums and the precedence of
+ * verdicts are those of the switch being off for every read whose sources are
+ * well-formed.  A call in which every such source is read from its first 64 KiB
+ * (from < 65536), and a call with more such sources than the small-batch
+ * decoder takes, is queued exactly as with the switch off.  A fault in a
+ * sequence in front of the chunk a source's reads start in goes unseen unless
+ * the object CRC-32C is checked.  The compaction calls do not consult the
+ * switch.
+ * The initial value is read once from JFS_READ_LZ4_WINDOW = "off" | "on"
+ * (case-insensitive; anything else, or unset: off).
+ * jfs_set_read_lz4_window_mode returns the previous value, or -1 for an unknown
+ * one (which changes nothing); it is atomic and applies to calls that start
+ * afterwards. */
+#define JFS_READ_LZ4_WINDOW_OFF 0
+#define JFS_READ_LZ4_WINDOW_ON 1
+int jfs_read_lz4_window_mode(void);
+int jfs_set_read_lz4_window_mode(int mode);
 
 /* ---- Runtime / utilities ------------------------------------------------- */
 

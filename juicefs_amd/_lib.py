@@ -60,6 +60,8 @@ EXPORTS = [
     "jfs_set_compact_splice_mode_ext", "jfs_zstd_seek_tables_device",
     "jfs_lz4_decompress_ranges_device", "jfs_lz4_chase_counts", "jfs_read_lz4_chase_mode",
     "jfs_set_read_lz4_chase_mode", "jfs_lz4_chase_max", "jfs_set_lz4_chase_max",
+    "jfs_lz4_decompress_window_device_small", "jfs_lz4_window_counts", "jfs_read_lz4_window_mode",
+    "jfs_set_read_lz4_window_mode",
 ]
 # the hook include/jfs_gpucodec_lz4_fast_test.h declares (the fast LZ4 encoder's host twin)
 LZ4_FAST_TEST_EXPORTS = ["jfs_test_lz4_fast_host"]
@@ -71,6 +73,7 @@ LZ4_PARSE_EXACT, LZ4_PARSE_FAST = 0, 1
 ZSTD_PARSE_EXACT, ZSTD_PARSE_FAST, ZSTD_PARSE_SEEKABLE = 0, 1, 2
 READ_SEEK_OFF, READ_SEEK_ON, READ_SEEK_SPARSE = 0, 1, 2
 READ_LZ4_CHASE_OFF, READ_LZ4_CHASE_ON = 0, 1
+READ_LZ4_WINDOW_OFF, READ_LZ4_WINDOW_ON = 0, 1
 ZSTD_SPLIT_FRAMES_MAX = 16384
 ZSTD_SEEK_CSUM_OFF, ZSTD_SEEK_CSUM_ON = 0, 1
 COMPACT_SPLICE_OFF, COMPACT_SPLICE_ON, COMPACT_SPLICE_ALL = 0, 1, 2
@@ -199,6 +202,14 @@ def load() -> ctypes.CDLL:
     lib.jfs_read_lz4_chase_mode.restype = ctypes.c_int
     lib.jfs_set_read_lz4_chase_mode.argtypes = [ctypes.c_int]
     lib.jfs_set_read_lz4_chase_mode.restype = ctypes.c_int
+    lib.jfs_lz4_decompress_window_device_small.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int, vp, vp]
+    lib.jfs_lz4_decompress_window_device_small.restype = i64
+    lib.jfs_lz4_window_counts.argtypes = [vp, ctypes.c_int]
+    lib.jfs_lz4_window_counts.restype = ctypes.c_int
+    lib.jfs_read_lz4_window_mode.argtypes = []
+    lib.jfs_read_lz4_window_mode.restype = ctypes.c_int
+    lib.jfs_set_read_lz4_window_mode.argtypes = [ctypes.c_int]
+    lib.jfs_set_read_lz4_window_mode.restype = ctypes.c_int
     lib.jfs_lz4_chase_max.argtypes = []
     lib.jfs_lz4_chase_max.restype = i64
     lib.jfs_set_lz4_chase_max.argtypes = [i64]

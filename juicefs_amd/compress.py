@@ -387,6 +387,25 @@ def set_read_lz4_chase_mode(mode: str) -> str:
     return next(k for k, v in _READ_LZ4_CHASE.items() if v == prev)
 
 
+_READ_LZ4_WINDOW = {"off": L.READ_LZ4_WINDOW_OFF, "on": L.READ_LZ4_WINDOW_ON}
+
+
+def read_lz4_window_mode() -> str:
+    """The LZ4 window switch of the read calls (jfs_read_lz4_window_mode):
+    "off", or "on" -- an LZ4 source of a small batch is decoded from the 64 KiB
+    chunk its reads start in, where the block's sequences allow it."""
+    m = L.load().jfs_read_lz4_window_mode()
+    return next(k for k, v in _READ_LZ4_WINDOW.items() if v == m)
+
+
+def set_read_lz4_window_mode(mode: str) -> str:
+    """Set it (jfs_set_read_lz4_window_mode) and return the previous value."""
+    if mode not in _READ_LZ4_WINDOW:
+        raise ValueError(f"read lz4 window mode {mode!r}: expected 'off' or 'on'")
+    prev = L.load().jfs_set_read_lz4_window_mode(_READ_LZ4_WINDOW[mode])
+    return next(k for k, v in _READ_LZ4_WINDOW.items() if v == prev)
+
+
 def lz4_chase_max() -> int:
     """The most bytes the reads may ask of one LZ4 source for it to take the
     chase (jfs_lz4_chase_max; JFS_LZ4_CHASE_MAX, default 0)."""

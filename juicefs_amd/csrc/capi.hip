@@ -1503,6 +1503,20 @@ int64_t launch_lz4_decode_prefix(Slot &sl, const jfs_dev_block *h_desc, const jf
         jfs_launch_lz4_split_prefix(d_desc, n, d_ret, d_want, sl.sp, g.nseg, g.max_cap, g.norg, max_want, st));
 }
 
+bool lz4_decode_is_small(int n) { return n <= split_max(); }
+// The window decode of n <= split_max() staged blocks: block k for [d_lo[k], d_hi[k]) (max_want: the largest
+// hi, known on the host).  The scratch is lz4_decode_scratch's.
+int64_t launch_lz4_decode_window(Slot &sl, const jfs_dev_block *h_desc, const jfs_dev_block *d_desc, int n,
+                                 int32_t *d_ret, const int32_t *d_lo, const int32_t *d_hi, int64_t max_want,
+                                 hipStream_t st) {
+    if (n > split_max()) return JFS_ERR_INVALID;
+    const std::vector<int32_t> lens = desc_lens(h_desc, n), caps = desc_caps(h_desc, n);
+    if (!sl.ensure_split(lz4_decode_scratch(n, lens.data(), caps.data()))) return JFS_ERR_NO_MEMORY;
+    const jfs_plan::Lz4SplitGeom g = jfs_plan::lz4_split_geom(n, lens.data(), caps.data());
+    return launch_rc(
+        jfs_launch_lz4_split_window(d_desc, n, d_ret, d_lo, d_hi, sl.sp, g.nseg, g.max_cap, g.norg, max_want, st));
+}
+
 bool lane_healthy(DevCtx *dev, Lane &ln) {
     DevGuard guard;
     (void)hipSetDevice(dev->id);
@@ -1900,6 +1914,8 @@ int jfs_set_read_seek_mode(int mode) { return ReadSeek::set(mode); }
 int jfs_set_read_seek_mode_ext(int mode) { return ReadSeek::set_ext(mode); }
 int jfs_read_lz4_chase_mode(void) { return ReadLz4Chase::get(); }
 int jfs_set_read_lz4_chase_mode(int mode) { return ReadLz4Chase::set(mode); }
+int jfs_read_lz4_window_mode(void) { return ReadLz4Window::get(); }
+int jfs_set_read_lz4_window_mode(int mode) { return ReadLz4Window::set(mode); }
 int64_t jfs_lz4_chase_max(void) { return Lz4ChaseMax::get(); }
 int64_t jfs_set_lz4_chase_max(int64_t bytes) { return Lz4ChaseMax::set(bytes); }
 int jfs_compact_splice_mode(void) { return CompactSplice::get(); }

@@ -21,6 +21,7 @@
 #include "capi_host.h"
 #include "chain_plan.h"
 #include "jfs_internal.h"
+#include "lz4_window.h"
 #include "splice_plan.h"
 #include "zstd_seek.h"
 
@@ -202,6 +203,8 @@ bool chain_lz4_scratch(const Chain &c, const jfs_dev_block *h_enc, bool fast) {
 // d_rf, d_rng (Zstd with JFS_READ_SEEK sparse; else null): the list of ranges each source is decoded for.
 // nchase (LZ4 with JFS_READ_LZ4_CHASE on; else 0): sources [0, nchase) take the origin chase for their lists in
 // d_rf, d_rng, which touch at most max_quads 4-byte groups; the rest are decoded as without the switch.
+// window (LZ4 with JFS_READ_LZ4_WINDOW on, where read_run takes it): the sources the chase leaves are decoded by
+// the window launcher for [d_from, d_want).
 struct ChainDecode {
     const int32_t *d_want = nullptr;
     int64_t max_want = 0;
@@ -209,6 +212,7 @@ struct ChainDecode {
     const jfs_range *d_rng = nullptr;
     int nchase = 0;
     int64_t max_quads = 0;
+    bool window = false;
 };
 
 // Queues open -> decode -> the opens' verdicts merged into the source lengths.
@@ -226,7 +230,9 @@ int chain_decode(const Chain &c, const ChainDecode &q) {
             r = launch_rc(jfs_launch_lz4_chase(d_sdesc, desc_lens(h_sdesc, q.nchase).data(), desc_caps(h_sdesc, q.nchase).data(),
                                                q.d_rf, q.d_rng, q.nchase, d_srcn, c.s1->sp, q.max_quads, c.ks));
         if (r == JFS_OK && rest > 0)
-            r = q.d_want ? launch_lz4_decode_prefix(*c.s1, h_sdesc + q.nchase, d_sdesc + q.nchase, rest, d_srcn + q.nchase,
+            r = q.window ? launch_lz4_decode_window(*c.s1, h_sdesc + q.nchase, d_sdesc + q.nchase, rest, d_srcn + q.nchase,
+                                                    q.d_from + q.nchase, q.d_want + q.nchase, q.max_want, c.ks)
+                : q.d_want ? launch_lz4_decode_prefix(*c.s1, h_sdesc + q.nchase, d_sdesc + q.nchase, rest, d_srcn + q.nchase,
                                                   q.d_want + q.nchase, q.max_want, c.ks)
                        : launch_lz4_decode(*c.s1, h_sdesc + q.nchase, d_sdesc + q.nchase, rest, d_srcn + q.nchase, c.ks);
         lk = r == JFS_OK ? 0 : -1;
@@ -713,12 +719,19 @@ int64_t compact_splice_run(DevCtx *dev, Lane &ln, const ChainCall &cc, const Com
 // gather on the same stream, and the checksum area comes back in front of the
 // reads in the same D2H copy.  A call without such a read is laid out and
 // queued exactly like one without csum.
+// wneed, wfrom (LZ4 with JFS_READ_LZ4_WINDOW on, else null): chain_need and
+// chain_from of the call, whatever the decode mode.  Where the sources the
+// chase leaves fit the small-batch decoder and one of them has a read that starts
+// at or above its first 64 KiB chunk boundary (Fc(from) > 0, lz4_window.h),
+// those sources are decoded by the window launcher for [from, need), staged as
+// the seek mode's; any other call is laid out and queued exactly as without them.
 struct ReadOpts {
     uint32_t *crc_got;
     const int64_t *need, *from;
     uint8_t *const *csum;
     bool sparse;
     int nchase;  // LZ4 with JFS_READ_LZ4_CHASE on: the sources at the front that take the chase
+    const int64_t *wneed = nullptr, *wfrom = nullptr;
 };
 
 int64_t read_run(DevCtx *dev, Lane &ln, const ChainCall &cc, const ReadOpts &opt) {
@@ -746,13 +759,21 @@ int64_t read_run(DevCtx *dev, Lane &ln, const ChainCall &cc, const ReadOpts &opt
         if (ntiles > INT32_MAX) return JFS_ERR_NO_MEMORY;
     }
     tile_first[no] = (int32_t)ntiles;
-    const bool seek = need && from && algo == JFS_ALGO_ZSTD && ns > 0;
+    // (LZ4 with JFS_READ_LZ4_CHASE on: read_call moved the nchase sources that take the chase to the front)
+    nchase = algo == JFS_ALGO_LZ4 ? std::min(nchase, ns) : 0;
+    bool window = false;
+    if (algo == JFS_ALGO_LZ4 && opt.wneed && opt.wfrom && ns > nchase && lz4_decode_is_small(ns - nchase))
+        for (int k = nchase; k < ns && !window; k++)
+            window = jfs::lz4w::floor_of((int32_t)std::min<int64_t>(opt.wfrom[st[k].idx], st[k].cap)) > 0;
+    if (window) {
+        need = opt.wneed;
+        from = opt.wfrom;
+    }
+    const bool seek = need && from && ((algo == JFS_ALGO_ZSTD && ns > 0) || window);
     if (need && (algo == JFS_ALGO_LZ4 || algo == JFS_ALGO_ZSTD)) want = jfs_plan::chain_want(need, st, ns, &max_want, seek);
     const bool prefix = !want.empty();
     sparse = sparse && algo == JFS_ALGO_ZSTD && ns > 0;
     jfs_plan::ChainRanges lists;
-    // (LZ4 with JFS_READ_LZ4_CHASE on: read_call moved the nchase sources that take the chase to the front)
-    nchase = algo == JFS_ALGO_LZ4 ? std::min(nchase, ns) : 0;
     const bool listed = sparse || nchase > 0;
     if (listed) lists = jfs_plan::chain_ranges(nsrc, nout, seg_first, seg, st, ns);
     std::vector<uint8_t> cs_want(no, 0);
@@ -826,6 +847,7 @@ int64_t read_run(DevCtx *dev, Lane &ln, const ChainCall &cc, const ReadOpts &opt
     dec.d_rng = listed ? c.dev<jfs_range>(L.rng) : nullptr;
     dec.nchase = nchase;
     dec.max_quads = nchase > 0 ? jfs_plan::chain_range_quads(lists, nchase) : 0;
+    dec.window = window;
     if (lk == 0) lk = chain_decode(c, dec);
     if (lk == 0 && any_check)
         lk = jfs_launch_verify_gate(c.dev<uint32_t>(L.scrc), d_len, c.dev<uint32_t>(L.exp), n, ns, d_srcn,
@@ -1134,8 +1156,14 @@ static int64_t read_call(int algo, int cipher, int nsrc, const jfs_iov *src, con
     int nchase = 0;
     if (algo == JFS_ALGO_LZ4 && ns > 0 && ReadLz4Chase::get() == JFS_READ_LZ4_CHASE_ON)
         nchase = jfs_plan::chain_chase_front(nsrc, nout, seg_first, seg, st, ns, src_map, Lz4ChaseMax::get());
+    // JFS_READ_LZ4_WINDOW: the range every LZ4 source is asked for, in every decode mode (read_run decides)
+    std::vector<int64_t> wneed, wfrom;
+    if (algo == JFS_ALGO_LZ4 && ns > 0 && ReadLz4Window::get() == JFS_READ_LZ4_WINDOW_ON) {
+        wneed = jfs_plan::chain_need(nsrc, nout, seg_first, seg);
+        wfrom = jfs_plan::chain_from(nsrc, nout, seg_first, seg);
+    }
     const ReadOpts opt{crc_got, need.empty() ? nullptr : need.data(), from.empty() ? nullptr : from.data(), csum, sparse,
-                       nchase};
+                       nchase, wneed.empty() ? nullptr : wneed.data(), wfrom.empty() ? nullptr : wfrom.data()};
     chain_dispatch(ds, algo, DECOMPRESS, st, oo, src_n, out_n,
                    [&](DevCtx *dev, Lane &ln) { return read_run(dev, ln, cc, opt); });
     chain_stat(algo, DECOMPRESS, nsrc, [&](int i) { return src[i].src_len; }, src_n, ns > 0, steady_ns() - t0);

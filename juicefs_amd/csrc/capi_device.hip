@@ -101,6 +101,21 @@ int64_t jfs_lz4_decompress_prefix_device_small(const jfs_dev_block *d_blocks, co
                           });
 }
 
+int64_t jfs_lz4_decompress_window_device_small(const jfs_dev_block *d_blocks, const int32_t *src_len,
+                                               const int32_t *dst_cap, const int32_t *d_lo, const int32_t *d_hi, int nblk,
+                                               int32_t *d_ret, void *stream) {
+    if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
+    if (nblk < 0 || (nblk > 0 && (!d_blocks || !src_len || !dst_cap || !d_lo || !d_hi || !d_ret))) return JFS_ERR_INVALID;
+    if (nblk == 0) return JFS_OK;
+    const jfs_plan::Lz4SplitGeom g = jfs_plan::lz4_split_geom(nblk, src_len, dst_cap);
+    // (the windows live on the device only: the grids stay sized by the largest dst_cap)
+    return scratch_launch(g_split, DECOMPRESS, nblk, jfs_lz4_split_scratch_bytes(nblk, src_len, dst_cap), stream,
+                          [&](uint8_t *p, int64_t, hipStream_t st) {
+                              return jfs_launch_lz4_split_window(d_blocks, nblk, d_ret, d_lo, d_hi, p, g.nseg, g.max_cap,
+                                                                 g.norg, g.max_cap, st);
+                          });
+}
+
 int64_t jfs_lz4_decompress_ranges_device(const jfs_dev_block *d_blocks, const int32_t *src_len, const int32_t *dst_cap,
                                          const int32_t *d_rng_first, const jfs_range *d_rng, int nblk, int32_t *d_ret,
                                          void *stream) {

@@ -355,6 +355,11 @@ int64_t launch_lz4_decode(Slot &sl, const jfs_dev_block *h_desc, const jfs_dev_b
                           hipStream_t st);
 int64_t launch_lz4_decode_prefix(Slot &sl, const jfs_dev_block *h_desc, const jfs_dev_block *d_desc, int n,
                                  int32_t *d_ret, const int32_t *d_want, int64_t max_want, hipStream_t st);
+// the window decode of a batch the small-batch path takes, and whether it takes n blocks (JFS_LZ4_SPLIT_MAX)
+int64_t launch_lz4_decode_window(Slot &sl, const jfs_dev_block *h_desc, const jfs_dev_block *d_desc, int n,
+                                 int32_t *d_ret, const int32_t *d_lo, const int32_t *d_hi, int64_t max_want,
+                                 hipStream_t st);
+bool lz4_decode_is_small(int n);
 
 // Small-batch device launches: per-device scratch shared by every caller,
 // ordered across streams by an event (like the Zstd device decoder's).

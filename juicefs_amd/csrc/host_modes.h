@@ -1,5 +1,5 @@
 // The run-time switches of the C ABI (include/jfs_gpucodec.h), each described
-// once: the seven enumerated ones by environment name, default, accepted
+// once: the eight enumerated ones by environment name, default, accepted
 // spellings and what their setters take; the two integer ones by name, default
 // and closed range.  The initial value is read once from the environment,
 // case-insensitively; an unknown or malformed value gives the default.  A
@@ -86,6 +86,9 @@ inline constexpr ModeDesc MODE_READ_SEEK{"JFS_READ_SEEK", JFS_READ_SEEK_OFF,
 inline constexpr ModeDesc MODE_READ_LZ4_CHASE{"JFS_READ_LZ4_CHASE", JFS_READ_LZ4_CHASE_OFF,
     {{"off", JFS_READ_LZ4_CHASE_OFF}, {"on", JFS_READ_LZ4_CHASE_ON}, {nullptr, 0}},
     JFS_READ_LZ4_CHASE_ON, JFS_READ_LZ4_CHASE_ON};
+inline constexpr ModeDesc MODE_READ_LZ4_WINDOW{"JFS_READ_LZ4_WINDOW", JFS_READ_LZ4_WINDOW_OFF,
+    {{"off", JFS_READ_LZ4_WINDOW_OFF}, {"on", JFS_READ_LZ4_WINDOW_ON}, {nullptr, 0}},
+    JFS_READ_LZ4_WINDOW_ON, JFS_READ_LZ4_WINDOW_ON};
 inline constexpr ModeDesc MODE_ZSTD_PARSE{"JFS_ZSTD_PARSE", JFS_ZSTD_PARSE_EXACT,
     {{"exact", JFS_ZSTD_PARSE_EXACT}, {"fast", JFS_ZSTD_PARSE_FAST}, {"seekable", JFS_ZSTD_PARSE_SEEKABLE}},
     JFS_ZSTD_PARSE_FAST, JFS_ZSTD_PARSE_SEEKABLE};
@@ -104,6 +107,7 @@ using Lz4Parse = Mode<MODE_LZ4_PARSE>;
 using ReadDecode = Mode<MODE_READ_DECODE>;
 using ReadSeek = Mode<MODE_READ_SEEK>;
 using ReadLz4Chase = Mode<MODE_READ_LZ4_CHASE>;
+using ReadLz4Window = Mode<MODE_READ_LZ4_WINDOW>;
 using ZstdParse = Mode<MODE_ZSTD_PARSE>;
 using ZstdSeekCsum = Mode<MODE_ZSTD_SEEK_CSUM>;
 using CompactSplice = Mode<MODE_COMPACT_SPLICE>;

@@ -130,6 +130,12 @@ int jfs_launch_lz4_split(const jfs_dev_block *d_desc, int nb, int32_t *d_ret, vo
 int jfs_launch_lz4_split_prefix(const jfs_dev_block *d_desc, int nb, int32_t *d_ret, const int32_t *d_want,
                                 void *d_scratch, int64_t nseg_all, int64_t max_cap, int64_t norg_all, int64_t max_want,
                                 hipStream_t st);
+// the window decode (lz4_window.h): block b for its output bytes [d_lo[b], d_hi[b]), from the 64 KiB chunk
+// boundary below d_lo[b] where the probe proves that enough, else as the prefix launch with want = d_hi[b];
+// max_want: a host-side upper bound of the d_hi, as above
+int jfs_launch_lz4_split_window(const jfs_dev_block *d_desc, int nb, int32_t *d_ret, const int32_t *d_lo,
+                                const int32_t *d_hi, void *d_scratch, int64_t nseg_all, int64_t max_cap,
+                                int64_t norg_all, int64_t max_want, hipStream_t st);
 // ranges decode by origin chase (lz4_chase.hip): block i is decoded for the ranges d_rng[d_rng_first[i] ..
 // d_rng_first[i + 1]) of its output.  src_len / cap: the host's copies of the descriptors' sizes, which size the
 // scratch (jfs_lz4_chase_scratch_bytes) and the index grids; max_quads: a host-side upper bound of the 4-byte

@@ -64,17 +64,18 @@ JFS_OM_HD void put_lits(g_u32 *org, P p, P n, uint32_t v0) {
 }
 
 // entries [p, p + n) of a match at p with offset off: entry i = p - off +
-// (i mod off), the modulo as a running j (n may stop short of the match)
-template <class P>
-JFS_OM_HD void put_match(g_u32 *org, P p, P n, uint32_t off) {
+// (i mod off), the modulo as a running j (n may stop short of the match).
+// FROM: only the entries [p + i0, p + n) (a decode from a floor above 0).
+template <class P, bool FROM = false>
+JFS_OM_HD void put_match(g_u32 *org, P p, P n, uint32_t off, P i0 = 0) {
     const P base = p - (P)off;
-    uint32_t j = 0;
+    uint32_t j = FROM ? (uint32_t)i0 % off : 0u;
     auto next = [&]() {
         const uint32_t e = (uint32_t)(base + j);
         j = j + 1 == off ? 0u : j + 1;
         return e;
     };
-    P i = 0;
+    P i = FROM ? i0 : 0;
     for (; i < n && ((p + i) & 3); i++) org[p + i] = next();
     for (; i + 4 <= n; i += 4) {
         uint32_t e[4];
@@ -90,16 +91,20 @@ JFS_OM_UNROLL
 // interleaved (four independent loads in flight), and the quad is stored if
 // it changed.  load(o) reads entry o (o < total: an entry at or above total is
 // neither followed nor changed).  Returns whether anything was stored.
-template <class LD>
-JFS_OM_HD bool jump_walk(g_u32 *org, int64_t total, int64_t first, int64_t stride, LD load) {
+// FROM: the map holds the entries [start, total) only (a decode from a floor
+// above 0); the walk covers the quads from start's on, `first` counted from
+// there, and an entry below start is neither followed nor changed.
+template <bool FROM = false, class LD>
+JFS_OM_HD bool jump_walk(g_u32 *org, int64_t total, int64_t first, int64_t stride, LD load, int64_t start = 0) {
     bool any = false;
-    for (int64_t p = first; p < total; p += stride) {
+    for (int64_t p = FROM ? (start & ~(int64_t)3) + first : first; p < total; p += stride) {
         const int lim = total - p < 4 ? (int)(total - p) : 4;
+        const int low = FROM && start > p ? (int)(start - p) : 0;
         const uint4 v = *(const g_u4 *)(org + p);
         const uint32_t e0[4] = {v.x, v.y, v.z, v.w};
         int32_t o[4];  // (negative: a literal, or past total)
 JFS_OM_UNROLL
-        for (int i = 0; i < 4; i++) o[i] = i < lim ? (int32_t)e0[i] : -1;
+        for (int i = 0; i < 4; i++) o[i] = i < lim && (!FROM || i >= low) ? (int32_t)e0[i] : -1;
         for (int h = 0; h < HOPS; h++) {
             if (o[0] < 0 && o[1] < 0 && o[2] < 0 && o[3] < 0) break;
             int32_t nx[4];
@@ -112,7 +117,7 @@ JFS_OM_UNROLL
         bool changed = false;
 JFS_OM_UNROLL
         for (int i = 0; i < 4; i++) {
-            e[i] = i < lim ? (uint32_t)o[i] : e0[i];
+            e[i] = i < lim && (!FROM || i >= low) ? (uint32_t)o[i] : e0[i];
             changed |= e[i] != e0[i];
         }
         if (changed) {
@@ -126,20 +131,23 @@ JFS_OM_UNROLL
 // ---- gather step: the quad at p (a multiple of 4, below total).  Writes
 // dst[p + i] = lit[index of org[p + i]] for p + i < total and returns true, or
 // writes nothing and returns false when one of those entries is not a literal.
-JFS_OM_HD bool gather_quad(const g_u32 *org, const g_u8 *lit, g_u8 *dst, int64_t p, int64_t total) {
+// FROM: only the positions at or above start (the map holds nothing below it).
+template <bool FROM = false>
+JFS_OM_HD bool gather_quad(const g_u32 *org, const g_u8 *lit, g_u8 *dst, int64_t p, int64_t total, int64_t start = 0) {
     const uint4 v = *(const g_u4 *)(org + p);
     const uint32_t e[4] = {v.x, v.y, v.z, v.w};
     bool settled = true;
 JFS_OM_UNROLL
-    for (int i = 0; i < 4; i++) settled &= p + i >= total || is_lit(e[i]);
+    for (int i = 0; i < 4; i++) settled &= p + i >= total || (FROM && p + i < start) || is_lit(e[i]);
     if (!settled) return false;
-    if (p + 4 <= total && (((uintptr_t)(dst + p)) & 3u) == 0) {
+    if (p + 4 <= total && (!FROM || p >= start) && (((uintptr_t)(dst + p)) & 3u) == 0) {
         uint32_t w = 0;
 JFS_OM_UNROLL
         for (int i = 0; i < 4; i++) w |= (uint32_t)lit[lit_index(e[i])] << (8 * i);
         *(g_u32 *)(dst + p) = w;
     } else {
-        for (int i = 0; i < 4 && p + i < total; i++) dst[p + i] = lit[lit_index(e[i])];
+        for (int i = 0; i < 4 && p + i < total; i++)
+            if (!FROM || p + i >= start) dst[p + i] = lit[lit_index(e[i])];
     }
     return true;
 }

@@ -235,6 +235,31 @@ def lz4_decompress_ranges(desc: torch.Tensor, rng_first: torch.Tensor, rng: torc
                                                      _stream_ptr(stream)), "jfs_lz4_decompress_ranges_device")
 
 
+def lz4_decompress_window(desc: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor, ret: torch.Tensor, src_lens, dst_caps,
+                          stream=None):
+    """jfs_lz4_decompress_window_device_small: block i is decoded for its output
+    bytes [lo[i], hi[i]) (int32 device tensors, one entry per descriptor) from
+    the 64 KiB chunk boundary below lo[i] where the block's sequences allow it,
+    else from byte 0; src_lens / dst_caps are host copies of the descriptors'
+    sizes.  ret[i] = min(size, hi[i] clamped) for a well-formed block."""
+    n = desc.numel() // DESC_DTYPE.itemsize
+    assert lo.dtype == torch.int32 and hi.dtype == torch.int32 and lo.numel() >= n and hi.numel() >= n
+    sl = (ctypes.c_int32 * max(n, 1))(*[int(x) for x in src_lens])
+    dc = (ctypes.c_int32 * max(n, 1))(*[int(x) for x in dst_caps])
+    _check(L.load().jfs_lz4_decompress_window_device_small(desc.data_ptr(), sl, dc, lo.data_ptr(), hi.data_ptr(), n,
+                                                           ret.data_ptr(), _stream_ptr(stream)),
+           "jfs_lz4_decompress_window_device_small")
+
+
+def lz4_window_counts(reset: bool = False):
+    """(blocks the window decode took from a floor above 0, blocks whose probe
+    sent them to floor 0, blocks handed to the exact kernel, origin entries
+    written) on the current device."""
+    out = (ctypes.c_uint64 * 4)()
+    _check(L.load().jfs_lz4_window_counts(out, 1 if reset else 0), "jfs_lz4_window_counts")
+    return tuple(int(x) for x in out)
+
+
 def lz4_chase_counts(reset: bool = False):
     """(blocks the origin chase resolved, bytes requested of them, chain steps
     taken, blocks handed to the prefix path) on the current device."""
