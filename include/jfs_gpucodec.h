@@ -304,6 +304,34 @@ int64_t jfs_lz4_compress_device_small(const jfs_dev_block *d_blocks, const int32
  * not consult jfs_lz4_parse_mode. */
 int64_t jfs_lz4_compress_fast_device(const jfs_dev_block *d_blocks, const int32_t *src_len, int nblk, int32_t *d_ret,
                                      void *stream);
+/* jfs_lz4_compress_fast_device with LIFTED chunks (compaction; juicefs_amd/csrc/
+ * lz4_lift.h has the rule).  The blocks of d_blocks were gathered from decoded
+ * sources; d_lift[g], one per 64 KiB chunk of the blocks in order (block after
+ * block, ceil(src_len / 65536) each, 1 for an empty block, none for a block over
+ * 0x7E000000 bytes), names the source chunk whose bytes chunk g is: bytes
+ * [src_chunk * 65536, (src_chunk + 1) * 65536) of source `src`.  That is the
+ * caller's statement and is not checked.  The sequence records of such a chunk
+ * are read back from the source's stored LZ4 stream instead of being parsed
+ * again, where the device finds that they are what the parse would leave; every
+ * other chunk -- src < 0, src >= nsrc, src_chunk < 0 or past the source's end, a
+ * source that failed, a chunk whose stream the rule refuses -- is parsed as
+ * without this call, never a fault.  For a source the fast encoder wrote the
+ * bytes and d_ret EQUAL jfs_lz4_compress_fast_device's on the same blocks; for
+ * any other source they are a valid LZ4 block of the same content.
+ * d_src[i]: src / src_len = source i's stored stream, dst_cap = its decode
+ * capacity (dst is not read); d_src_n[i] = what it decoded to, as a decoder's
+ * d_ret wrote it; src_src_len / src_cap = HOST copies of d_src's src_len and
+ * dst_cap (they size the scratch: some 44 bytes per 256 stored bytes beside the
+ * fast encoder's).  d_lifted (may be NULL): chunks lifted per block.
+ * JFS_ERR_INVALID for a NULL array with a positive count. */
+typedef struct jfs_lz4_lift {
+    int32_t src;       /* < 0: parse */
+    int32_t src_chunk;
+} jfs_lz4_lift;
+int64_t jfs_lz4_compress_fast_lift_device(const jfs_dev_block *d_blocks, const int32_t *src_len, int nblk,
+                                          const jfs_lz4_lift *d_lift, const jfs_dev_block *d_src,
+                                          const int32_t *d_src_n, const int32_t *src_src_len, const int32_t *src_cap,
+                                          int nsrc, int32_t *d_ret, int32_t *d_lifted, void *stream);
 /* Diagnostics of the segment encoder: out[r] (r = 1..16) = blocks whose
  * segments settled after r rounds, out[0] = blocks handed to the serial kernel
  * (not settled within JFS_LZ4E_SEG_ROUNDS, default 8, or a segment with too
@@ -916,6 +944,32 @@ int64_t jfs_zstd_seek_tables_device(const jfs_dev_block *d_blocks, const int32_t
 int jfs_compact_splice_mode(void);
 int jfs_set_compact_splice_mode(int mode);
 int jfs_set_compact_splice_mode_ext(int mode);
+/* The LZ4 lift switch of the compaction calls (jfs_compact_batch and
+ * jfs_compact_seal_batch with algo = LZ4), a switch of its own: JFS_COMPACT_SPLICE
+ * never changes what an LZ4 call does.  JFS_COMPACT_LZ4_LIFT_OFF (default):
+ * nothing changes, every call is queued as before.  JFS_COMPACT_LZ4_LIFT_ON: where
+ * the LZ4 parse mode is JFS_LZ4_PARSE_FAST and the plan has an output chunk that is
+ * one whole 64 KiB chunk of one source (one segment covers it, chunk-aligned in
+ * both, not within 12 bytes of either block's end), the encode step is
+ * jfs_lz4_compress_fast_lift_device's: such chunks are not parsed again.  out_n,
+ * the bytes, crc and src_n are the switch off's ONLY for sources the fast encoder
+ * wrote.  For a source of any other encoder the device refuses most candidates
+ * (its matches cross chunk boundaries) and parses them, at the cost of the index
+ * of their streams; a chunk the rule does accept there -- typically chunk 0, when
+ * no match straddles its end -- is emitted from the source's own sequences, so
+ * the object is a valid LZ4 block of the same content whose bytes may differ
+ * from the switch off's.  Measured: calls of a hundred blocks or more
+ * on fast-parse volumes gain a few percent, smaller calls lose.  The initial value is read once from JFS_COMPACT_LZ4_LIFT =
+ * "off" | "on" (case-insensitive; anything else, or unset: off).  The setter
+ * returns the previous value, or -1 for an unknown one (which changes nothing). */
+#define JFS_COMPACT_LZ4_LIFT_OFF 0
+#define JFS_COMPACT_LZ4_LIFT_ON 1
+int jfs_compact_lz4_lift_mode(void);
+int jfs_set_compact_lz4_lift_mode(int mode);
+/* Diagnostics of those calls since the last reset, process-wide: out[0] = calls
+ * that took the lift, out[1] = candidate chunks planned, out[2] = chunks lifted,
+ * out[3] = candidates the device refused and parsed.  0, or -1 (NULL). */
+int jfs_compact_lz4_lift_counts(uint64_t out[4], int reset);
 /* Diagnostics of the spliced calls since the last reset, process-wide: out[0] =
  * outputs spliced, out[1] = frames passed, out[2] = frames re-encoded inside
  * spliced outputs, out[3] = compressed bytes passed.  0, or -1 (NULL). */

@@ -20,6 +20,10 @@ extern "C" {
  * same bytes (0, and not a byte, when the block does not fit dst_cap).  Not a
  * fallback: no product entry point calls it. */
 int64_t jfs_test_lz4_fast_host(uint8_t *dst, int64_t dst_cap, const uint8_t *src, int64_t n);
+/* Chunks per launch group of the fast encoder (default 8,192; 0 restores it), so
+ * that a test reaches several groups with small blocks.  Returns the previous
+ * value.  Process-wide; not for use while a call is in flight. */
+int jfs_test_set_lz4_fast_group_chunks(int chunks);
 
 #ifdef __cplusplus
 }

@@ -62,9 +62,13 @@ EXPORTS = [
     "jfs_set_read_lz4_chase_mode", "jfs_lz4_chase_max", "jfs_set_lz4_chase_max",
     "jfs_lz4_decompress_window_device_small", "jfs_lz4_window_counts", "jfs_read_lz4_window_mode",
     "jfs_set_read_lz4_window_mode",
+    "jfs_lz4_compress_fast_lift_device", "jfs_compact_lz4_lift_mode", "jfs_set_compact_lz4_lift_mode",
+    "jfs_compact_lz4_lift_counts",
 ]
 # the hook include/jfs_gpucodec_lz4_fast_test.h declares (the fast LZ4 encoder's host twin)
 LZ4_FAST_TEST_EXPORTS = ["jfs_test_lz4_fast_host"]
+# and the hook of the lift's tests in the same header (the fast encoder's chunks per launch group)
+LZ4_LIFT_TEST_EXPORTS = ["jfs_test_set_lz4_fast_group_chunks"]
 # the hooks include/jfs_gpucodec_zstd_fast_test.h declares (the fast Zstd parse: host twin, kernels)
 ZSTD_FAST_TEST_EXPORTS = ["jfs_test_zstd_fast_host_seqs", "jfs_test_zstd_fast_seqs_device"]
 
@@ -74,6 +78,7 @@ ZSTD_PARSE_EXACT, ZSTD_PARSE_FAST, ZSTD_PARSE_SEEKABLE = 0, 1, 2
 READ_SEEK_OFF, READ_SEEK_ON, READ_SEEK_SPARSE = 0, 1, 2
 READ_LZ4_CHASE_OFF, READ_LZ4_CHASE_ON = 0, 1
 READ_LZ4_WINDOW_OFF, READ_LZ4_WINDOW_ON = 0, 1
+COMPACT_LZ4_LIFT_OFF, COMPACT_LZ4_LIFT_ON = 0, 1
 ZSTD_SPLIT_FRAMES_MAX = 16384
 ZSTD_SEEK_CSUM_OFF, ZSTD_SEEK_CSUM_ON = 0, 1
 COMPACT_SPLICE_OFF, COMPACT_SPLICE_ON, COMPACT_SPLICE_ALL = 0, 1, 2
@@ -270,6 +275,16 @@ def load() -> ctypes.CDLL:
     lib.jfs_lz4_parse_mode.restype = ctypes.c_int
     lib.jfs_set_lz4_parse_mode.argtypes = [ctypes.c_int]
     lib.jfs_set_lz4_parse_mode.restype = ctypes.c_int
+    lib.jfs_lz4_compress_fast_lift_device.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int, vp, vp, vp]
+    lib.jfs_lz4_compress_fast_lift_device.restype = i64
+    lib.jfs_compact_lz4_lift_mode.argtypes = []
+    lib.jfs_compact_lz4_lift_mode.restype = ctypes.c_int
+    lib.jfs_set_compact_lz4_lift_mode.argtypes = [ctypes.c_int]
+    lib.jfs_set_compact_lz4_lift_mode.restype = ctypes.c_int
+    lib.jfs_compact_lz4_lift_counts.argtypes = [vp, ctypes.c_int]
+    lib.jfs_compact_lz4_lift_counts.restype = ctypes.c_int
+    lib.jfs_test_set_lz4_fast_group_chunks.argtypes = [ctypes.c_int]
+    lib.jfs_test_set_lz4_fast_group_chunks.restype = ctypes.c_int
     lib.jfs_test_lz4_fast_host.argtypes = [vp, i64, vp, i64]
     lib.jfs_test_lz4_fast_host.restype = i64
     lib.jfs_zstd_parse_mode.argtypes = []

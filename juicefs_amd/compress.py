@@ -470,6 +470,36 @@ def compact_splice_counts(reset: bool = False):
     return tuple(int(x) for x in out)
 
 
+_COMPACT_LZ4_LIFT = {"off": L.COMPACT_LZ4_LIFT_OFF, "on": L.COMPACT_LZ4_LIFT_ON}
+
+
+def compact_lz4_lift_mode() -> str:
+    """The LZ4 lift switch of the compaction calls (jfs_compact_lz4_lift_mode):
+    "off", or "on" -- while the LZ4 parse mode is "fast", an output chunk that is
+    one whole 64 KiB chunk of one source takes its sequence records from the
+    source's stored stream instead of being parsed again; the bytes do not change."""
+    m = L.load().jfs_compact_lz4_lift_mode()
+    return next(k for k, v in _COMPACT_LZ4_LIFT.items() if v == m)
+
+
+def set_compact_lz4_lift_mode(mode: str) -> str:
+    """Set it (process-wide, for calls that start afterwards) and return the
+    previous value's name."""
+    if mode not in _COMPACT_LZ4_LIFT:
+        raise ValueError(f"compact lz4 lift mode {mode!r}: expected 'off' or 'on'")
+    prev = L.load().jfs_set_compact_lz4_lift_mode(_COMPACT_LZ4_LIFT[mode])
+    return next(k for k, v in _COMPACT_LZ4_LIFT.items() if v == prev)
+
+
+def compact_lz4_lift_counts(reset: bool = False):
+    """(calls that took the lift, candidate chunks planned, chunks lifted,
+    candidates the device refused and parsed) since the last reset."""
+    out = (ctypes.c_uint64 * 4)()
+    if L.load().jfs_compact_lz4_lift_counts(out, 1 if reset else 0) != 0:
+        raise RuntimeError("jfs_compact_lz4_lift_counts failed")
+    return tuple(int(x) for x in out)
+
+
 def zstd_seek_csum_mode() -> str:
     """The checksum switch of the seekable parse mode (jfs_zstd_seek_csum_mode):
     "off", or "on" -- while the Zstd parse mode is "seekable" the compress calls

@@ -1921,6 +1921,8 @@ int64_t jfs_set_lz4_chase_max(int64_t bytes) { return Lz4ChaseMax::set(bytes); }
 int jfs_compact_splice_mode(void) { return CompactSplice::get(); }
 int jfs_set_compact_splice_mode(int mode) { return CompactSplice::set(mode); }
 int jfs_set_compact_splice_mode_ext(int mode) { return CompactSplice::set_ext(mode); }
+int jfs_compact_lz4_lift_mode(void) { return CompactLz4Lift::get(); }
+int jfs_set_compact_lz4_lift_mode(int mode) { return CompactLz4Lift::set(mode); }
 
 int jfs_stats(jfs_op_stats *out, int n) {
     for (int i = 0; out && i < n && i < JFS_STATS_N; i++) {

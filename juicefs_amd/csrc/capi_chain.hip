@@ -21,6 +21,7 @@
 #include "capi_host.h"
 #include "chain_plan.h"
 #include "jfs_internal.h"
+#include "lz4_lift.h"
 #include "lz4_window.h"
 #include "splice_plan.h"
 #include "zstd_seek.h"
@@ -187,13 +188,14 @@ void chain_stage_plan(const Chain &c, const std::vector<ChainOut> &oo, const std
 
 // The small-batch LZ4 decoder and encoder (h_enc, or null) run one after the
 // other on the stream: they share slot 1's scratch, sized for both before
-// anything is queued.
-bool chain_lz4_scratch(const Chain &c, const jfs_dev_block *h_enc, bool fast) {
+// anything is queued.  lift_need (> 0: the encode step is the lift launcher's): its scratch instead of the encoder's.
+bool chain_lz4_scratch(const Chain &c, const jfs_dev_block *h_enc, bool fast, int64_t lift_need = 0) {
     if (!c.lz4) return true;
     const jfs_dev_block *h_sdesc = c.host<jfs_dev_block>(c.L.sdesc);
     int64_t need = 0;
     if (c.ns > 0) need = lz4_decode_scratch(c.ns, desc_lens(h_sdesc, c.ns).data(), desc_caps(h_sdesc, c.ns).data());
-    if (h_enc && c.no > 0) need = std::max(need, lz4_encode_scratch(c.no, desc_lens(h_enc, c.no).data(), fast));
+    if (h_enc && c.no > 0)
+        need = std::max(need, lift_need > 0 ? lift_need : lz4_encode_scratch(c.no, desc_lens(h_enc, c.no).data(), fast));
     return need <= 0 || c.s1->ensure_split(need);
 }
 
@@ -280,6 +282,29 @@ struct CompactOpts {
     uint32_t *crc;
 };
 
+// jfs_compact_lz4_lift_counts: calls that took the lift launcher, candidate chunks planned, chunks lifted, candidates
+// the device refused and parsed
+std::atomic<uint64_t> g_lift_counts[4];
+
+// The lift plan of a compaction call (lz4_lift.h) over the outputs and sources the device works on: empty unless
+// the call is LZ4 in the fast parse mode with JFS_COMPACT_LZ4_LIFT on.  The segments are the staged ones
+// (chain_remap), so a source the host answered is no candidate.
+jfs::lz4l::LiftPlan compact_lift_plan(const ChainCall &cc, bool fast) {
+    jfs::lz4l::LiftPlan lp;
+    if (cc.algo != JFS_ALGO_LZ4 || !fast || CompactLz4Lift::get() != JFS_COMPACT_LZ4_LIFT_ON || cc.ns <= 0 || cc.oo.empty())
+        return lp;
+    std::vector<int32_t> first(1, 0), total, cap;
+    std::vector<jfs_compact_seg> sg;
+    for (const ChainOut &o : cc.oo) {
+        for (int q = cc.seg_first[o.idx]; q < cc.seg_first[o.idx + 1]; q++)
+            sg.push_back(jfs_plan::chain_remap(cc.seg[q], cc.src_map, cc.ns));
+        first.push_back((int32_t)sg.size());
+        total.push_back((int32_t)o.total);
+    }
+    for (int k = 0; k < cc.ns; k++) cap.push_back((int32_t)cc.st[k].cap);
+    return jfs::lz4l::lift_plan((int)cc.oo.size(), first.data(), sg.data(), total.data(), cc.ns, cap.data());
+}
+
 // Compaction on one lane: stored sources (sealed payloads), keys and the plan
 // H2D, open in place, decode, the opens' verdicts merged into the source
 // lengths, gather, encode into the output's payload area, seal in place
@@ -290,6 +315,11 @@ struct CompactOpts {
 // nothing filled.  Per-block results of sealed calls follow BatchRun::finish's
 // rules for sealed batches, so they equal jfs_open_decompress_batch's and
 // jfs_compress_seal_batch's.
+// LZ4 in the fast parse mode with JFS_COMPACT_LZ4_LIFT on, where the plan has a
+// candidate chunk: the candidates and the sources to index ride in
+// the H2D copy, the encode step is the lift launcher's over the stored (opened)
+// streams, and the chunks lifted per output come back with the results.  Any
+// other call is laid out and queued exactly as without the switch.
 int64_t compact_run(DevCtx *dev, Lane &ln, const ChainCall &cc, const CompactOpts &opt) {
     const int algo = cc.algo, cipher = cc.cipher;
     const std::vector<ChainSrc> &ss = cc.st;
@@ -303,7 +333,17 @@ int64_t compact_run(DevCtx *dev, Lane &ln, const ChainCall &cc, const CompactOpt
     ChainFlags flags{};
     flags.encode = true;
     flags.out_crc = crc != nullptr;
-    const int64_t rc = chain_open(c, ln, cc, oo, cc.seg_first, flags, {});
+    const bool fast = lz4_fast_mode();
+    const jfs::lz4l::LiftPlan lp = compact_lift_plan(cc, fast);
+    const bool lift = lp.candidates > 0;
+    const int nsel = (int)lp.srcs.size();
+    const int64_t m_sel = align16((int64_t)lp.chunk.size() * (int64_t)sizeof(jfs_lz4_lift));
+    ChainExtra x;
+    if (lift) {
+        x.meta = m_sel + align16(nsel * 4ll);
+        x.res = align16((int64_t)oo.size() * 4);
+    }
+    const int64_t rc = chain_open(c, ln, cc, oo, cc.seg_first, flags, x);
     if (rc != JFS_OK) return rc;
     const ChainLayout &L = c.L;
     const int ns = c.ns, no = c.no;
@@ -325,8 +365,19 @@ int64_t compact_run(DevCtx *dev, Lane &ln, const ChainCall &cc, const CompactOpt
             jfs_aead_block{pay, pay, (int32_t)oo[k].total, (int32_t)(oo[k].cap + 16), d_cell, d_cell + 32};
         if (crc) c.host<uint32_t>(L.oseed)[k] = seal_header_crc(p);
     }
-    const bool fast = lz4_fast_mode();
-    if (!chain_lz4_scratch(c, h_enc, fast)) return JFS_ERR_NO_MEMORY;
+    std::vector<int32_t> sel_len(nsel), sel_cap(nsel);
+    int64_t lift_need = 0;
+    if (lift) {
+        memcpy(c.h + L.xmeta, lp.chunk.data(), lp.chunk.size() * sizeof(jfs_lz4_lift));
+        memcpy(c.h + L.xmeta + m_sel, lp.srcs.data(), (size_t)nsel * 4);
+        const jfs_dev_block *h_sdesc = c.host<jfs_dev_block>(L.sdesc);
+        for (int q = 0; q < nsel; q++) {
+            sel_len[q] = h_sdesc[lp.srcs[q]].src_len;
+            sel_cap[q] = h_sdesc[lp.srcs[q]].dst_cap;
+        }
+        lift_need = jfs_lz4_fast_lift_scratch_bytes(no, desc_lens(h_enc, no).data(), ns, nsel, sel_len.data());
+    }
+    if (!chain_lz4_scratch(c, h_enc, fast, lift_need)) return JFS_ERR_NO_MEMORY;
     hipStream_t ks = c.ks;
     // one H2D: stored sources, the plan, keys and the preset source lengths
     if (hipMemcpyAsync(c.d, c.h, (size_t)L.h2d, hipMemcpyHostToDevice, ks) != hipSuccess) return JFS_ERR_HIP;
@@ -340,8 +391,14 @@ int64_t compact_run(DevCtx *dev, Lane &ln, const ChainCall &cc, const CompactOpt
     int lk = chain_decode(c, {});
     if (lk == 0) lk = gather(0);
     if (lk == 0 && codec && no > 0) {
-        lk = c.lz4 ? (launch_lz4_encode(*c.s1, h_enc, d_enc, no, d_ret, ks, fast) == JFS_OK ? 0 : -1)
-                   : launch_kernel(algo, COMPRESS, d_enc, no, d_ret, ks, zstd_encode_now());
+        if (lift) {
+            const jfs_lz4_lift_srcs S{d_sdesc, d_srcn, ns, c.dev<int32_t>(L.xmeta + m_sel), nsel, sel_len.data(), sel_cap.data()};
+            lk = jfs_launch_lz4_fast_lift(d_enc, no, desc_lens(h_enc, no).data(), c.dev<jfs_lz4_lift>(L.xmeta), &S, d_ret,
+                                          c.dev<int32_t>(L.xres), c.s1->sp, c.s1->sp_cap, ks);
+        } else {
+            lk = c.lz4 ? (launch_lz4_encode(*c.s1, h_enc, d_enc, no, d_ret, ks, fast) == JFS_OK ? 0 : -1)
+                       : launch_kernel(algo, COMPRESS, d_enc, no, d_ret, ks, zstd_encode_now());
+        }
         // the encoder ran on every block: a failed gather's verdict replaces its result
         if (lk == 0) lk = gather(1);
     }
@@ -379,6 +436,15 @@ int64_t compact_run(DevCtx *dev, Lane &ln, const ChainCall &cc, const CompactOpt
         if (crc) crc[j] = res[k] >= 0 ? c.host<uint32_t>(L.ocrc)[k] : 0u;
     }
     par_copy(jobs);
+    if (lift) {
+        uint64_t lifted = 0;
+        for (int k = 0; k < no; k++) lifted += (uint64_t)std::max(c.host<int32_t>(L.xres)[k], 0);
+        const uint64_t planned = (uint64_t)lp.candidates;
+        g_lift_counts[0].fetch_add(1, std::memory_order_relaxed);
+        g_lift_counts[1].fetch_add(planned, std::memory_order_relaxed);
+        g_lift_counts[2].fetch_add(lifted, std::memory_order_relaxed);
+        g_lift_counts[3].fetch_add(planned > lifted ? planned - lifted : 0, std::memory_order_relaxed);
+    }
     return JFS_OK;
 }
 
@@ -989,6 +1055,13 @@ int jfs_compact_splice_counts(uint64_t out[4], int reset) {
     if (!out) return -1;
     for (int k = 0; k < 4; k++)
         out[k] = reset ? g_splice_counts[k].exchange(0) : g_splice_counts[k].load(std::memory_order_relaxed);
+    return 0;
+}
+
+int jfs_compact_lz4_lift_counts(uint64_t out[4], int reset) {
+    if (!out) return -1;
+    for (int k = 0; k < 4; k++)
+        out[k] = reset ? g_lift_counts[k].exchange(0) : g_lift_counts[k].load(std::memory_order_relaxed);
     return 0;
 }
 

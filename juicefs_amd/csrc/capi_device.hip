@@ -153,6 +153,28 @@ int64_t jfs_lz4_compress_fast_device(const jfs_dev_block *d_blocks, const int32_
                           });
 }
 
+int64_t jfs_lz4_compress_fast_lift_device(const jfs_dev_block *d_blocks, const int32_t *src_len, int nblk,
+                                          const jfs_lz4_lift *d_lift, const jfs_dev_block *d_src,
+                                          const int32_t *d_src_n, const int32_t *src_src_len, const int32_t *src_cap,
+                                          int nsrc, int32_t *d_ret, int32_t *d_lifted, void *stream) {
+    if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
+    if (nblk < 0 || nsrc < 0 || (nblk > 0 && (!d_blocks || !src_len || !d_lift || !d_ret)) ||
+        (nsrc > 0 && (!d_src || !d_src_n || !src_src_len || !src_cap)))
+        return JFS_ERR_INVALID;
+    if (nblk == 0) return JFS_OK;
+    // (no source: every chunk is a parse chunk, and there is nothing to index)
+    if (nsrc == 0) {
+        if (d_lifted && hipMemsetAsync(d_lifted, 0, (size_t)nblk * 4, (hipStream_t)stream) != hipSuccess) return JFS_ERR_HIP;
+        return jfs_lz4_compress_fast_device(d_blocks, src_len, nblk, d_ret, stream);
+    }
+    // (the candidates live on the device only: every source is indexed)
+    const jfs_lz4_lift_srcs S{d_src, d_src_n, nsrc, nullptr, nsrc, src_src_len, src_cap};
+    return scratch_launch(g_fast_scr, COMPRESS, nblk, jfs_lz4_fast_lift_scratch_bytes(nblk, src_len, nsrc, nsrc, src_src_len),
+                          stream, [&](uint8_t *p, int64_t cap, hipStream_t st) {
+                              return jfs_launch_lz4_fast_lift(d_blocks, nblk, src_len, d_lift, &S, d_ret, d_lifted, p, cap, st);
+                          });
+}
+
 int64_t jfs_lz4_compress_device(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, void *stream) {
     if (!current_device_ok()) return JFS_ERR_NO_DEVICE;
     stat_launch(JFS_ALGO_LZ4, COMPRESS, nblk);

@@ -1,5 +1,5 @@
 // The run-time switches of the C ABI (include/jfs_gpucodec.h), each described
-// once: the eight enumerated ones by environment name, default, accepted
+// once: the nine enumerated ones by environment name, default, accepted
 // spellings and what their setters take; the two integer ones by name, default
 // and closed range.  The initial value is read once from the environment,
 // case-insensitively; an unknown or malformed value gives the default.  A
@@ -98,6 +98,9 @@ inline constexpr ModeDesc MODE_ZSTD_SEEK_CSUM{"JFS_ZSTD_SEEK_CSUM", JFS_ZSTD_SEE
 inline constexpr ModeDesc MODE_COMPACT_SPLICE{"JFS_COMPACT_SPLICE", JFS_COMPACT_SPLICE_OFF,
     {{"off", JFS_COMPACT_SPLICE_OFF}, {"on", JFS_COMPACT_SPLICE_ON}, {"all", JFS_COMPACT_SPLICE_ALL}},
     JFS_COMPACT_SPLICE_ON, JFS_COMPACT_SPLICE_ALL};
+inline constexpr ModeDesc MODE_COMPACT_LZ4_LIFT{"JFS_COMPACT_LZ4_LIFT", JFS_COMPACT_LZ4_LIFT_OFF,
+    {{"off", JFS_COMPACT_LZ4_LIFT_OFF}, {"on", JFS_COMPACT_LZ4_LIFT_ON}, {nullptr, 0}},
+    JFS_COMPACT_LZ4_LIFT_ON, JFS_COMPACT_LZ4_LIFT_ON};
 // bytes per source, default 0 (the measured crossover)
 inline constexpr IntDesc INT_LZ4_CHASE_MAX{"JFS_LZ4_CHASE_MAX", 0, 0, INT32_MAX};
 inline constexpr IntDesc INT_ZSTD_SPLIT_FRAMES{"JFS_ZSTD_SPLIT_FRAMES", JFS_ZSTD_SPLIT_FRAMES_MAX, 1, JFS_ZSTD_SPLIT_FRAMES_MAX};
@@ -111,6 +114,7 @@ using ReadLz4Window = Mode<MODE_READ_LZ4_WINDOW>;
 using ZstdParse = Mode<MODE_ZSTD_PARSE>;
 using ZstdSeekCsum = Mode<MODE_ZSTD_SEEK_CSUM>;
 using CompactSplice = Mode<MODE_COMPACT_SPLICE>;
+using CompactLz4Lift = Mode<MODE_COMPACT_LZ4_LIFT>;
 using Lz4ChaseMax = IntSwitch<INT_LZ4_CHASE_MAX>;
 using ZstdSplitFrames = IntSwitch<INT_ZSTD_SPLIT_FRAMES>;
 

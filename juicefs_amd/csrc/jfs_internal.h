@@ -36,6 +36,37 @@ int jfs_launch_lz4_encode_seg(const jfs_dev_block *d_blocks, int nblk, const int
 int64_t jfs_lz4_fast_scratch_bytes(int nblk, const int32_t *lens);
 int jfs_launch_lz4_fast(const jfs_dev_block *d_blocks, int nblk, const int32_t *lens, int32_t *d_ret, void *scratch,
                         int64_t scratch_cap, hipStream_t stream);
+// The fast encode with LIFTED chunks (lz4_lift.h): d_lift[g] names, per output chunk in the flat
+// order of the launch groups, the source chunk its records are read back from (src < 0: parse).  The sources'
+// stored streams are indexed once (lz4_lift.hip), then every group runs plan, lift, parse (which skips the
+// lifted chunks), stitch and emit.  S: the sources; d_lifted (may be null): chunks lifted per output block.
+struct jfs_lz4_lift_srcs {
+    const jfs_dev_block *d_src;  // [nsrc] src / src_len: the stored stream; dst_cap: its decode capacity
+    const int32_t *d_src_n;      // [nsrc] what each source decoded to (negative: it failed)
+    int nsrc;
+    const int32_t *d_sel;        // [nsel] the sources to index (device), or null: all of them, nsel = nsrc
+    int nsel;
+    const int32_t *sel_len, *sel_cap;  // [nsel] the host's copies of their descriptors' src_len and dst_cap
+};
+int64_t jfs_lz4_fast_lift_scratch_bytes(int nblk, const int32_t *lens, int nsrc, int nsel, const int32_t *sel_len);
+int jfs_launch_lz4_fast_lift(const jfs_dev_block *d_blocks, int nblk, const int32_t *lens, const jfs_lz4_lift *d_lift,
+                             const jfs_lz4_lift_srcs *S, int32_t *d_ret, int32_t *d_lifted, void *scratch,
+                             int64_t scratch_cap, hipStream_t stream);
+// its parts in lz4_lift.hip: the index areas' bytes, the index launch (once per call, into d_scratch) and the
+// lift of one launch group (grp: where lz4_fast.hip keeps the group's parse results)
+struct jfs_lz4_lift_group {
+    int nblk, ncand;  // ncand: the chunks the host counted for the group, which d_lift holds
+    const int32_t *cfirst;
+    int32_t *nrec, *tail, *lit0, *body, *lifted;
+    uint2 *recs;
+};
+int64_t jfs_lz4_lift_index_bytes(int nsrc, int nsel, const int32_t *sel_len);
+int jfs_launch_lz4_lift_index(const jfs_lz4_lift_srcs *S, void *d_scratch, hipStream_t stream);
+int jfs_launch_lz4_lift(const jfs_dev_block *d_blocks, const jfs_lz4_lift_group *grp, int chunks,
+                        const jfs_lz4_lift *d_lift, const jfs_lz4_lift_srcs *S, void *d_scratch, int32_t *d_lifted,
+                        hipStream_t stream);
+// test hook (include/jfs_gpucodec_lz4_fast_test.h): chunks per launch group, 0 = the default
+int jfs_test_set_lz4_fast_group_chunks(int chunks);
 // parse_mode: JFS_ZSTD_PARSE_EXACT (libzstd's bytes), JFS_ZSTD_PARSE_FAST (zstd_fast.hip: valid frames, not libzstd's
 // bytes) or JFS_ZSTD_PARSE_SEEKABLE (the fast parse, one frame per 128 KiB block and a seek table)
 int jfs_launch_zstd_encode(const jfs_dev_block *d_blocks, int nblk, int32_t *d_ret, hipStream_t stream,

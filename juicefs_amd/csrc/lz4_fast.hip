@@ -4,9 +4,15 @@
 // lists into output offsets and the block's size (stitch), and one wave per
 // chunk writes the bytes of the blocks that fit (emit).  lz4_fast_host.cc
 // restates the parse on the host and gives the same bytes.
+// The LIFT form (jfs_launch_lz4_fast_lift; lz4_lift.h) runs
+// lz4_lift.hip's kernels between plan and parse: they fill the parse results of
+// the chunks whose records a compaction source's stored stream already holds,
+// and parse_kernel<true> returns at once for those.
 #include "jfs_internal.h"
 #include "lz4_fast.h"
 #include "wave.cuh"
+
+#include <algorithm>
 
 namespace jfs {
 namespace lz4f {
@@ -28,6 +34,7 @@ struct Ctl {
     int32_t *start, *cin, *delta;                         // [C] stitch results
     int32_t *fin_off, *fin_lit;                           // [B] the block's last (literal-only) sequence; off < 0: no emit
     uint2 *recs;                                          // [C * kMaxRec] {pos | mlen << 16, off | lit << 16}
+    const int32_t *lifted;                                // [C] the LIFT form: the chunk's results are in place
 };
 
 __device__ __forceinline__ uint32_t ld32u(const gc_u8 *p) {
@@ -88,6 +95,7 @@ __global__ __launch_bounds__(256) void plan_kernel(const jfs_dev_block *__restri
     if (hi == c.nblk) cfirst[c.nblk] = (int32_t)(run < cap ? run : cap);  // every such thread holds the total
 }
 
+template <bool LIFT>
 __global__ __launch_bounds__(64) void parse_kernel(const jfs_dev_block *__restrict__ blocks_, Ctl c) {
     __shared__ uint16_t tab[1 << kHashLog];
     gc_blk *blocks = (gc_blk *)blocks_;
@@ -95,6 +103,7 @@ __global__ __launch_bounds__(64) void parse_kernel(const jfs_dev_block *__restri
     const int lane = lane_id();
     const int g = (int)blockIdx.x;
     if (g >= cfirst[c.nblk]) return;
+    if (LIFT && ((gc_i32 *)c.lifted)[g]) return;  // (the lift left this chunk's records and counts)
     const int b = find_block(cfirst, c.nblk, g);
     const int64_t n = blocks[b].src_len;
     if (!block_ok(n, cfirst[b + 1] - cfirst[b])) return;
@@ -406,13 +415,53 @@ Layout layout(int64_t B, int64_t C) {
     return y;
 }
 int64_t host_chunks(int32_t n) { return n >= 0 && n <= kMaxInput ? nchunks(n) : 0; }
+int g_group_chunks = kGroupChunks;  // (jfs_test_set_lz4_fast_group_chunks)
 // blocks [b0, return) form the next launch group
 int next_group(int nblk, const int32_t *lens, int b0, int64_t *chunks) {
     int64_t C = 0;
     int b = b0;
-    while (b < nblk && (b == b0 || C + host_chunks(lens[b]) <= kGroupChunks)) C += host_chunks(lens[b++]);
+    while (b < nblk && (b == b0 || C + host_chunks(lens[b]) <= g_group_chunks)) C += host_chunks(lens[b++]);
     *chunks = C;
     return b;
+}
+// the scratch views of a group of B blocks and C chunks
+Ctl views(uint8_t *base, const Layout &y, int B, int64_t C) {
+    Ctl c{};
+    c.nblk = B;
+    c.cap_chunks = (int)C;
+    c.cfirst = (int32_t *)base;
+    int32_t *pc = (int32_t *)(base + y.o_chunk);
+    c.nrec = pc;
+    c.tail = pc + C;
+    c.lit0 = pc + 2 * C;
+    c.body = pc + 3 * C;
+    c.start = pc + 4 * C;
+    c.cin = pc + 5 * C;
+    c.delta = pc + 6 * C;
+    c.fin_off = (int32_t *)(base + y.o_blk);
+    c.fin_lit = c.fin_off + B;
+    c.recs = (uint2 *)(base + y.o_rec);
+    return c;
+}
+// the LIFT form's scratch: [the groups' areas | lifted, one per chunk of the largest group | the index areas]
+struct LiftLayout {
+    int64_t o_lifted, o_index, total;
+};
+LiftLayout lift_layout(int nblk, const int32_t *lens, int64_t index_bytes) {
+    int64_t need = 0, cmax = 1;
+    for (int b0 = 0; b0 < nblk;) {
+        int64_t C;
+        const int b1 = next_group(nblk, lens, b0, &C);
+        C = C > 0 ? C : 1;
+        need = std::max(need, layout(b1 - b0, C).total);
+        cmax = std::max(cmax, C);
+        b0 = b1;
+    }
+    LiftLayout y;
+    y.o_lifted = a16(need);
+    y.o_index = (y.o_lifted + 4 * cmax + 255) & ~(int64_t)255;
+    y.total = y.o_index + index_bytes;
+    return y;
 }
 }  // namespace
 
@@ -445,27 +494,61 @@ extern "C" int jfs_launch_lz4_fast(const jfs_dev_block *d_blocks, int nblk, cons
         if (C < 1) C = 1;
         const Layout y = layout(B, C);
         if (!scratch || y.total > scratch_cap) return -1;
-        Ctl c{};
-        c.nblk = B;
-        c.cap_chunks = (int)C;
-        c.cfirst = (int32_t *)base;
-        int32_t *pc = (int32_t *)(base + y.o_chunk);
-        c.nrec = pc;
-        c.tail = pc + C;
-        c.lit0 = pc + 2 * C;
-        c.body = pc + 3 * C;
-        c.start = pc + 4 * C;
-        c.cin = pc + 5 * C;
-        c.delta = pc + 6 * C;
-        c.fin_off = (int32_t *)(base + y.o_blk);
-        c.fin_lit = c.fin_off + B;
-        c.recs = (uint2 *)(base + y.o_rec);
+        const Ctl c = views(base, y, B, C);
         hipLaunchKernelGGL(plan_kernel, dim3(1), dim3(256), 0, st, d_blocks + b0, c);
-        hipLaunchKernelGGL(parse_kernel, dim3((unsigned)C), dim3(64), 0, st, d_blocks + b0, c);
+        hipLaunchKernelGGL(parse_kernel<false>, dim3((unsigned)C), dim3(64), 0, st, d_blocks + b0, c);
         hipLaunchKernelGGL(stitch_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, d_blocks + b0, c,
                            d_ret + b0);
         hipLaunchKernelGGL(emit_kernel, dim3((unsigned)C), dim3(64), 0, st, d_blocks + b0, c);
         b0 = b1;
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+extern "C" int64_t jfs_lz4_fast_lift_scratch_bytes(int nblk, const int32_t *lens, int nsrc, int nsel,
+                                                   const int32_t *sel_len) {
+    return jfs::lz4f::lift_layout(nblk, lens, jfs_lz4_lift_index_bytes(nsrc, nsel, sel_len)).total;
+}
+
+extern "C" int jfs_launch_lz4_fast_lift(const jfs_dev_block *d_blocks, int nblk, const int32_t *lens,
+                                        const jfs_lz4_lift *d_lift, const jfs_lz4_lift_srcs *S, int32_t *d_ret,
+                                        int32_t *d_lifted, void *scratch, int64_t scratch_cap, hipStream_t st) {
+    using namespace jfs::lz4f;
+    if (nblk <= 0) return 0;
+    if (!S || S->nsrc <= 0 || S->nsel <= 0 || !d_lift) return -1;
+    uint8_t *base = (uint8_t *)scratch;
+    const LiftLayout ly = lift_layout(nblk, lens, jfs_lz4_lift_index_bytes(S->nsrc, S->nsel, S->sel_len));
+    if (!scratch || ly.total > scratch_cap) return -1;
+    // the index: once, in front of the first group, behind every group's areas
+    if (jfs_launch_lz4_lift_index(S, base + ly.o_index, st) != 0) return -1;
+    int64_t chunk0 = 0;  // the flat candidate array is offset per group
+    for (int b0 = 0; b0 < nblk;) {
+        int64_t C;
+        const int b1 = next_group(nblk, lens, b0, &C);
+        const int B = b1 - b0;
+        const int64_t own = C;
+        if (C < 1) C = 1;
+        Ctl c = views(base, layout(B, C), B, C);
+        int32_t *lifted = (int32_t *)(base + ly.o_lifted);
+        c.lifted = lifted;
+        const jfs_lz4_lift_group grp{B, (int)own, c.cfirst, c.nrec, c.tail, c.lit0, c.body, lifted, c.recs};
+        hipLaunchKernelGGL(plan_kernel, dim3(1), dim3(256), 0, st, d_blocks + b0, c);
+        if (jfs_launch_lz4_lift(d_blocks + b0, &grp, (int)C, d_lift + chunk0, S, base + ly.o_index,
+                                d_lifted ? d_lifted + b0 : nullptr, st) != 0)
+            return -1;
+        hipLaunchKernelGGL(parse_kernel<true>, dim3((unsigned)C), dim3(64), 0, st, d_blocks + b0, c);
+        hipLaunchKernelGGL(stitch_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, d_blocks + b0, c,
+                           d_ret + b0);
+        hipLaunchKernelGGL(emit_kernel, dim3((unsigned)C), dim3(64), 0, st, d_blocks + b0, c);
+        chunk0 += own;
+        b0 = b1;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// Test hook (include/jfs_gpucodec_lz4_fast_test.h)
+extern "C" int jfs_test_set_lz4_fast_group_chunks(int chunks) {
+    const int prev = jfs::lz4f::g_group_chunks;
+    jfs::lz4f::g_group_chunks = chunks > 0 ? chunks : jfs::lz4f::kGroupChunks;
+    return prev;
 }

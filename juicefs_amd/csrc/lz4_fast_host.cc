@@ -76,16 +76,11 @@ uint8_t *put_len(uint8_t *o, int64_t v) {  // v = length - 15 already checked >=
     *o++ = (uint8_t)v;
     return o;
 }
-}  // namespace
 
-extern "C" int64_t jfs_test_lz4_fast_host(uint8_t *dst, int64_t dst_cap, const uint8_t *src, int64_t n) {
-    if (n < 0 || n > kMaxInput || dst_cap < 0) return 0;
-    std::vector<Rec> recs;
-    int64_t carry = 0;
-    for (int64_t cbase = 0; cbase < n; cbase += kChunk) {
-        const int64_t clen = n - cbase < kChunk ? n - cbase : kChunk;
-        carry = parse_chunk(src + cbase, n, cbase, clen, carry, recs);
-    }
+// The block of the sequences recs over src and `carry` trailing literals (stitch
+// and emit): its size, or 0 and not a byte when it does not fit dst_cap.
+// (tests/lz4_lift_main.cc includes this file and feeds it lifted records.)
+int64_t emit_block(uint8_t *dst, int64_t dst_cap, const uint8_t *src, const std::vector<Rec> &recs, int64_t carry) {
     int64_t total = 1 + len_bytes(carry) + carry;
     for (const Rec &r : recs) total += 1 + len_bytes(r.lit) + r.lit + 2 + len_bytes(r.mlen - kMinMatch);
     if (total > dst_cap) return 0;
@@ -107,4 +102,16 @@ extern "C" int64_t jfs_test_lz4_fast_host(uint8_t *dst, int64_t dst_cap, const u
     if (carry) memcpy(o, ip, (size_t)carry);
     o += carry;
     return o - dst == total ? total : 0;
+}
+}  // namespace
+
+extern "C" int64_t jfs_test_lz4_fast_host(uint8_t *dst, int64_t dst_cap, const uint8_t *src, int64_t n) {
+    if (n < 0 || n > kMaxInput || dst_cap < 0) return 0;
+    std::vector<Rec> recs;
+    int64_t carry = 0;
+    for (int64_t cbase = 0; cbase < n; cbase += kChunk) {
+        const int64_t clen = n - cbase < kChunk ? n - cbase : kChunk;
+        carry = parse_chunk(src + cbase, n, cbase, clen, carry, recs);
+    }
+    return emit_block(dst, dst_cap, src, recs, carry);
 }

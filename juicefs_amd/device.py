@@ -147,6 +147,27 @@ def lz4_compress_fast(desc: torch.Tensor, ret: torch.Tensor, src_lens, stream=No
            "jfs_lz4_compress_fast_device")
 
 
+LIFT_DTYPE = np.dtype([("src", "<i4"), ("src_chunk", "<i4")])  # jfs_lz4_lift
+
+
+def lz4_compress_fast_lift(desc: torch.Tensor, ret: torch.Tensor, src_lens, lift: torch.Tensor, src_desc: torch.Tensor,
+                           src_n: torch.Tensor, src_src_lens, src_caps, lifted: torch.Tensor | None = None, stream=None):
+    """jfs_lz4_compress_fast_lift_device: lz4_compress_fast of gathered blocks
+    whose chunks named in `lift` (LIFT_DTYPE records on the device, one per
+    64 KiB chunk, flat) take their sequence records from the stored streams of
+    the sources in src_desc (src_n: what each decoded to).  src_lens,
+    src_src_lens and src_caps are host copies; `lifted` (int32, one per block)
+    receives the chunks lifted."""
+    n = desc.numel() // DESC_DTYPE.itemsize
+    ns = src_desc.numel() // DESC_DTYPE.itemsize
+    sl = (ctypes.c_int32 * max(n, 1))(*[int(x) for x in src_lens])
+    ssl = (ctypes.c_int32 * max(ns, 1))(*[int(x) for x in src_src_lens])
+    scp = (ctypes.c_int32 * max(ns, 1))(*[int(x) for x in src_caps])
+    _check(L.load().jfs_lz4_compress_fast_lift_device(
+        desc.data_ptr(), sl, n, lift.data_ptr(), src_desc.data_ptr(), src_n.data_ptr(), ssl, scp, ns, ret.data_ptr(),
+        lifted.data_ptr() if lifted is not None else None, _stream_ptr(stream)), "jfs_lz4_compress_fast_lift_device")
+
+
 def lz4_eseg_counts(reset: bool = False):
     """Segment encoder: {rounds: blocks settled after that many rounds}, with
     0 = blocks handed to the serial kernel."""
