@@ -156,6 +156,11 @@ class JfsSpliceOut(ctypes.Structure):
 _lib = None
 
 
+def _proto(lib, name: str, restype, *argtypes):
+    f = getattr(lib, name)
+    f.restype, f.argtypes = restype, list(argtypes)
+
+
 def load() -> ctypes.CDLL:
     """Load libjfsgpu.so; raises if it has not been built."""
     global _lib
@@ -191,48 +196,16 @@ def load() -> ctypes.CDLL:
     lib.jfs_zstd_decompress_prefix_device.restype = i64
     lib.jfs_zstd_decompress_range_device.argtypes = [vp, vp, vp, ctypes.c_int, vp, vp]
     lib.jfs_zstd_decompress_range_device.restype = i64
-    lib.jfs_read_seek_mode.argtypes = []
-    lib.jfs_read_seek_mode.restype = ctypes.c_int
-    lib.jfs_set_read_seek_mode.argtypes = [ctypes.c_int]
-    lib.jfs_set_read_seek_mode.restype = ctypes.c_int
-    lib.jfs_set_read_seek_mode_ext.argtypes = [ctypes.c_int]
-    lib.jfs_set_read_seek_mode_ext.restype = ctypes.c_int
     lib.jfs_zstd_decompress_ranges_device.argtypes = [vp, vp, vp, ctypes.c_int, vp, vp]
     lib.jfs_zstd_decompress_ranges_device.restype = i64
     lib.jfs_lz4_decompress_ranges_device.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int, vp, vp]
     lib.jfs_lz4_decompress_ranges_device.restype = i64
-    lib.jfs_lz4_chase_counts.argtypes = [vp, ctypes.c_int]
-    lib.jfs_lz4_chase_counts.restype = ctypes.c_int
-    lib.jfs_read_lz4_chase_mode.argtypes = []
-    lib.jfs_read_lz4_chase_mode.restype = ctypes.c_int
-    lib.jfs_set_read_lz4_chase_mode.argtypes = [ctypes.c_int]
-    lib.jfs_set_read_lz4_chase_mode.restype = ctypes.c_int
     lib.jfs_lz4_decompress_window_device_small.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int, vp, vp]
     lib.jfs_lz4_decompress_window_device_small.restype = i64
-    lib.jfs_lz4_window_counts.argtypes = [vp, ctypes.c_int]
-    lib.jfs_lz4_window_counts.restype = ctypes.c_int
-    lib.jfs_read_lz4_window_mode.argtypes = []
-    lib.jfs_read_lz4_window_mode.restype = ctypes.c_int
-    lib.jfs_set_read_lz4_window_mode.argtypes = [ctypes.c_int]
-    lib.jfs_set_read_lz4_window_mode.restype = ctypes.c_int
-    lib.jfs_lz4_chase_max.argtypes = []
-    lib.jfs_lz4_chase_max.restype = i64
-    lib.jfs_set_lz4_chase_max.argtypes = [i64]
-    lib.jfs_set_lz4_chase_max.restype = i64
     lib.jfs_zstd_splice_device.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp, vp]
     lib.jfs_zstd_splice_device.restype = i64
-    lib.jfs_compact_splice_mode.argtypes = []
-    lib.jfs_compact_splice_mode.restype = ctypes.c_int
-    lib.jfs_set_compact_splice_mode.argtypes = [ctypes.c_int]
-    lib.jfs_set_compact_splice_mode.restype = ctypes.c_int
-    lib.jfs_set_compact_splice_mode_ext.argtypes = [ctypes.c_int]
-    lib.jfs_set_compact_splice_mode_ext.restype = ctypes.c_int
     lib.jfs_zstd_seek_tables_device.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp, vp]
     lib.jfs_zstd_seek_tables_device.restype = i64
-    lib.jfs_compact_splice_counts.argtypes = [vp, ctypes.c_int]
-    lib.jfs_compact_splice_counts.restype = ctypes.c_int
-    lib.jfs_zstd_sparse_counts.argtypes = [vp, ctypes.c_int]
-    lib.jfs_zstd_sparse_counts.restype = ctypes.c_int
     lib.jfs_xxh64_device.argtypes = [vp, ctypes.c_int, vp, vp, vp]
     lib.jfs_xxh64_device.restype = i64
     lib.jfs_zstd_compress_seekable_csum_device.argtypes = [vp, ctypes.c_int, vp, vp]
@@ -243,59 +216,21 @@ def load() -> ctypes.CDLL:
     lib.jfs_zstd_seek_plan.restype = i64
     lib.jfs_zstd_load_range_batch.argtypes = [ctypes.c_int, ctypes.POINTER(JfsRangeRead), ctypes.POINTER(i64), u32]
     lib.jfs_zstd_load_range_batch.restype = i64
-    lib.jfs_zstd_seek_csum_mode.argtypes = []
-    lib.jfs_zstd_seek_csum_mode.restype = ctypes.c_int
-    lib.jfs_set_zstd_seek_csum_mode.argtypes = [ctypes.c_int]
-    lib.jfs_set_zstd_seek_csum_mode.restype = ctypes.c_int
-    lib.jfs_set_zstd_parse_mode_ext.argtypes = [ctypes.c_int]
-    lib.jfs_set_zstd_parse_mode_ext.restype = ctypes.c_int
-    lib.jfs_read_decode_mode.argtypes = []
-    lib.jfs_read_decode_mode.restype = ctypes.c_int
-    lib.jfs_set_read_decode_mode.argtypes = [ctypes.c_int]
-    lib.jfs_set_read_decode_mode.restype = ctypes.c_int
-    lib.jfs_set_read_decode_mode_ext.argtypes = [ctypes.c_int]
-    lib.jfs_set_read_decode_mode_ext.restype = ctypes.c_int
-    lib.jfs_lz4_split_counts.argtypes = [vp, ctypes.c_int]
-    lib.jfs_lz4_split_counts.restype = ctypes.c_int
-    lib.jfs_zstd_split_counts.argtypes = [vp, ctypes.c_int]
-    lib.jfs_zstd_split_counts.restype = ctypes.c_int
-    lib.jfs_zstd_split_frame_counts.argtypes = [vp, ctypes.c_int]
-    lib.jfs_zstd_split_frame_counts.restype = ctypes.c_int
-    lib.jfs_get_zstd_split_frames.argtypes = []
-    lib.jfs_get_zstd_split_frames.restype = ctypes.c_int
-    lib.jfs_set_zstd_split_frames.argtypes = [ctypes.c_int]
-    lib.jfs_set_zstd_split_frames.restype = ctypes.c_int
     lib.jfs_test_set_split_jump_rounds.argtypes = [ctypes.c_int, ctypes.c_int]
     lib.jfs_test_set_split_jump_rounds.restype = ctypes.c_int
     lib.jfs_lz4_compress_device_small.argtypes = [vp, vp, ctypes.c_int, vp, vp]
     lib.jfs_lz4_compress_device_small.restype = ctypes.c_int64
     lib.jfs_lz4_compress_fast_device.argtypes = [vp, vp, ctypes.c_int, vp, vp]
     lib.jfs_lz4_compress_fast_device.restype = i64
-    lib.jfs_lz4_parse_mode.argtypes = []
-    lib.jfs_lz4_parse_mode.restype = ctypes.c_int
-    lib.jfs_set_lz4_parse_mode.argtypes = [ctypes.c_int]
-    lib.jfs_set_lz4_parse_mode.restype = ctypes.c_int
     lib.jfs_lz4_compress_fast_lift_device.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int, vp, vp, vp]
     lib.jfs_lz4_compress_fast_lift_device.restype = i64
-    lib.jfs_compact_lz4_lift_mode.argtypes = []
-    lib.jfs_compact_lz4_lift_mode.restype = ctypes.c_int
-    lib.jfs_set_compact_lz4_lift_mode.argtypes = [ctypes.c_int]
-    lib.jfs_set_compact_lz4_lift_mode.restype = ctypes.c_int
-    lib.jfs_compact_lz4_lift_counts.argtypes = [vp, ctypes.c_int]
-    lib.jfs_compact_lz4_lift_counts.restype = ctypes.c_int
     lib.jfs_test_set_lz4_fast_group_chunks.argtypes = [ctypes.c_int]
     lib.jfs_test_set_lz4_fast_group_chunks.restype = ctypes.c_int
     lib.jfs_test_lz4_fast_host.argtypes = [vp, i64, vp, i64]
     lib.jfs_test_lz4_fast_host.restype = i64
-    lib.jfs_zstd_parse_mode.argtypes = []
-    lib.jfs_zstd_parse_mode.restype = ctypes.c_int
-    lib.jfs_set_zstd_parse_mode.argtypes = [ctypes.c_int]
-    lib.jfs_set_zstd_parse_mode.restype = ctypes.c_int
     for f in (lib.jfs_test_zstd_fast_host_seqs, lib.jfs_test_zstd_fast_seqs_device):
         f.argtypes = [vp, i64, vp, i64, vp, vp]
         f.restype = i64
-    lib.jfs_lz4_eseg_counts.argtypes = [vp, ctypes.c_int]
-    lib.jfs_lz4_eseg_counts.restype = ctypes.c_int
     lib.jfs_cipher_from_name.argtypes = [ctypes.c_char_p]
     lib.jfs_cipher_from_name.restype = ctypes.c_int
     lib.jfs_cipher_key_size.argtypes = [ctypes.c_int]
@@ -389,5 +324,16 @@ def load() -> ctypes.CDLL:
     lib.jfs_gen_block_host.restype = None
     lib.jfs_selftest_wave.argtypes = [vp, vp]
     lib.jfs_selftest_wave.restype = ctypes.c_int
+    # the run-time switches and the counters, from their tables (switches.py imports this module, hence here)
+    from . import switches as S
+    for sw in S.ENUMS:
+        _proto(lib, sw.getter, ctypes.c_int)
+        for name in filter(None, (sw.setter, sw.ext)):
+            _proto(lib, name, ctypes.c_int, ctypes.c_int)
+    for sw in S.INTS:
+        _proto(lib, sw.getter, sw.ctype)
+        _proto(lib, sw.setter, sw.ctype, sw.ctype)
+    for c in S.COUNTERS:
+        _proto(lib, c.cname, ctypes.c_int, vp, ctypes.c_int)
     _lib = lib
     return lib

@@ -19,12 +19,15 @@ fallback (the library returns ``JFS_ERR_NO_DEVICE`` without a gfx950 GPU).
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes
 
 import numpy as np
 
 from . import _lib as L
+# the run-time switches (read_seek_mode, set_read_seek_mode, zstd_parse_mode, lz4_chase_max, ...: switches.__all__),
+# built from the one table in switches.py, and the two counter readers that belong here
+from .switches import *  # noqa: F401,F403
+from .switches import compact_lz4_lift_counts, compact_splice_counts  # noqa: F401
 
 ZSTD_LEVEL = 1
 
@@ -266,25 +269,6 @@ def NewCompressor(algr: str):
     return None
 
 
-_LZ4_PARSE = {"exact": L.LZ4_PARSE_EXACT, "fast": L.LZ4_PARSE_FAST}
-
-
-@contextlib.contextmanager
-def lz4_parse_mode(mode: str):
-    """Hold the LZ4 parse of the host-buffer compress calls at "exact"
-    (LZ4_compress_default's bytes) or "fast" (jfs_lz4_compress_fast_device's
-    blocks) and put the previous mode back on exit.  The mode is process-wide
-    (jfs_set_lz4_parse_mode)."""
-    if mode not in _LZ4_PARSE:
-        raise ValueError(f"lz4 parse mode {mode!r}: expected 'exact' or 'fast'")
-    lib = L.load()
-    prev = lib.jfs_set_lz4_parse_mode(_LZ4_PARSE[mode])
-    try:
-        yield
-    finally:
-        lib.jfs_set_lz4_parse_mode(prev)
-
-
 def lz4_fast_host(src) -> bytes:
     """The fast encoder's host twin (jfs_test_lz4_fast_host, test
     infrastructure): the bytes jfs_lz4_compress_fast_device writes for src."""
@@ -296,225 +280,7 @@ def lz4_fast_host(src) -> bytes:
     return dst.raw[:n]
 
 
-_ZSTD_PARSE = {"exact": L.ZSTD_PARSE_EXACT, "fast": L.ZSTD_PARSE_FAST, "seekable": L.ZSTD_PARSE_SEEKABLE}
-
-
-def set_zstd_parse_mode(mode: str) -> str:
-    """Set the Zstd parse of the host-buffer compress calls (process-wide, for
-    calls that start afterwards; jfs_set_zstd_parse_mode_ext) and return the
-    previous mode's name: "exact", "fast", or "seekable" -- the fast parse laid
-    out as one frame per 128 KiB block and a seek table
-    (jfs_zstd_compress_seekable_device's objects)."""
-    if mode not in _ZSTD_PARSE:
-        raise ValueError(f"zstd parse mode {mode!r}: expected 'exact', 'fast' or 'seekable'")
-    prev = L.load().jfs_set_zstd_parse_mode_ext(_ZSTD_PARSE[mode])
-    return next(k for k, v in _ZSTD_PARSE.items() if v == prev)
-
-
-@contextlib.contextmanager
-def zstd_parse_mode(mode: str):
-    """Hold the Zstd parse of the host-buffer compress calls at "exact"
-    (ZSTD_compress level 1's bytes), "fast" (jfs_zstd_compress_fast_device's
-    frames) or "seekable" (jfs_zstd_compress_seekable_device's objects) and put
-    the previous mode back on exit.  The mode is process-wide
-    (jfs_set_zstd_parse_mode_ext)."""
-    prev = set_zstd_parse_mode(mode)
-    try:
-        yield
-    finally:
-        set_zstd_parse_mode(prev)
-
-
-_READ_DECODE = {"full": L.READ_DECODE_FULL, "prefix": L.READ_DECODE_PREFIX, "prefix-all": L.READ_DECODE_PREFIX_ALL}
-
-
-def read_decode_mode() -> str:
-    """The decode mode of the read calls (jfs_read_decode_mode): "full", or
-    "prefix" -- every LZ4 decode stops at the last byte a read needs, or
-    "prefix-all" -- so does every Zstd decode, at the Zstd block that holds it."""
-    m = L.load().jfs_read_decode_mode()
-    return next(k for k, v in _READ_DECODE.items() if v == m)
-
-
-def set_read_decode_mode(mode: str) -> str:
-    """Set it (process-wide, for calls that start afterwards) and return the
-    previous mode's name."""
-    if mode not in _READ_DECODE:
-        raise ValueError(f"read decode mode {mode!r}: expected 'full', 'prefix' or 'prefix-all'")
-    prev = L.load().jfs_set_read_decode_mode_ext(_READ_DECODE[mode])
-    return next(k for k, v in _READ_DECODE.items() if v == prev)
-
-
-_READ_SEEK = {"off": L.READ_SEEK_OFF, "on": L.READ_SEEK_ON, "sparse": L.READ_SEEK_SPARSE}
-
-
-def read_seek_mode() -> str:
-    """The seek switch of the read calls (jfs_read_seek_mode): "off", or "on" --
-    every Zstd source is decoded through its seek table for the byte range the
-    reads ask of it (an object without one: prefix-decoded to their end), or
-    "sparse" -- for the list of ranges the reads ask of it, exactly the frames
-    they touch, tables with checksums read and verified too."""
-    m = L.load().jfs_read_seek_mode()
-    return next(k for k, v in _READ_SEEK.items() if v == m)
-
-
-def set_read_seek_mode(mode: str) -> str:
-    """Set it (process-wide, for calls that start afterwards) and return the
-    previous value's name."""
-    if mode not in _READ_SEEK:
-        raise ValueError(f"read seek mode {mode!r}: expected 'off', 'on' or 'sparse'")
-    prev = L.load().jfs_set_read_seek_mode_ext(_READ_SEEK[mode])
-    return next(k for k, v in _READ_SEEK.items() if v == prev)
-
-
-_READ_LZ4_CHASE = {"off": L.READ_LZ4_CHASE_OFF, "on": L.READ_LZ4_CHASE_ON}
-
-
-def read_lz4_chase_mode() -> str:
-    """The LZ4 chase switch of the read calls (jfs_read_lz4_chase_mode): "off",
-    or "on" -- an LZ4 source whose reads ask for at most lz4_chase_max() bytes
-    is decoded for exactly those bytes by the origin chase."""
-    m = L.load().jfs_read_lz4_chase_mode()
-    return next(k for k, v in _READ_LZ4_CHASE.items() if v == m)
-
-
-def set_read_lz4_chase_mode(mode: str) -> str:
-    """Set it (process-wide, for calls that start afterwards) and return the
-    previous value's name."""
-    if mode not in _READ_LZ4_CHASE:
-        raise ValueError(f"read lz4 chase mode {mode!r}: expected 'off' or 'on'")
-    prev = L.load().jfs_set_read_lz4_chase_mode(_READ_LZ4_CHASE[mode])
-    return next(k for k, v in _READ_LZ4_CHASE.items() if v == prev)
-
-
-_READ_LZ4_WINDOW = {"off": L.READ_LZ4_WINDOW_OFF, "on": L.READ_LZ4_WINDOW_ON}
-
-
-def read_lz4_window_mode() -> str:
-    """The LZ4 window switch of the read calls (jfs_read_lz4_window_mode):
-    "off", or "on" -- an LZ4 source of a small batch is decoded from the 64 KiB
-    chunk its reads start in, where the block's sequences allow it."""
-    m = L.load().jfs_read_lz4_window_mode()
-    return next(k for k, v in _READ_LZ4_WINDOW.items() if v == m)
-
-
-def set_read_lz4_window_mode(mode: str) -> str:
-    """Set it (jfs_set_read_lz4_window_mode) and return the previous value."""
-    if mode not in _READ_LZ4_WINDOW:
-        raise ValueError(f"read lz4 window mode {mode!r}: expected 'off' or 'on'")
-    prev = L.load().jfs_set_read_lz4_window_mode(_READ_LZ4_WINDOW[mode])
-    return next(k for k, v in _READ_LZ4_WINDOW.items() if v == prev)
-
-
-def lz4_chase_max() -> int:
-    """The most bytes the reads may ask of one LZ4 source for it to take the
-    chase (jfs_lz4_chase_max; JFS_LZ4_CHASE_MAX, default 0)."""
-    return int(L.load().jfs_lz4_chase_max())
-
-
-def set_lz4_chase_max(nbytes: int) -> int:
-    """Set it (jfs_set_lz4_chase_max) and return the previous value."""
-    prev = int(L.load().jfs_set_lz4_chase_max(int(nbytes)))
-    if prev < 0:
-        raise ValueError(f"lz4 chase max {nbytes!r}: expected 0 .. 2^31 - 1")
-    return prev
-
-
-def zstd_split_frames() -> int:
-    """The most frames a Zstd input may hold for the small-batch decode path to
-    replay it block-parallel (jfs_get_zstd_split_frames; default 16384)."""
-    return L.load().jfs_get_zstd_split_frames()
-
-
-def set_zstd_split_frames(n: int) -> int:
-    """Set it (process-wide, for launches enqueued afterwards) and return the
-    previous value; 1 hands every multi-frame input to the one-wave replay."""
-    if not isinstance(n, int) or isinstance(n, bool) or not 1 <= n <= L.ZSTD_SPLIT_FRAMES_MAX:
-        raise ValueError(f"zstd split frames {n!r}: expected an int in [1, {L.ZSTD_SPLIT_FRAMES_MAX}]")
-    return L.load().jfs_set_zstd_split_frames(n)
-
-
-_SEEK_CSUM = {"off": L.ZSTD_SEEK_CSUM_OFF, "on": L.ZSTD_SEEK_CSUM_ON}
 _PLAN_STATUS = {L.SEEK_PLAN_OK: "ok", L.SEEK_PLAN_MORE: "more", L.SEEK_PLAN_NONE: "none"}
-
-
-_COMPACT_SPLICE = {"off": L.COMPACT_SPLICE_OFF, "on": L.COMPACT_SPLICE_ON, "all": L.COMPACT_SPLICE_ALL}
-
-
-def compact_splice_mode() -> str:
-    """The splice switch of the Zstd compaction call (jfs_compact_splice_mode):
-    "off", or "on" -- while the Zstd parse mode is "seekable", a 128 KiB piece
-    of an output that is exactly one frame of a seekable source is copied as
-    stored bytes, and only the other pieces are decoded and re-encoded; or
-    "all" -- "on", and the sealed compaction call splices too, from seek tables
-    it lifts out of the sources once they are opened on the device."""
-    m = L.load().jfs_compact_splice_mode()
-    return next(k for k, v in _COMPACT_SPLICE.items() if v == m)
-
-
-def set_compact_splice_mode(mode: str) -> str:
-    """Set it (process-wide, for calls that start afterwards) and return the
-    previous value's name."""
-    if mode not in _COMPACT_SPLICE:
-        raise ValueError(f"compact splice mode {mode!r}: expected 'off', 'on' or 'all'")
-    prev = L.load().jfs_set_compact_splice_mode_ext(_COMPACT_SPLICE[mode])
-    return next(k for k, v in _COMPACT_SPLICE.items() if v == prev)
-
-
-def compact_splice_counts(reset: bool = False):
-    """(outputs spliced, frames passed, frames re-encoded inside spliced
-    outputs, compressed bytes passed) since the last reset."""
-    out = (ctypes.c_uint64 * 4)()
-    if L.load().jfs_compact_splice_counts(out, 1 if reset else 0) != 0:
-        raise RuntimeError("jfs_compact_splice_counts failed")
-    return tuple(int(x) for x in out)
-
-
-_COMPACT_LZ4_LIFT = {"off": L.COMPACT_LZ4_LIFT_OFF, "on": L.COMPACT_LZ4_LIFT_ON}
-
-
-def compact_lz4_lift_mode() -> str:
-    """The LZ4 lift switch of the compaction calls (jfs_compact_lz4_lift_mode):
-    "off", or "on" -- while the LZ4 parse mode is "fast", an output chunk that is
-    one whole 64 KiB chunk of one source takes its sequence records from the
-    source's stored stream instead of being parsed again; the bytes do not change."""
-    m = L.load().jfs_compact_lz4_lift_mode()
-    return next(k for k, v in _COMPACT_LZ4_LIFT.items() if v == m)
-
-
-def set_compact_lz4_lift_mode(mode: str) -> str:
-    """Set it (process-wide, for calls that start afterwards) and return the
-    previous value's name."""
-    if mode not in _COMPACT_LZ4_LIFT:
-        raise ValueError(f"compact lz4 lift mode {mode!r}: expected 'off' or 'on'")
-    prev = L.load().jfs_set_compact_lz4_lift_mode(_COMPACT_LZ4_LIFT[mode])
-    return next(k for k, v in _COMPACT_LZ4_LIFT.items() if v == prev)
-
-
-def compact_lz4_lift_counts(reset: bool = False):
-    """(calls that took the lift, candidate chunks planned, chunks lifted,
-    candidates the device refused and parsed) since the last reset."""
-    out = (ctypes.c_uint64 * 4)()
-    if L.load().jfs_compact_lz4_lift_counts(out, 1 if reset else 0) != 0:
-        raise RuntimeError("jfs_compact_lz4_lift_counts failed")
-    return tuple(int(x) for x in out)
-
-
-def zstd_seek_csum_mode() -> str:
-    """The checksum switch of the seekable parse mode (jfs_zstd_seek_csum_mode):
-    "off", or "on" -- while the Zstd parse mode is "seekable" the compress calls
-    write seek tables with a checksum per frame."""
-    m = L.load().jfs_zstd_seek_csum_mode()
-    return next(k for k, v in _SEEK_CSUM.items() if v == m)
-
-
-def set_zstd_seek_csum_mode(mode: str) -> str:
-    """Set it (process-wide, for calls that start afterwards) and return the
-    previous value's name."""
-    if mode not in _SEEK_CSUM:
-        raise ValueError(f"zstd seek checksum mode {mode!r}: expected 'off' or 'on'")
-    prev = L.load().jfs_set_zstd_seek_csum_mode(_SEEK_CSUM[mode])
-    return next(k for k, v in _SEEK_CSUM.items() if v == prev)
 
 
 def seek_plan(tail: bytes, object_len: int, lo: int, hi: int) -> dict:

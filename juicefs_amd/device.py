@@ -13,6 +13,9 @@ import numpy as np
 import torch
 
 from . import _lib as L
+# the counter readers of the device calls, built from the table in switches.py
+from .switches import (lz4_chase_counts, lz4_eseg_counts, lz4_split_counts, lz4_window_counts,  # noqa: F401
+                       zstd_sparse_counts, zstd_split_counts, zstd_split_frame_counts)
 
 DESC_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("src_len", "<i4"), ("dst_cap", "<i4")])
 assert DESC_DTYPE.itemsize == ctypes.sizeof(L.JfsDevBlock)
@@ -96,31 +99,6 @@ def zstd_decompress_prefix(desc: torch.Tensor, want: torch.Tensor, ret: torch.Te
                                                       _stream_ptr(stream)), "jfs_zstd_decompress_prefix_device")
 
 
-def lz4_split_counts(reset: bool = False):
-    """(blocks the small-batch path decoded itself, blocks it handed to the
-    one-workgroup kernel, ... the reasons: fix-up, jumping, token, no last run)
-    on the current device."""
-    out = (ctypes.c_uint64 * 6)()
-    _check(L.load().jfs_lz4_split_counts(out, 1 if reset else 0), "jfs_lz4_split_counts")
-    return tuple(int(x) for x in out)
-
-
-def zstd_split_counts(reset: bool = False):
-    """(inputs the Zstd small-batch path replayed itself, inputs it handed to
-    the exact one-wave replay) on the current device."""
-    out = (ctypes.c_uint64 * 2)()
-    _check(L.load().jfs_zstd_split_counts(out, 1 if reset else 0), "jfs_zstd_split_counts")
-    return tuple(int(x) for x in out)
-
-
-def zstd_split_frame_counts(reset: bool = False):
-    """(multi-frame inputs -- two frames or more -- the Zstd small-batch path
-    replayed itself, the frames they held) on the current device."""
-    out = (ctypes.c_uint64 * 2)()
-    _check(L.load().jfs_zstd_split_frame_counts(out, 1 if reset else 0), "jfs_zstd_split_frame_counts")
-    return tuple(int(x) for x in out)
-
-
 def set_split_jump_rounds(lz4: int = 0, zstd: int = 0):
     """Test hook (jfs_test_set_split_jump_rounds): the pointer-jumping rounds
     the small-batch decoders launch, full and prefix; 0 = the computed count.
@@ -166,14 +144,6 @@ def lz4_compress_fast_lift(desc: torch.Tensor, ret: torch.Tensor, src_lens, lift
     _check(L.load().jfs_lz4_compress_fast_lift_device(
         desc.data_ptr(), sl, n, lift.data_ptr(), src_desc.data_ptr(), src_n.data_ptr(), ssl, scp, ns, ret.data_ptr(),
         lifted.data_ptr() if lifted is not None else None, _stream_ptr(stream)), "jfs_lz4_compress_fast_lift_device")
-
-
-def lz4_eseg_counts(reset: bool = False):
-    """Segment encoder: {rounds: blocks settled after that many rounds}, with
-    0 = blocks handed to the serial kernel."""
-    out = (ctypes.c_uint64 * 17)()
-    _check(L.load().jfs_lz4_eseg_counts(out, 1 if reset else 0), "jfs_lz4_eseg_counts")
-    return {i: int(x) for i, x in enumerate(out) if x}
 
 
 def zstd_decompress(desc: torch.Tensor, ret: torch.Tensor, stream=None):
@@ -272,23 +242,6 @@ def lz4_decompress_window(desc: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor
            "jfs_lz4_decompress_window_device_small")
 
 
-def lz4_window_counts(reset: bool = False):
-    """(blocks the window decode took from a floor above 0, blocks whose probe
-    sent them to floor 0, blocks handed to the exact kernel, origin entries
-    written) on the current device."""
-    out = (ctypes.c_uint64 * 4)()
-    _check(L.load().jfs_lz4_window_counts(out, 1 if reset else 0), "jfs_lz4_window_counts")
-    return tuple(int(x) for x in out)
-
-
-def lz4_chase_counts(reset: bool = False):
-    """(blocks the origin chase resolved, bytes requested of them, chain steps
-    taken, blocks handed to the prefix path) on the current device."""
-    out = (ctypes.c_uint64 * 4)()
-    _check(L.load().jfs_lz4_chase_counts(out, 1 if reset else 0), "jfs_lz4_chase_counts")
-    return tuple(int(x) for x in out)
-
-
 SPLICE_FRAME_DTYPE = np.dtype([("src", "<u8"), ("c", "<i4"), ("d", "<i4"), ("x", "<u4"), ("unit", "<i4"), ("out", "<i4"),
                                ("reserved", "<i4")])
 SPLICE_OUT_DTYPE = np.dtype([("dst", "<u8"), ("dst_cap", "<i4"), ("frame_first", "<i4"), ("frame_count", "<i4"),
@@ -332,14 +285,6 @@ def zstd_seek_tables(desc: torch.Tensor, lens: torch.Tensor, slot_first: torch.T
     _check(L.load().jfs_zstd_seek_tables_device(desc.data_ptr(), lens.data_ptr(), n, slot_first.data_ptr(),
                                                 tables.data_ptr(), table_len.data_ptr(), _stream_ptr(stream)),
            "jfs_zstd_seek_tables_device")
-
-
-def zstd_sparse_counts(reset: bool = False):
-    """(inputs the ranges decode took through a seek table, frames it selected,
-    frames whose checksum it compared) on the current device."""
-    out = (ctypes.c_uint64 * 3)()
-    _check(L.load().jfs_zstd_sparse_counts(out, 1 if reset else 0), "jfs_zstd_sparse_counts")
-    return tuple(int(x) for x in out)
 
 
 def xxh64(desc: torch.Tensor, hash: torch.Tensor, ret: torch.Tensor | None = None, stream=None):

@@ -29,6 +29,8 @@ ENUMS = [
      {"off": H["JFS_READ_SEEK_OFF"], "on": H["JFS_READ_SEEK_ON"], "sparse": H["JFS_READ_SEEK_SPARSE"]}, 2),
     ("JFS_READ_LZ4_CHASE", "jfs_read_lz4_chase_mode", "jfs_set_read_lz4_chase_mode", None,
      {"off": H["JFS_READ_LZ4_CHASE_OFF"], "on": H["JFS_READ_LZ4_CHASE_ON"]}, 2),
+    ("JFS_READ_LZ4_WINDOW", "jfs_read_lz4_window_mode", "jfs_set_read_lz4_window_mode", None,
+     {"off": H["JFS_READ_LZ4_WINDOW_OFF"], "on": H["JFS_READ_LZ4_WINDOW_ON"]}, 2),
     ("JFS_ZSTD_PARSE", "jfs_zstd_parse_mode", "jfs_set_zstd_parse_mode", "jfs_set_zstd_parse_mode_ext",
      {"exact": H["JFS_ZSTD_PARSE_EXACT"], "fast": H["JFS_ZSTD_PARSE_FAST"],
       "seekable": H["JFS_ZSTD_PARSE_SEEKABLE"]}, 2),
@@ -36,6 +38,8 @@ ENUMS = [
      {"off": H["JFS_ZSTD_SEEK_CSUM_OFF"], "on": H["JFS_ZSTD_SEEK_CSUM_ON"]}, 2),
     ("JFS_COMPACT_SPLICE", "jfs_compact_splice_mode", "jfs_set_compact_splice_mode", "jfs_set_compact_splice_mode_ext",
      {"off": H["JFS_COMPACT_SPLICE_OFF"], "on": H["JFS_COMPACT_SPLICE_ON"], "all": H["JFS_COMPACT_SPLICE_ALL"]}, 2),
+    ("JFS_COMPACT_LZ4_LIFT", "jfs_compact_lz4_lift_mode", "jfs_set_compact_lz4_lift_mode", None,
+     {"off": H["JFS_COMPACT_LZ4_LIFT_OFF"], "on": H["JFS_COMPACT_LZ4_LIFT_ON"]}, 2),
 ]
 # integer: variable, getter, setter, default, closed range
 INTS = [
