@@ -67,8 +67,9 @@ EXPORTS = [
 ]
 # the hook include/jfs_gpucodec_lz4_fast_test.h declares (the fast LZ4 encoder's host twin)
 LZ4_FAST_TEST_EXPORTS = ["jfs_test_lz4_fast_host"]
-# and the hook of the lift's tests in the same header (the fast encoder's chunks per launch group)
-LZ4_LIFT_TEST_EXPORTS = ["jfs_test_set_lz4_fast_group_chunks"]
+# and the hooks of the lift's tests in the same header (the fast encoder's chunks per launch group; the host
+# twin with chunks lifted)
+LZ4_LIFT_TEST_EXPORTS = ["jfs_test_set_lz4_fast_group_chunks", "jfs_test_lz4_fast_lift_host"]
 # the hooks include/jfs_gpucodec_zstd_fast_test.h declares (the fast Zstd parse: host twin, kernels)
 ZSTD_FAST_TEST_EXPORTS = ["jfs_test_zstd_fast_host_seqs", "jfs_test_zstd_fast_seqs_device"]
 
@@ -228,6 +229,8 @@ def load() -> ctypes.CDLL:
     lib.jfs_test_set_lz4_fast_group_chunks.restype = ctypes.c_int
     lib.jfs_test_lz4_fast_host.argtypes = [vp, i64, vp, i64]
     lib.jfs_test_lz4_fast_host.restype = i64
+    lib.jfs_test_lz4_fast_lift_host.argtypes = [vp, i64, vp, i64, vp, ctypes.c_int, vp, vp, vp, vp, vp]
+    lib.jfs_test_lz4_fast_lift_host.restype = i64
     for f in (lib.jfs_test_zstd_fast_host_seqs, lib.jfs_test_zstd_fast_seqs_device):
         f.argtypes = [vp, i64, vp, i64, vp, vp]
         f.restype = i64

@@ -280,6 +280,34 @@ def lz4_fast_host(src) -> bytes:
     return dst.raw[:n]
 
 
+def lz4_fast_lift_host(src, lift, streams, src_caps):
+    """The host twin with chunks lifted (jfs_test_lz4_fast_lift_host, test
+    infrastructure): the bytes jfs_lz4_compress_fast_lift_device writes for the
+    gathered block src.  lift: one (source, source chunk) per 64 KiB chunk of
+    src, source < 0 for none; streams: the sources' stored LZ4 blocks;
+    src_caps: their decode capacities.  Returns (bytes, chunks lifted, per chunk
+    a lifted chunk's record count or -1)."""
+    import numpy as np
+    lib = L.load()
+    src = bytes(src)
+    nch = (len(src) + 65535) // 65536
+    if len(lift) != nch or len(src_caps) != len(streams):
+        raise ValueError("lz4_fast_lift_host: one candidate per chunk, one capacity per stream")
+    flat = np.array([x for pair in lift for x in pair], dtype=np.int32).reshape(-1)
+    bufs = [bytes(s) for s in streams]
+    ptrs = (ctypes.c_char_p * max(len(bufs), 1))(*bufs)
+    lens = np.array([len(s) for s in bufs], dtype=np.int32)
+    caps = np.array(list(src_caps), dtype=np.int32)
+    nrec = np.full(max(nch, 1), -1, dtype=np.int32)
+    lifted = ctypes.c_int32(0)
+    cap = int(lib.jfs_compress_bound(L.ALGO_LZ4, len(src)))
+    dst = ctypes.create_string_buffer(max(cap, 1))
+    n = int(lib.jfs_test_lz4_fast_lift_host(ctypes.addressof(dst), cap, src, len(src), flat.ctypes.data, len(bufs),
+                                            ctypes.addressof(ptrs), lens.ctypes.data, caps.ctypes.data,
+                                            ctypes.addressof(lifted), nrec.ctypes.data))
+    return dst.raw[:n], int(lifted.value), nrec[:nch].tolist()
+
+
 _PLAN_STATUS = {L.SEEK_PLAN_OK: "ok", L.SEEK_PLAN_MORE: "more", L.SEEK_PLAN_NONE: "none"}
 
 

@@ -8,6 +8,7 @@
 
 #include "../../include/jfs_gpucodec_lz4_fast_test.h"
 #include "lz4_fast.h"
+#include "lz4_lift.h"
 
 namespace {
 using namespace jfs::lz4f;
@@ -79,7 +80,7 @@ uint8_t *put_len(uint8_t *o, int64_t v) {  // v = length - 15 already checked >=
 
 // The block of the sequences recs over src and `carry` trailing literals (stitch
 // and emit): its size, or 0 and not a byte when it does not fit dst_cap.
-// (tests/lz4_lift_main.cc includes this file and feeds it lifted records.)
+// (the records may be lifted ones: jfs_test_lz4_fast_lift_host below.)
 int64_t emit_block(uint8_t *dst, int64_t dst_cap, const uint8_t *src, const std::vector<Rec> &recs, int64_t carry) {
     int64_t total = 1 + len_bytes(carry) + carry;
     for (const Rec &r : recs) total += 1 + len_bytes(r.lit) + r.lit + 2 + len_bytes(r.mlen - kMinMatch);
@@ -113,5 +114,41 @@ extern "C" int64_t jfs_test_lz4_fast_host(uint8_t *dst, int64_t dst_cap, const u
         const int64_t clen = n - cbase < kChunk ? n - cbase : kChunk;
         carry = parse_chunk(src + cbase, n, cbase, clen, carry, recs);
     }
+    return emit_block(dst, dst_cap, src, recs, carry);
+}
+
+// The lift form (lz4_lift.h): a chunk the lift takes contributes the
+// records lift_host reads from its source's stored stream, as stitch joins them
+// to the chunks around it; every other chunk is parsed.
+extern "C" int64_t jfs_test_lz4_fast_lift_host(uint8_t *dst, int64_t dst_cap, const uint8_t *src, int64_t n,
+                                               const int32_t *lift, int nsrc, const uint8_t *const *stream,
+                                               const int32_t *stream_len, const int32_t *src_cap, int32_t *lifted,
+                                               int32_t *chunk_nrec) {
+    namespace lz4l = jfs::lz4l;
+    if (lifted) *lifted = 0;
+    if (n < 0 || n > kMaxInput || dst_cap < 0) return 0;
+    std::vector<Rec> recs;
+    int64_t carry = 0;
+    int32_t count = 0;
+    for (int64_t cbase = 0; cbase < n; cbase += kChunk) {
+        const int64_t clen = n - cbase < kChunk ? n - cbase : kChunk, j = cbase >> kChunkLog;
+        const int32_t s = lift[2 * j], i = lift[2 * j + 1];
+        bool take = lz4l::interior(j, n) && s >= 0 && s < nsrc && lz4l::interior(i, src_cap[s]) && stream_len[s] >= 0;
+        if (take) {
+            const lz4l::Lifted r = lz4l::lift_host(stream[s], stream_len[s], i);
+            take = r.ok && r.total <= src_cap[s];
+            // what stitch does with a chunk's results
+            for (int32_t k = 0; take && k < r.nrec; k++)
+                recs.push_back({(int64_t)(r.y[k] >> 16) + (k ? 0 : carry), (int32_t)(r.x[k] >> 16), (int32_t)(r.y[k] & 0xffff)});
+            if (take) carry = r.nrec ? r.tail : carry + r.tail;
+            if (take && chunk_nrec) chunk_nrec[j] = r.nrec;
+            count += take;
+        }
+        if (!take) {
+            carry = parse_chunk(src + cbase, n, cbase, clen, carry, recs);
+            if (chunk_nrec) chunk_nrec[j] = -1;
+        }
+    }
+    if (lifted) *lifted = count;
     return emit_block(dst, dst_cap, src, recs, carry);
 }

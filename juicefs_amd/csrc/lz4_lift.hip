@@ -135,9 +135,15 @@ __global__ __launch_bounds__(64) void lift_kernel(const jfs_dev_block *__restric
     const gc_u8 *s = (const gc_u8 *)B.src;
     gc_i32 *entry = (gc_i32 *)(ix.sc.entry + B.seg0), *cnt = (gc_i32 *)(ix.sc.cnt + B.seg0);
     const int32_t k0 = seg_at(cnt, B.nseg, F), k1 = seg_at(cnt, B.nseg, E - 1);
-    // A chunk's stored bytes span some 260 segments at most (a sequence of four output bytes takes three stored
-    // ones at least): kRounds rounds of 64.  A stream that spreads a chunk wider is none of the fast encoder's.
-    if (k1 - k0 >= 64 * kRounds) return;
+    // Segment k0 holds the token of the sequence that reaches F.  Its literals may begin any distance below F --
+    // the trailing literals of the chunks in front, whole chunks without a match among them -- so the segments
+    // behind k0 may hold no token for any length: they share the cnt of kA, the next segment that holds one.  The
+    // chunk is taken as k0, then kA .. k1.  From kA on the tokens' output lies inside the chunk, whose stored bytes
+    // span some 260 segments at most (a sequence of four output bytes takes three stored ones at least): kRounds
+    // rounds of 64.  A stream that spreads a chunk wider is none of the fast encoder's.
+    const int32_t kA = k0 < k1 ? seg_at(cnt, B.nseg, cnt[k0 + 1]) : k0 + 1;
+    if (k1 - kA + 2 > 64 * kRounds) return;
+    const auto seg_of = [&](int32_t idx) { return idx == 0 ? k0 : kA + idx - 1; };  // (> k1: none)
     // pass 1: the rule, and per round every lane's first record index (a wave prefix sum of its count), its body
     // and its last match's end
     int32_t first[kRounds];
@@ -146,7 +152,7 @@ __global__ __launch_bounds__(64) void lift_kernel(const jfs_dev_block *__restric
     bool good = true;
 #pragma unroll
     for (int r = 0; r < kRounds; r++) {
-        const int32_t k = k0 + 64 * r + lane;
+        const int32_t k = seg_of(64 * r + lane);
         int32_t mine = 0, mend = 0;
         uint32_t mbody = 0;
         bool ok = true;
@@ -172,7 +178,7 @@ __global__ __launch_bounds__(64) void lift_kernel(const jfs_dev_block *__restric
     int32_t lit0 = 0;
 #pragma unroll
     for (int r = 0; r < kRounds; r++) {
-        const int32_t k = k0 + 64 * r + lane;
+        const int32_t k = seg_of(64 * r + lane);
         int32_t at = first[r];
         if (k <= k1)
             walk(s, B.n, k, entry[k], cnt[k], F, [&](int32_t a, int32_t m, int32_t ml, int32_t off) {

@@ -8,6 +8,9 @@
 //   2  [u32 n][n bytes A][n bytes B]     two blocks to encode, B an overwrite of A
 //   3  [u32 nout][u32 nsrc][i32 cap * nsrc] then per output
 //      [i32 total][u32 nseg][{src, src_off, dst_off, len} * nseg]   a compaction plan
+//   4  [u32 n][u32 nsrc] then per source [i32 len][i32 cap][len bytes], then
+//      [n bytes G][{i32 src, i32 src_chunk} * chunks of n]   a gathered block, the
+//      stored sources and their decode capacities, and a candidate per chunk
 // and one line per record:
 //   lift I total T ok L nrec R tail X lit0 Y body B first P:M:O:L valid V
 //      the serial restatement's answer (lift_host); first = record 0's pos, mlen,
@@ -16,11 +19,15 @@
 //      place, the literals between the matches tile the chunk, and nrec, tail,
 //      lit0 and body are parse_kernel's formulas over them
 //   det I n N chunks C lifted K refused R same S
-//      A and B encoded by the fast encoder's host twin; B encoded again with the
-//      records of every interior chunk that A and B share lifted from A's stream
-//      and the other chunks parsed; same = the two encodings of B are equal
+//      A and B encoded by the fast encoder's host twin; B encoded again by
+//      jfs_test_lz4_fast_lift_host with every interior chunk that A and B share
+//      a candidate from A's stream; same = the two encodings of B are equal
 //   plan I cand b:j:src:i,... srcs a,b,... per_out x,y,...
 //      lift_plan's candidates ("-": none)
+//   emit I n N size S crc C lifted K valid V nrec r,r,...
+//      jfs_test_lz4_fast_lift_host over G: the block's size, zlib's CRC-32 of its
+//      bytes, the chunks lifted, valid = the serial interpreter decodes the block
+//      to G, and per chunk the lifted records' count or -1 for a parsed chunk
 // The last line checks the switch's row of host_modes.h.
 #include <stdint.h>
 #include <stdio.h>
@@ -29,7 +36,7 @@
 #include <vector>
 
 #include "host_modes.h"
-#include "lz4_fast_host.cc"  // the host twin's parse_chunk, Rec and emit_block
+#include "lz4_fast_host.cc"  // the host twin and its lift form
 #include "lz4_lift.h"
 
 namespace lz4l = jfs::lz4l;
@@ -97,6 +104,16 @@ static std::vector<uint8_t> twin(const std::vector<uint8_t> &src) {
     return dst;
 }
 
+// zlib's CRC-32 (reflected 0xedb88320), bit by bit
+static uint32_t crc32(const uint8_t *p, int64_t n) {
+    uint32_t c = 0xffffffffu;
+    for (int64_t i = 0; i < n; i++) {
+        c ^= p[i];
+        for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xedb88320u & (0u - (c & 1)));
+    }
+    return ~c;
+}
+
 static int check_mode_row() {
     using namespace jfs_host;
     const ModeDesc &d = MODE_COMPACT_LZ4_LIFT;
@@ -138,27 +155,23 @@ int main(int argc, char **argv) {
             std::vector<uint8_t> A(n), B(n);
             if (!rd(f, A.data(), n) || !rd(f, B.data(), n)) return 2;
             const std::vector<uint8_t> ea = twin(A), eb = twin(B);
-            std::vector<Rec> recs;
-            int64_t carry = 0, lifted = 0, refused = 0, chunks = 0;
+            // the candidates: every interior chunk that A and B share, from A's stream
+            std::vector<int32_t> lift;
+            int64_t cand = 0, chunks = 0;
             for (int64_t cbase = 0; cbase < n; cbase += kChunk, chunks++) {
-                const int64_t clen = n - cbase < kChunk ? n - cbase : kChunk, c = cbase >> kChunkLog;
-                bool take = lz4l::interior(c, n) && memcmp(A.data() + cbase, B.data() + cbase, (size_t)kChunk) == 0;
-                if (take) {
-                    const lz4l::Lifted r = lz4l::lift_host(ea.data(), (int32_t)ea.size(), (int32_t)c);
-                    take = r.ok;
-                    refused += !r.ok;
-                    // what stitch does with a chunk's results
-                    for (int32_t k = 0; take && k < r.nrec; k++) {
-                        recs.push_back({(int64_t)(r.y[k] >> 16) + (k ? 0 : carry), (int32_t)(r.x[k] >> 16),
-                                        (int32_t)(r.y[k] & 0xffff)});
-                    }
-                    if (take) carry = r.nrec ? r.tail : carry + r.tail;
-                    lifted += take;
-                }
-                if (!take) carry = parse_chunk(B.data() + cbase, n, cbase, clen, carry, recs);
+                const int64_t c = cbase >> kChunkLog;
+                const bool take = lz4l::interior(c, n) && memcmp(A.data() + cbase, B.data() + cbase, (size_t)kChunk) == 0;
+                lift.push_back(take ? 0 : -1);
+                lift.push_back(take ? (int32_t)c : 0);
+                cand += take;
             }
+            const uint8_t *stream = ea.data();
+            const int32_t slen = (int32_t)ea.size(), cap = (int32_t)n;
+            int32_t lifted = 0;
             std::vector<uint8_t> out(eb.size() + 64);
-            const int64_t got = n ? emit_block(out.data(), (int64_t)out.size(), B.data(), recs, carry) : -1;
+            const int64_t got = jfs_test_lz4_fast_lift_host(out.data(), (int64_t)out.size(), B.data(), n, lift.data(), 1, &stream,
+                                                            &slen, &cap, &lifted, nullptr);
+            const int64_t refused = cand - lifted;
             const bool same = got == (int64_t)eb.size() && memcmp(out.data(), eb.data(), eb.size()) == 0;
             printf("det %d n %u chunks %lld lifted %lld refused %lld same %d\n", cases, n, (long long)chunks,
                    (long long)lifted, (long long)refused, (int)same);
@@ -190,6 +203,33 @@ int main(int argc, char **argv) {
             printf("%s per_out ", P.srcs.empty() ? "-" : "");
             for (uint32_t k = 0; k < nout; k++) printf("%s%d", k ? "," : "", P.per_out[k]);
             printf("\n");
+        } else if (kind == 4) {
+            uint32_t nsrc = 0;
+            if (!rd(f, &n, 4) || !rd(f, &nsrc, 4) || n > (1u << 28) || nsrc > 4096) return 2;
+            std::vector<int32_t> slen(nsrc), cap(nsrc);
+            std::vector<std::vector<uint8_t>> streams(nsrc);
+            std::vector<const uint8_t *> ptr(nsrc);
+            for (uint32_t i = 0; i < nsrc; i++) {
+                if (!rd(f, &slen[i], 4) || !rd(f, &cap[i], 4) || slen[i] < 0 || slen[i] > (1 << 28)) return 2;
+                streams[i].resize((size_t)slen[i]);
+                if (!rd(f, streams[i].data(), (size_t)slen[i])) return 2;
+                ptr[i] = streams[i].data();
+            }
+            const int64_t nc = nchunks(n);
+            std::vector<uint8_t> G(n);
+            std::vector<int32_t> lift(2 * (size_t)nc), nrec((size_t)nc, -2);
+            if (!rd(f, G.data(), n) || !rd(f, lift.data(), 8 * (size_t)nc)) return 2;
+            std::vector<uint8_t> out((size_t)n + n / 255 + 64);
+            int32_t lifted = -1;
+            const int64_t got = jfs_test_lz4_fast_lift_host(out.data(), (int64_t)out.size(), G.data(), n, lift.data(), (int)nsrc,
+                                                            ptr.data(), slen.data(), cap.data(), &lifted, nrec.data());
+            // the block is a block of G, whatever was lifted
+            const std::vector<uint8_t> back = interpret(out.data(), got);
+            const bool valid = got > 0 && back == G;
+            printf("emit %d n %u size %lld crc %u lifted %d valid %d nrec ", cases, n, (long long)got, crc32(out.data(), got),
+                   lifted, (int)valid);
+            for (int64_t j = 0; j < nc; j++) printf("%s%d", j ? "," : "", nrec[(size_t)j]);
+            printf("%s\n", nc ? "" : "-");
         } else {
             return 2;
         }

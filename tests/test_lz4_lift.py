@@ -13,6 +13,7 @@ import re
 import shutil
 import struct
 import subprocess
+import zlib
 
 import numpy as np
 import pytest
@@ -22,6 +23,8 @@ from juicefs_amd import compress as C
 from juicefs_amd.blockgen import gen_block
 from tests import lz4_chase_cases as K
 from tests import lz4_fast_cases as F
+from tests import lz4_lift_cases as LC
+from tests.lz4_lift_cases import directed, fill  # noqa: F401  (the streams, shared with the device's tests)
 from tests.test_modes import H, _check_setter, _children, _mixed
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -131,47 +134,6 @@ def test_host_plan_directed(built):
         assert row == (cand, srcs, per), (name, row)
 
 
-def fill(seed, upto, at, ml=30, off=9):
-    """one sequence from output position `at` whose match ends exactly at `upto`"""
-    return K.seq(_rand(seed, upto - at - ml), ml, off)
-
-
-def directed():
-    """[(name, stream, chunk, ok, expected fields or None)]"""
-    out = []
-    tail = K.last(_rand(99, 100))
-    ends = K.seq(_rand(1, CH - 20), 20, 100) + K.seq(_rand(2, CH - 50), 50, 30) + tail
-    out.append(("match-ends-on-E", ends, 1, 1, dict(nrec=1, tail=0, lit0=CH - 50, pos=CH - 50, mlen=50, off=30, lit=CH - 50)))
-    out.append(("match-ends-on-E-chunk-0", ends, 0, 1, dict(nrec=1, tail=0, lit0=CH - 20, pos=CH - 20, mlen=20, off=100)))
-    cross = K.seq(_rand(3, CH - 6), 20, 10) + fill(4, 2 * CH, CH + 14) + tail
-    out.append(("match-straddles-F", cross, 1, 0, None))
-    out.append(("match-straddles-E", cross, 0, 0, None))
-    on = K.seq(_rand(5, CH), 300, 1) + fill(6, 2 * CH, CH + 300) + tail
-    out.append(("overlap-off1-on-F", on, 1, 0, None))
-    behind = K.seq(_rand(7, CH + 1), 300, 1) + fill(8, 2 * CH, CH + 301) + tail
-    out.append(("overlap-off1-behind-one-literal", behind, 1, 1, dict(nrec=2, tail=0, lit0=1, pos=1, mlen=300, off=1, lit=1)))
-    lits = K.seq(_rand(9, 65000), 8, 50) + K.seq(_rand(10, 1000), 10, 20) + fill(11, 2 * CH, 66018) + tail
-    out.append(("literals-across-F", lits, 1, 1, dict(nrec=2, tail=0, lit0=472, pos=472, mlen=10, off=20, lit=472)))
-    none = K.seq(_rand(12, 100), 8, 50) + K.seq(_rand(13, 2 * CH + 500), 12, 9) + tail
-    out.append(("no-match", none, 1, 1, dict(nrec=0, tail=CH, lit0=0, body=0)))
-    far = K.seq(_rand(14, CH + 100), 16, 300) + fill(15, 2 * CH, CH + 116) + tail
-    out.append(("offset-reaches-below-F", far, 1, 0, None))
-    # kMaxRec four-byte matches tile a chunk only with the first on F, which copies from below it: refused by the
-    # offset rule (the count rule cannot be met with more, matches being four bytes at least); behind four literals
-    # the chunk holds kMaxRec - 1 of them and is lifted
-    head = K.seq(_rand(16, CH - 8), 8, 20)
-    out.append(("kMaxRec-matches", head + K.seq(b"", 4, 4) * MAX_REC + tail, 1, 0, None))
-    out.append(("kMaxRec-less-one", head + K.seq(_rand(17, 4), 4, 4) + K.seq(b"", 4, 4) * (MAX_REC - 2) + tail, 1, 1,
-                dict(nrec=MAX_REC - 1, tail=0, lit0=4, pos=4, mlen=4, off=4, lit=4)))
-    # the source's true length: the chunk must be interior in it
-    short = K.seq(_rand(18, CH - 20), 20, 100) + K.last(_rand(19, 11))
-    out.append(("eleven-bytes-follow", short, 0, 0, None))
-    out.append(("twelve-bytes-follow", K.seq(_rand(18, CH - 20), 20, 100) + K.last(_rand(19, 12)), 0, 1, dict(nrec=1, tail=0)))
-    out.append(("chunk-past-the-end", ends, 2, 0, None))
-    out.append(("negative-chunk", ends, -1, 0, None))
-    return out
-
-
 def test_rule_on_hand_made_streams(built):
     cases = directed()
     rows = lift_rows(run_driver(built, b"".join(lift_rec(s, c) for _, s, c, _, _ in cases)))
@@ -192,6 +154,98 @@ def test_rule_on_hand_made_streams(built):
     (l0, _, m0, _), (l1, _, _, _) = by["literals-across-F"][:2]
     assert l0 + m0 < CH < l0 + m0 + l1
     assert len(by["kMaxRec-matches"]) == MAX_REC + 2
+
+
+def test_new_streams_are_what_their_names_say():
+    by = {name: (s, K.sequences(s), LC.token_starts(s)) for name, s, *_ in directed()}
+    assert all(len(s) < 4 * CH for s, _, _ in by.values())
+    _, seqs, _ = by["longest-match"]
+    assert seqs[0] == (CH + 1, seqs[0][1], 65535, 1) and len(K.seq(b"", 65535, 1)) == 1 + 2 + 257
+    _, seqs, _ = by["longest-literal-run"]
+    assert seqs[0][0] + seqs[0][2] == CH and seqs[1][0] == 65532 and seqs[1][2] == 4 and seqs[1][3] <= 65532
+    _, seqs, _ = by["literals-begin-below-F"]
+    assert seqs[0][0] + seqs[0][2] == CH - 200 and seqs[1][0] == 300
+    # the tokens of the sequences whose matches lie in chunk 1 start in 257 segments: rounds 0 to 3 take 256
+    _, seqs, starts = by["records-in-the-fifth-round"]
+    segs = [pos // LC.SEG for (pos, op), (ll, _, ml, _) in zip(starts, seqs) if ml and CH <= op + ll < 2 * CH]
+    assert len(segs) == CH // 64 and segs[-1] - segs[0] == 256
+    # the chunk's first token: at 253 mod 256, three literal-length bytes on both sides of the edge, and 238
+    # match-length bytes across another
+    s, seqs, starts = by["token-spans-a-segment-edge"]
+    (pos, op), (ll, lit, ml, off) = starts[1], seqs[1]
+    assert op == CH and pos % LC.SEG == 253 and lit - pos == 4 and ll == 530 and off <= ll
+    mlb = lit + ll + 2
+    assert starts[2][0] - mlb == 238 and mlb // LC.SEG != (starts[2][0] - 1) // LC.SEG
+
+
+def emit_rec(out, lift, streams, caps):
+    b = struct.pack("<III", 4, len(out), len(streams))
+    for s, cap in zip(streams, caps):
+        b += struct.pack("<ii", len(s), cap) + s
+    return b + out + b"".join(struct.pack("<ii", *c) for c in lift)
+
+
+def emit_rows(lines):
+    return [(int(n), int(size), int(crc), int(lifted), int(valid), [int(x) for x in nrec.split(",")])
+            for n, size, crc, lifted, valid, nrec in re.findall(
+                r"^emit \d+ n (\d+) size (\d+) crc (\d+) lifted (\d+) valid (\d+) nrec (\S+)$", "\n".join(lines), re.M)]
+
+
+def real_encoder_blocks():
+    return [LC.unshared_block(40 + i) for i in range(4)]
+
+
+def zero_record_blocks():
+    """(outs, lift, stored streams): the overwrite in the last whole chunk, and in chunk 0"""
+    raws = [LC.zero_record_block(50), LC.zero_record_block(60)]
+    outs, lift = LC.overwritten(raws, [3 * CH + 1000, 1000])
+    return outs, lift, [C.lz4_fast_host(r) for r in raws]
+
+
+def test_real_encoder_leaves_chunks_liftable(built, oracle):
+    """the condition tests/test_lz4_lift_foreign_gpu.py rests on: of a block whose chunks share no content, liblz4's
+    parse (which the exact encoder restates byte for byte) leaves three of the four interior chunks liftable at least"""
+    raws = real_encoder_blocks()
+    streams = [oracle.lz4_compress(r)[1] for r in raws]
+    rows = lift_rows(run_driver(built, b"".join(lift_rec(s, c) for s in streams for c in range(4))))
+    assert len(rows) == 16 and all(r["total"] == LC.N and r["valid"] == r["ok"] for r in rows)
+    per = [sum(r["ok"] for r in rows[4 * k:4 * k + 4]) for k in range(4)]
+    assert min(per) >= 3, per
+    # and its records are none the fast parse would leave: the hook's block differs from the fast encoder's
+    got, lifted, _ = C.lz4_fast_lift_host(raws[0], [(0, j) for j in range(4)] + [(-1, 0)], streams[:1], [LC.N])
+    assert lifted == per[0] and got != C.lz4_fast_host(raws[0])
+
+
+def test_hook_equals_the_driver(built, oracle):
+    """jfs_test_lz4_fast_lift_host as the library exports it against the sanitizer-built driver's copy of the same
+    source: size, CRC-32 of the bytes, lifted count and per-chunk record counts, over every hand-made stream, the
+    real encoder's blocks and the zero-record blocks; the driver also decodes each block back to its content"""
+    jobs = []  # (name, out, lift, streams, caps, expected lifted count or None)
+    for name, s, c, ok, _ in directed():
+        total = sum(ll + ml for ll, _, ml, _ in K.sequences(s))
+        out = oracle.lz4_decompress(s, total)[1]
+        assert len(out) == total, name
+        jobs.append((name, out, LC.candidates(c, total), [s], [total], ok))
+    raws = real_encoder_blocks()
+    streams = [oracle.lz4_compress(r)[1] for r in raws]
+    outs, lift = LC.overwritten(raws)
+    assert [sum(s >= 0 for s, _ in l) for l in lift] == LC.PLANNED
+    jobs += [(f"liblz4-{k}", o, l, streams, [LC.N] * 4, None) for k, (o, l) in enumerate(zip(outs, lift))]
+    outs, lift, streams = zero_record_blocks()
+    jobs += [(f"zero-record-{k}", o, l, streams, [LC.N] * 2, 3) for k, (o, l) in enumerate(zip(outs, lift))]
+    rows = emit_rows(run_driver(built, b"".join(emit_rec(o, l, s, c) for _, o, l, s, c, _ in jobs)))
+    assert len(rows) == len(jobs)
+    for (name, out, lift, streams, caps, want), (n, size, crc, lifted, valid, nrec) in zip(jobs, rows):
+        got, glifted, gnrec = C.lz4_fast_lift_host(out, lift, streams, caps)
+        assert (n, valid) == (len(out), 1), name
+        assert (len(got), zlib.crc32(got), glifted, gnrec) == (size, crc, lifted, nrec), name
+        assert want is None or lifted == want, (name, lifted)
+        assert lifted == sum(r >= 0 for r in nrec), name
+        if lifted == 0:
+            assert got == C.lz4_fast_host(out), name
+    # the zero-record blocks: two of the three lifted chunks hold no record
+    for (name, *_), row in zip(jobs[-2:], rows[-2:]):
+        assert sum(r == 0 for r in row[5]) == 2, (name, row[5])
 
 
 def test_exact_encoder_block_has_a_refused_chunk(built, oracle):
@@ -239,8 +293,12 @@ def test_new_symbols_exported(lib):
     for name in ("jfs_lz4_compress_fast_lift_device", "jfs_compact_lz4_lift_mode", "jfs_set_compact_lz4_lift_mode",
                  "jfs_compact_lz4_lift_counts"):
         assert name in L.EXPORTS and hasattr(lib, name) and name + "(" in header, name
-    # the launch-group size is a test hook in the fast encoder's test header, outside the public ABI
-    hook = "jfs_test_set_lz4_fast_group_chunks"
-    assert L.LZ4_LIFT_TEST_EXPORTS == [hook] and hasattr(lib, hook) and hook not in L.EXPORTS
-    assert hook + "(" in open(os.path.join(inc, "jfs_gpucodec_lz4_fast_test.h")).read() and hook not in header
+    # the launch-group size and the host twin's lift form are test hooks in the fast encoder's test header, outside
+    # the public ABI
+    hooks = ["jfs_test_set_lz4_fast_group_chunks", "jfs_test_lz4_fast_lift_host"]
+    assert L.LZ4_LIFT_TEST_EXPORTS == hooks
+    test_header = open(os.path.join(inc, "jfs_gpucodec_lz4_fast_test.h")).read()
+    for hook in hooks:
+        assert hasattr(lib, hook) and hook not in L.EXPORTS
+        assert hook + "(" in test_header and hook not in header
     assert "typedef struct jfs_lz4_lift {" in header

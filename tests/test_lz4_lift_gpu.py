@@ -65,11 +65,13 @@ def pack(dev, blobs, pad=3):
 
 def run_lift(dev, streams, outs, lift, caps=None, src_cap=N):
     """decode the streams on the device, then both encoders over `outs`; returns (ret, dst) of the plain fast
-    encoder, (ret, dst) of the lift call, the lifted counts and the decodes' results"""
+    encoder, (ret, dst) of the lift call, the lifted counts and the decodes' results.  src_cap: the sources' decode
+    capacity, one for all or one each"""
+    scaps = list(src_cap) if isinstance(src_cap, (list, tuple)) else [src_cap] * len(streams)
+    pitch = max(scaps) + 16
+    ddec = torch.full((len(streams) * pitch,), CANARY, dtype=torch.uint8, device=dev)
     dstream, soffs = pack(dev, streams)
-    ddec = torch.full((len(streams) * (src_cap + 16),), CANARY, dtype=torch.uint8, device=dev)
-    sdesc = D.make_desc(dstream, soffs, [len(s) for s in streams], ddec, [i * (src_cap + 16) for i in range(len(streams))],
-                        [src_cap] * len(streams))
+    sdesc = D.make_desc(dstream, soffs, [len(s) for s in streams], ddec, [i * pitch for i in range(len(streams))], scaps)
     src_n = torch.full((len(streams),), -9, dtype=torch.int32, device=dev)
     D.lz4_decompress(sdesc, src_n)
     dgat, goffs = pack(dev, outs)
@@ -89,7 +91,7 @@ def run_lift(dev, streams, outs, lift, caps=None, src_cap=N):
             D.lz4_compress_fast(desc, ret, [len(x) for x in outs])
         else:
             D.lz4_compress_fast_lift(desc, ret, [len(x) for x in outs], dlift, sdesc, src_n, [len(s) for s in streams],
-                                     [src_cap] * len(streams), lifted)
+                                     scaps, lifted)
         torch.cuda.synchronize()
         res.append((ret.cpu().tolist(), ddst.cpu().numpy()))
     return res[0], res[1], lifted.cpu().tolist(), src_n.cpu().tolist(), doffs
